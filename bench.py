@@ -23,17 +23,24 @@ csrc/mi_comm.hip, either way -- what a Go host calls; `--exchange torch` keeps t
                                                  mi_comm_init_all + mi_dedup_allgather_all, no torch in the job
   python -m torch.distributed.run ... bench.py   one process per GPU: mi_comm_init_rank + mi_dedup_allgather; torch
                                                  ships the 128-byte id and runs the host-side barrier (gloo)
-Both refuse to print a line unless ncclCommCount says N, and both first run the N = 1 form of the same per-GPU work
+Both refuse to print a line unless ncclCommCount says N; with --full both first run the N = 1 form of the same per-GPU work
 (`n1_same_run`) so that the line carries `efficiency_vs_n1`.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
+Prints ONE JSON line on rank 0: metric, value (GiB/s), unit, higher_is_better, dtype, ms_per_step (the wall time of one
+timed step), steps, warmup, config, and the per-batch phase times of the timed region.  A plain run does nothing else:
+it sets up, warms up, times --steps steps and prints the line.  --full adds what takes runs of its own:
   roofline     -- the dominant kernel (sha256_items_kernel, chunk pass): algorithmic bytes
                   per launch / its average launch duration measured with HIP events on the
                   engine's own stream, against the 8 TB/s HBM3E peak; plus the VALU roof that
                   actually binds SHA-256.
   cpu_baseline -- the CPU oracle (a port; the Go reference cannot be built here) doing the
                   same work on a bounded sample on this node's host cores.
+  one_batch_at_a_time, clocks, dedup_check, n1_same_run / efficiency_vs_n1 (N > 1), and at N = 1
+  with_rows_on_host, commit_e2e and c3's host-fed rate.
 Only the cpu_baseline leg touches oracle/.
+
+--dump-outputs DIR writes what the last timed step computed (the file and chunk rows its batches hold, a fixed seeded
+sample of larger tables) as .npy files under DIR; the workload is seeded, so the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -448,6 +455,43 @@ def with_rows_leg(makisu_amd, W, config, args, dev_index, inflight, value_withou
                    "host thread that then submits the next batch"}
 
 
+DUMP_MAX_FILE_ROWS = 1 << 16
+DUMP_MAX_CHUNK_ROWS = 1 << 17
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, batches):
+    """--dump-outputs: the rows a caller of the timed path receives for the last timed step (mi_batch_files + mi_batch_chunks of
+    the step's batches, concatenated in order) as float64 / float32 .npy files under `path`.  Larger tables are a fixed, seeded
+    sample of their rows (`*_rows` holds the row numbers); digests and roots go out byte by byte.  The inputs are the seeded
+    workload, so two builds given the same arguments can be compared file by file."""
+    import makisu_amd
+    files = np.concatenate([b.files() for b in batches]) if batches else np.zeros(0, makisu_amd.FILE_DTYPE)
+    chunks = np.concatenate([b.chunks() for b in batches]) if batches else np.zeros(0, makisu_amd.CHUNK_DTYPE)
+
+    def sample(n, cap, salt):
+        if n <= cap:
+            return np.arange(n, dtype=np.int64)
+        return np.sort(np.random.default_rng([SEED, salt]).choice(n, cap, replace=False))
+    fi, ci = sample(len(files), DUMP_MAX_FILE_ROWS, 1), sample(len(chunks), DUMP_MAX_CHUNK_ROWS, 2)
+    f, c = files[fi], chunks[ci]
+    arrays = {"counts": np.array([len(files), len(chunks)], dtype=np.float64),
+              "file_rows": fi.astype(np.float64), "chunk_rows": ci.astype(np.float64)}
+    for k in ("user_tag", "size", "first_chunk", "n_chunks", "crc32"):
+        arrays["file_" + k] = f[k].astype(np.float64)
+    for k in ("chunk_root", "file_sha256"):
+        arrays["file_" + k] = f[k].astype(np.float32)
+    for k in ("file_index", "offset", "length", "dup_of"):
+        arrays["chunk_" + k] = c[k].astype(np.float64)
+    arrays["chunk_sha256"] = c["sha256"].astype(np.float32)
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_MAX_BYTES, total
+    os.makedirs(path, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return total
+
+
 def closed_form_check(got, expect):
     """Distinct contents are independent random streams, so chunks of different contents differ -- except the
     shortest ones: a cut candidate on a file's second-to-last byte leaves a 1-BYTE tail chunk (P = 2^-13 per
@@ -463,14 +507,20 @@ def reexec_under_torchrun(n, reason):
     """The bare form could not bring its communicator up (or hung doing so): the same job once more as the driver's other
     launch form -- one process per GPU under torch.distributed.run, whose own chain (native communicator per rank, then the
     torch.distributed driver of the same exchange) gets its chance -- so that a first contact with N real GPUs still ends
-    in a line, and the line says which path produced it (config.launch_note).  Replaces this process."""
+    in a line, and the line says which path produced it (config.launch_note).  The job runs as a CHILD process (this one has
+    the GPU open, and a thread of it may still be stuck in the collective library): this process waits for it and leaves
+    with its exit status, without running its own teardown."""
+    import subprocess
     print("bench.py: %s -- re-executing under torch.distributed.run" % reason, file=sys.stderr, flush=True)
     env = dict(os.environ, MI_BENCH_REEXEC_REASON=reason[:800])
     port = 29600 + os.getpid() % 300
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
     sys.stdout.flush()
-    os.execve(sys.executable, cmd, env)
+    rc = subprocess.run(cmd, env=env).returncode
+    sys.stdout.flush()
+    sys.stderr.flush()
+    os._exit(rc if rc >= 0 else 128 - rc)
 
 
 def watched(what, seconds, fn):
@@ -539,7 +589,7 @@ def single_process_job(args):
     # the N = 1 form of the same per-GPU work on EVERY device of the job at once (boxes -- and the GPUs of one box -- differ
     # by a few per cent: efficiency_vs_n1 is against their mean, not against device 0's luck)
     n1 = None
-    if not args.no_n1:
+    if args.full and not args.no_n1:
         if len(set(devs)) == n:
             legs = each(lambda r: n1_leg(makisu_amd, W, config, args, devs[r], inflight))
             vals = [leg["value"] for leg in legs]
@@ -634,24 +684,27 @@ def single_process_job(args):
 
     job_bytes = sum(shards[r][0].n_bytes for r in range(n))
     value = job_bytes * args.steps / dt / 2**30
-    # the dominant kernel one batch at a time on rank 0, the other ranks idle: its own duration
-    serial_sha, st = [], None
-    for i in range(2 + min(7, max(3, args.steps))):
-        batches[0][0].submit()
-        batches[0][0].wait()
-        st = engines[0].stats()
-        if i >= 2:
-            serial_sha.append(st["ms_sha_chunks"])
-    alg = st["bytes_in"] + 52 * st["n_chunks"]
-    s_ms = float(np.mean(serial_sha))
-    valu_roof = max(engines[0].sha_valu_roof(w, 0) / 1e9 for w in (8, 4))
-    # closed form of the job-wide unique count
-    g_last = (args.steps - 1) % inflight
+    g_last = (args.steps - 1) % inflight                       # the batch of the last timed step
     n_total, n_unique, per_rank_chunks = checks[g_last]
-    if config in ("c5", "c5u"):
-        expect = sum(int(batches[r][g_last].files()["n_chunks"][shards[r][g_last].originals].sum()) for r in range(n))
-    else:
-        expect = n_total                                      # c2 / c4: every content is distinct
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [batches[r][g_last] for r in range(n)])
+    if args.full:
+        # the dominant kernel one batch at a time on rank 0, the other ranks idle: its own duration
+        serial_sha, st = [], None
+        for i in range(2 + min(7, max(3, args.steps))):
+            batches[0][0].submit()
+            batches[0][0].wait()
+            st = engines[0].stats()
+            if i >= 2:
+                serial_sha.append(st["ms_sha_chunks"])
+        alg = st["bytes_in"] + 52 * st["n_chunks"]
+        s_ms = float(np.mean(serial_sha))
+        valu_roof = max(engines[0].sha_valu_roof(w, 0) / 1e9 for w in (8, 4))
+        # closed form of the job-wide unique count
+        if config in ("c5", "c5u"):
+            expect = sum(int(batches[r][g_last].files()["n_chunks"][shards[r][g_last].originals].sum()) for r in range(n))
+        else:
+            expect = n_total                                      # c2 / c4: every content is distinct
     desc = shards[0][0]
     mean = lambda rows: [round(float(np.mean(x)), 4) for x in rows]     # noqa: E731
     out = {
@@ -678,21 +731,24 @@ def single_process_job(args):
                              "batch's pipeline, sharing the GPU with the other batch in flight; gather = the slab "
                              "all-gather on the ctx stream; marking = padding squeeze + job-wide marking of the rank's rows)"},
         "exchange_host_ms_avg": round(float(np.mean(rec["exchange_host_ms"])), 4),
-        "n1_same_run": n1,
-        "efficiency_vs_n1": round(value / (n * n1["value"]), 4) if n1 else None,
-        "dedup_check": dict(closed_form_check(n_unique, expect), n_total=int(n_total)),
-        "roofline": {"bound": "hbm", "kernel": "sha256_items_kernel (chunk pass)",
-                     "achieved": round(alg / (s_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(alg / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
-                     "algorithmic_bytes_per_launch": int(alg), "avg_launch_ms": round(s_ms, 4),
-                     "valu_roof_GBps": round(valu_roof, 1),
-                     "frac_of_valu_roof": round(alg / (s_ms * 1e-3) / 1e9 / valu_roof, 4),
-                     "path_frac": round(job_bytes / n * 1.006 / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "note": "rank 0's chunk pass one batch at a time right after the timed region (HIP events on the "
-                             "batch's stream, the other ranks idle); in the timed region the launches of the batches in "
-                             "flight share the SIMDs (per_rank.sha_chunks_ms); path_frac = a rank's whole step, "
-                             "algorithmic bytes / ms_per_step / peak"},
     }
+    if args.full:
+        out.update({
+            "n1_same_run": n1,
+            "efficiency_vs_n1": round(value / (n * n1["value"]), 4) if n1 else None,
+            "dedup_check": dict(closed_form_check(n_unique, expect), n_total=int(n_total)),
+            "roofline": {"bound": "hbm", "kernel": "sha256_items_kernel (chunk pass)",
+                         "achieved": round(alg / (s_ms * 1e-3) / 1e9, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                         "frac": round(alg / (s_ms * 1e-3) / 1e9 / HBM_PEAK_GBPS, 4), "traffic": None,
+                         "algorithmic_bytes_per_launch": int(alg), "avg_launch_ms": round(s_ms, 4),
+                         "valu_roof_GBps": round(valu_roof, 1),
+                         "frac_of_valu_roof": round(alg / (s_ms * 1e-3) / 1e9 / valu_roof, 4),
+                         "path_frac": round(job_bytes / n * 1.006 / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
+                         "note": "rank 0's chunk pass one batch at a time right after the timed region (HIP events on the "
+                                 "batch's stream, the other ranks idle); in the timed region the launches of the batches in "
+                                 "flight share the SIMDs (per_rank.sha_chunks_ms); path_frac = a rank's whole step, "
+                                 "algorithmic bytes / ms_per_step / peak"},
+        })
     if config in ("c5", "c5u"):
         out["config"].update({"lpt_imbalance_max_over_mean_bytes": round(desc.imbalance, 6),
                               "files_split_into_parts_job": getattr(desc, "n_split_files_job", 0),
@@ -704,7 +760,7 @@ def single_process_job(args):
         e.comm_destroy()
         e.close()
     pool.shutdown()
-    if not args.no_cpu_baseline:                               # north_star: the host's scanner "in the same run", at N > 1 too
+    if args.full and not args.no_cpu_baseline:                 # north_star: the host's scanner "in the same run", at N > 1 too
         try:
             out["cpu_baseline"] = cpu_baseline(shards[0][0])
         except Exception as e:                                  # noqa: BLE001
@@ -757,6 +813,13 @@ def main():
                          "bytes per row over xGMI at 8 ranks instead of 224)")
     ap.add_argument("--force-exchange", action="store_true",
                     help="run the digest exchange + global marking even with one rank (self-test)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: roofline (serial steps + same-run VALU roof), clocks, the other "
+                         "load scheme, dedup_check, n1_same_run at N > 1, and at N = 1 with_rows_on_host, commit_e2e, "
+                         "cpu_baseline, c3's host-fed leg.  Without it a run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the rows the last timed step computed (file and chunk tables, a seeded "
+                         "sample of larger ones) as float64 / float32 .npy files under DIR")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -807,7 +870,7 @@ def main():
 
     # the N = 1 form of the same per-GPU work, every rank on its own GPU at the same time, before the job
     n1 = None
-    if world > 1 and not args.no_n1 and config != "c3":
+    if world > 1 and args.full and not args.no_n1 and config != "c3":
         n1_mine = n1_leg(makisu_amd, W, config, args, dev_index, args.inflight)
         vals = all_ranks(n1_mine["value"])
         n1 = dict(n1_mine, value=round(float(np.mean(vals)), 2), per_rank_value=vals,
@@ -884,7 +947,7 @@ def main():
     # wiping their 130 GB of VRAM on the SDMA engines the H2D copies need (measured: 18 GB/s then,
     # 46 GB/s on a quiet device)
     host_fed = None
-    if config == "c3" and rank == 0 and world == 1 and not args.no_host_fed:
+    if config == "c3" and rank == 0 and world == 1 and args.full and not args.no_host_fed:
         host_fed = host_fed_rate(eng)
 
     split = config == "c3"
@@ -959,24 +1022,30 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    try:
-        bus = torch.cuda.get_device_properties(dev_index).pci_bus_id
-        dom = getattr(torch.cuda.get_device_properties(dev_index), "pci_domain_id", 0)
-        pci = "%04x:%02x:%02x.0" % (dom, bus, torch.cuda.get_device_properties(dev_index).pci_device_id)
-    except Exception:                                           # noqa: BLE001
-        pci = None
-    sampler = ClockSampler(pci)
-    if sampler.freq is None and pci is not None:
-        sampler = ClockSampler(None)                            # containers often show one card only
+    sampler = None
+    if args.full:                                               # sclk / power beside the timed region
+        try:
+            bus = torch.cuda.get_device_properties(dev_index).pci_bus_id
+            dom = getattr(torch.cuda.get_device_properties(dev_index), "pci_domain_id", 0)
+            pci = "%04x:%02x:%02x.0" % (dom, bus, torch.cuda.get_device_properties(dev_index).pci_device_id)
+        except Exception:                                       # noqa: BLE001
+            pci = None
+        sampler = ClockSampler(pci)
+        if sampler.freq is None and pci is not None:
+            sampler = ClockSampler(None)                        # containers often show one card only
     run_steps(args.warmup, False)
     fence()
-    sampler.start()
+    if sampler:
+        sampler.start()
     t0 = time.perf_counter()
     run_steps(args.steps, True)
     fence()
     dt = time.perf_counter() - t0
-    clocks = sampler.stop() if rank == 0 else None
+    clocks = sampler.stop() if sampler and rank == 0 else None
     chunks_last_batch = int(eng.stats()["n_chunks"])            # of the timed region's last step
+    if args.dump_outputs and rank == 0:                         # the rows of the last timed step: its batch (c3: all its parts)
+        last = args.steps * launches_per_step - 1
+        dump_outputs(args.dump_outputs, [batches[k % len(batches)] for k in range(last - launches_per_step + 1, last + 1)])
     if dist.is_initialized() and world > 1:
         t = torch.tensor([dt], dtype=torch.float64, device=red_dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -994,7 +1063,7 @@ def main():
     # from these launches when the timed region keeps several batches in flight.  2 untimed steps (the clock
     # ramps up again after the host-side pause), then --steps timed ones.
     serial_sha_ms, serial_alg, serial_phase, one_at_a_time = [], [], {}, None
-    if args.inflight > 1:
+    if args.full and args.inflight > 1:
         torch.cuda.synchronize(device)
         n_serial = args.steps * launches_per_step
         acc = {}
@@ -1022,16 +1091,18 @@ def main():
                                      "form of the headline (BENCH_r03: 1053.77 GiB/s, 5.7921 ms)"}
     # the SHA-256 VALU roof of THIS device in THIS run, right behind the serial steps (same thermal and
     # power state): best of three 10 ms launches of the compression alone
-    sampler.start()
-    roofs = {w: eng.sha_valu_roof(w, 0) / 1e9 for w in (8, 4)}   # waves per SIMD: the denser form draws more power
-    valu_roof = max(roofs.values())
-    roof_clocks = sampler.stop() if rank == 0 else None
+    roofs, valu_roof, roof_clocks = {}, None, None
+    if args.full:
+        sampler.start()
+        roofs = {w: eng.sha_valu_roof(w, 0) / 1e9 for w in (8, 4)}   # waves per SIMD: the denser form draws more power
+        valu_roof = max(roofs.values())
+        roof_clocks = sampler.stop() if rank == 0 else None
 
     # The same pass with the OTHER load scheme (quad-cooperative: far fewer address translations), a few
     # serial steps on a second ctx: on a box whose lane-owned launches run well below the VALU roof this
     # tells a translation-bound kernel (cooperative faster) from a clock-bound one (both slow alike).
     other_scheme = None
-    if config == "c2" and world == 1 and rank == 0:
+    if args.full and config == "c2" and world == 1 and rank == 0:
         auto_coop = shards[0].n_bytes >= (9 << 30)
         e2 = makisu_amd.Engine(device=dev_index, sha_load_scheme=makisu_amd.SHA_LOADS_LANE if auto_coop
                                else makisu_amd.SHA_LOADS_COOP)
@@ -1050,7 +1121,7 @@ def main():
     # closed-form check of the duplicate marking (c5: 90 % duplicate files): the job-wide unique
     # count must equal the chunk count of the first file of every distinct content
     dedup_check = None
-    if not split and (exchange or world == 1):
+    if args.full and not split and (exchange or world == 1):
         if config in ("c5", "c5u"):
             files0 = batches[0].files()
             expect = int(files0["n_chunks"][shards[0].originals].sum())
@@ -1080,8 +1151,9 @@ def main():
             traffic_src = tj.get("source")
         except Exception:
             traffic = None
-    mode = ("%d batches in flight (value, ms_per_step); roofline from the one-batch-at-a-time steps of the same run"
-            % args.inflight) if args.inflight > 1 else "one batch at a time (value, ms_per_step and roofline alike)"
+    mode = ("%d batches in flight (value, ms_per_step)%s" % (args.inflight, "; roofline from the one-batch-at-a-time steps of the same run"
+                                                                if args.full else "")) if args.inflight > 1 else \
+        "one batch at a time (value, ms_per_step%s)" % (" and roofline alike" if args.full else "")
     out = {
         "metric": "GiB/s hashed (Gear CDC + SHA-256 per chunk)",
         "value": round(value, 2), "unit": "GiB/s", "n_gpus": world, "steps": args.steps,
@@ -1109,38 +1181,39 @@ def main():
                    "results": "left on the device (16 B of counts read back per batch); mi_batch_chunks_view / "
                               "mi_batch_files bring 64 B per chunk + 96 B per file to the host on demand "
                               "(one packed copy, ~1.6 ms per C2 batch), outside this metric"},
-        "roofline": {"bound": "hbm", "kernel": "sha256_items_kernel (chunk pass)",
-                     "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
-                     "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
-                     "traffic_from_profile_run": traffic_src,
-                     "algorithmic_bytes_per_launch": int(alg_bytes),
-                     "avg_launch_ms": round(sha_avg_ms, 4),
-                     "avg_launch_ms_from": ("the %d one-batch-at-a-time steps right after the timed region" % len(serial_sha_ms))
-                                           if serial_sha_ms else "the timed region",
-                     "valu_roof_GBps": round(valu_roof, 1),
-                     "valu_roof_source": "mi_sha_valu_roof in this run, right after the timed region: the 64-round "
-                                         "compression alone on every SIMD (no memory traffic), best of 3 launches at 8 and "
-                                         "at 4 waves per SIMD: %s GB/s.  The roof launch is pure VALU work and is itself "
-                                         "subject to the socket's power management: on a box where it is throttled the "
-                                         "hashing pass can sit at (or a few %% above) it -- both are then at the same limit"
-                                         % {k: round(v, 1) for k, v in roofs.items()},
-                     "frac_of_valu_roof": round(achieved / valu_roof, 4),
-                     "path_frac": round(job_bytes / world * 1.006 / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
-                     "note": "SHA-256 is integer-VALU bound on CDNA4 (valu_roof_GBps, measured in this run); "
-                             "the HBM fraction cannot exceed valu_roof / peak. "
-                             "achieved/avg_launch_ms: HIP events around the launch on the batch's stream, %s; "
-                             "path_frac = whole CDC+SHA step per GPU, algorithmic bytes / ms_per_step / peak"
-                             % ("one batch at a time in the timed region, the kernel has the GPU to itself" if args.inflight == 1 else
-                                "from the one-batch-at-a-time steps of this run; in the timed region the kernel shares the "
-                                "SIMDs with the other in-flight batches' passes and the span between its events is "
-                                "inflight_span_ms")},
         "phase_ms_avg": {k: round(v / max(1, len(sha_ms)), 4) for k, v in sorted(stats_sum.items())},
         "phase_note": "per-batch stream timelines of the timed region; with several batches in flight a phase's span "
                       "includes time it shared the GPU with the other batches; serial_phase_ms = one batch at a time",
     }
+    if args.full:
+        out["roofline"] = {"bound": "hbm", "kernel": "sha256_items_kernel (chunk pass)",
+                           "achieved": round(achieved, 1), "peak": HBM_PEAK_GBPS, "unit": "GB/s",
+                           "frac": round(achieved / HBM_PEAK_GBPS, 4), "traffic": traffic,
+                           "traffic_from_profile_run": traffic_src,
+                           "algorithmic_bytes_per_launch": int(alg_bytes),
+                           "avg_launch_ms": round(sha_avg_ms, 4),
+                           "avg_launch_ms_from": ("the %d one-batch-at-a-time steps right after the timed region" % len(serial_sha_ms))
+                                                 if serial_sha_ms else "the timed region",
+                           "valu_roof_GBps": round(valu_roof, 1),
+                           "valu_roof_source": "mi_sha_valu_roof in this run, right after the timed region: the 64-round "
+                                               "compression alone on every SIMD (no memory traffic), best of 3 launches at 8 and "
+                                               "at 4 waves per SIMD: %s GB/s.  The roof launch is pure VALU work and is itself "
+                                               "subject to the socket's power management: on a box where it is throttled the "
+                                               "hashing pass can sit at (or a few %% above) it -- both are then at the same limit"
+                                               % {k: round(v, 1) for k, v in roofs.items()},
+                           "frac_of_valu_roof": round(achieved / valu_roof, 4),
+                           "path_frac": round(job_bytes / world * 1.006 / (dt / args.steps) / 1e9 / HBM_PEAK_GBPS, 4),
+                           "note": "SHA-256 is integer-VALU bound on CDNA4 (valu_roof_GBps, measured in this run); "
+                                   "the HBM fraction cannot exceed valu_roof / peak. "
+                                   "achieved/avg_launch_ms: HIP events around the launch on the batch's stream, %s; "
+                                   "path_frac = whole CDC+SHA step per GPU, algorithmic bytes / ms_per_step / peak"
+                                   % ("one batch at a time in the timed region, the kernel has the GPU to itself" if args.inflight == 1 else
+                                      "from the one-batch-at-a-time steps of this run; in the timed region the kernel shares the "
+                                      "SIMDs with the other in-flight batches' passes and the span between its events is "
+                                      "inflight_span_ms")}
     if args.inflight == 1:
         out["serial_phase_ms"] = dict(out["phase_ms_avg"])      # one batch at a time: the timed region IS serial
-    else:
+    elif args.full:
         out["serial_phase_ms"] = serial_phase
         out["roofline"]["inflight_span_ms"] = round(span_ms, 4)
     if one_at_a_time:
@@ -1165,7 +1238,7 @@ def main():
                                    "the GPU with the other batch in flight); exchange_host = wall time of the exchange call; "
                                    "gather / marking = device time of the slab all-gather and of the job-wide marking "
                                    "(HIP events on the ctx stream, native exchange only)")
-    if world > 1:
+    if world > 1 and args.full:
         out["n1_same_run"] = n1
         out["efficiency_vs_n1"] = round(value / (world * n1["value"]), 4) if n1 else None
     if clocks is not None:
@@ -1177,7 +1250,7 @@ def main():
     for b in batches:
         b.free()
     batches = []
-    if rank == 0 and world == 1:
+    if rank == 0 and world == 1 and args.full:
         if host_fed:
             out["config"].update(host_fed)
         # the legs behind the headline: one that fails (a full /dev/shm, a host without room for the sample) says so in its

@@ -265,15 +265,16 @@ def scenario_known_tree(tmp, eng):
     root = os.path.join(tmp, "known_root")
     rng = np.random.default_rng(5)
     entries, files = [], {}
+    owner = {"uid": os.geteuid(), "gid": os.getegid()}                   # who the files below belong to: the merged headers are theirs
     n_dirs, per_dir = 24, 60                                              # 94 MB: twelve pieces of 8 MiB (the tests' MI_ARENA_PIECE_MB), three of 32
     for d in range(n_dirs):
-        entries.append({"relpath": "k%02d" % d, "kind": M.KIND_DIR, "mode": 0o40755, "mtime_sec": MTIME, "size": 0})
+        entries.append({"relpath": "k%02d" % d, "kind": M.KIND_DIR, "mode": 0o40755, "mtime_sec": MTIME, "size": 0, **owner})
         for k in range(per_dir):
             rel = "k%02d/f%02d" % (d, k)
             data = rng.integers(0, 256, 65_536, dtype=np.uint8).tobytes()
             write_file(os.path.join(root, rel), data, 0o644, MTIME)
             files[rel] = data
-            entries.append({"relpath": rel, "kind": M.KIND_FILE, "mode": 0o100644, "mtime_sec": MTIME, "size": len(data)})
+            entries.append({"relpath": rel, "kind": M.KIND_FILE, "mode": 0o100644, "mtime_sec": MTIME, "size": len(data), **owner})
     for d in range(n_dirs):
         os.utime(os.path.join(root, "k%02d" % d), (MTIME, MTIME))
     total = sum(map(len, files.values()))

@@ -809,7 +809,7 @@ def test_the_bench_line_carries_the_products_numbers():
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--files", "20000", "--steps", "4", "--warmup", "1",
-                          "--no-commit-e2e"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
+                          "--full", "--no-commit-e2e"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
     j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     w = j["with_rows_on_host"]

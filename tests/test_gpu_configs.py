@@ -70,6 +70,40 @@ def test_c2_full_size_every_row(oracle, eng):
     assert len(chunks) > 700000 and nu == len(chunks) - len(dup) and (dup["length"] <= 2).all() and len(dup) <= 3
 
 
+@pytest.mark.timeout(600)
+def test_bench_plain_line_and_its_dumped_outputs(oracle, eng, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: the headline line alone (no leg of its own behind
+    it), and DIR holds the rows of the last timed step as float .npy files -- the oracle's rows of that step's shard"""
+    import json
+    from makisu_amd import workloads as W
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        env.pop(k, None)
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--files", "2000", "--steps", "3",
+                          "--warmup", "1", "--dump-outputs", str(tmp_path / "dump")], env=env, cwd=ROOT, capture_output=True,
+                         text=True, timeout=500)
+    assert out.returncode == 0, out.stdout[-1500:] + out.stderr[-3000:]
+    j = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
+    assert j["metric"] == "GiB/s hashed (Gear CDC + SHA-256 per chunk)" and j["unit"] == "GiB/s" and j["higher_is_better"] is True
+    assert j["value"] > 0 and j["ms_per_step"] > 0 and j["steps"] == 3 and j["warmup"] == 1 and j["dtype"] == "u32"
+    assert not {"roofline", "cpu_baseline", "with_rows_on_host", "commit_e2e", "one_batch_at_a_time", "clocks"} & set(j)
+    d = {f[:-4]: np.load(str(tmp_path / "dump" / f)) for f in os.listdir(str(tmp_path / "dump"))}
+    assert all(a.dtype in (np.float32, np.float64) for a in d.values())
+    assert sum(a.nbytes for a in d.values()) <= 64 << 20
+    n_files, n_chunks = (int(x) for x in d["counts"])
+    assert n_files == 2000 and n_chunks == j["config"]["chunks_last_batch"] == len(d["chunk_rows"])     # (small: every row)
+    # the last of 3 timed steps ran the first of the 2 batches in flight: generation 0 of the shard
+    shard = W.c2(0, 1, 2000, 0)
+    p = oracle.CdcParams(eng.cfg.gear_seed, eng.cfg.mask_bits, eng.cfg.min_size, eng.cfg.max_size)
+    rf, rc, _ = oracle.scan_synthetic(shard.seed, shard.cids, shard.sizes, p, True, _threads(), 0)
+    assert len(rc) == n_chunks
+    assert np.array_equal(d["file_n_chunks"], rf["n_chunks"].astype(np.float64))
+    assert np.array_equal(d["file_chunk_root"], rf["chunk_root"].astype(np.float32))
+    for k in ("file_index", "offset", "length", "dup_of"):
+        assert np.array_equal(d["chunk_" + k], rc[k].astype(np.float64)), k
+    assert np.array_equal(d["chunk_sha256"], rc["sha256"].astype(np.float32))
+
+
 @pytest.mark.timeout(900)
 def test_c3_full_size_every_row(oracle, eng):
     """BASELINE.json configs[2] as written and as `bench.py --config c3` times it: 1 000 x 128 MiB as ONE
@@ -186,7 +220,7 @@ def test_bench_c4_two_ranks_on_one_gpu_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29577", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--config", "c4", "--files", "20000", "--steps", "2", "--warmup", "1",
-           "--exchange", "torch", "--backend", "gloo", "--no-cpu-baseline"]
+           "--exchange", "torch", "--backend", "gloo", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-3000:]
     import json
@@ -207,7 +241,7 @@ def test_bench_c5_two_ranks_split_files_on_one_gpu_gloo():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29579", os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--config", "c5", "--bytes-per-gpu", "3", "--split-mib", "32", "--steps", "2",
-           "--warmup", "1", "--exchange", "torch", "--backend", "gloo", "--no-cpu-baseline"]
+           "--warmup", "1", "--exchange", "torch", "--backend", "gloo", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     assert out.returncode == 0, out.stderr[-3000:]
     import json

@@ -267,7 +267,7 @@ def test_bench_bare_gpus_8_is_the_library_exchange(stub):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "8", "--files", "20000",
-                          "--steps", "2", "--warmup", "1"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
+                          "--steps", "2", "--warmup", "1", "--full"], env=env, cwd=ROOT, capture_output=True, text=True, timeout=800)
     j = _bench_line(out)
     assert j["n_gpus"] == 8 and j["config"]["name"] == "c4" and j["config"]["rccl_ranks"] == 8
     assert j["config"]["exchange"] == "native" and "single process" in j["config"]["launch"]
@@ -290,7 +290,7 @@ def test_bench_with_the_all_to_all_form(stub, launch):
     (one process per rank: mi_dedup_alltoall): the job-wide unique count is the generator's closed form, the line says which
     form ran, and the per-rank wire / device-work times are there."""
     env = dict(os.environ, MI_BENCH_FORCE_DEVICE="0", MI_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1")
-    tail = ["--gpus", "4", "--files", "8000", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--exchange-form", "alltoall"]
+    tail = ["--gpus", "4", "--files", "8000", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--exchange-form", "alltoall"]
     if launch == "bare":
         for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
             env.pop(k, None)
@@ -318,7 +318,7 @@ def test_bench_bare_first_contact_always_ends_in_a_line(stub, fault, says):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--files", "8000", "--steps", "2",
-                          "--warmup", "1", "--watchdog-s", "8", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True,
+                          "--warmup", "1", "--watchdog-s", "8", "--full", "--no-cpu-baseline"], env=env, cwd=ROOT, capture_output=True,
                          text=True, timeout=800)
     j = _bench_line(out)
     assert j["n_gpus"] == 4 and j["config"]["rccl_ranks"] == 4 and j["config"]["launch"] == "one process per GPU"
@@ -348,7 +348,7 @@ def test_bench_torchrun_defaults_to_the_native_exchange(stub):
     env = dict(os.environ, MI_BENCH_FORCE_DEVICE="0", MI_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4",
            "--master-addr", "127.0.0.1", "--master-port", "29583", os.path.join(ROOT, "bench.py"),
-           "--gpus", "4", "--files", "20000", "--steps", "2", "--warmup", "1"]
+           "--gpus", "4", "--files", "20000", "--steps", "2", "--warmup", "1", "--full"]
     j = _bench_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800))
     assert j["n_gpus"] == 4 and j["config"]["name"] == "c4" and j["config"]["rccl_ranks"] == 4
     assert j["config"]["exchange"] == "native" and "gloo" in j["config"]["exchange_backend"]
@@ -386,7 +386,7 @@ def test_bench_torchrun_c5_split_files_through_the_native_exchange(stub):
     env = dict(os.environ, MI_BENCH_FORCE_DEVICE="0", MI_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29585", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--config", "c5", "--bytes-per-gpu", "3", "--split-mib", "32", "--steps", "2", "--warmup", "1"]
+           "--gpus", "2", "--config", "c5", "--bytes-per-gpu", "3", "--split-mib", "32", "--steps", "2", "--warmup", "1", "--full"]
     j = _bench_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800))
     assert j["n_gpus"] == 2 and j["config"]["name"] == "c5" and j["config"]["exchange"] == "native" and j["config"]["rccl_ranks"] == 2
     assert j["config"]["parts_this_rank"] > 0 and j["config"]["files_split_into_parts_job"] > 0
@@ -402,7 +402,7 @@ def test_bench_falls_back_to_the_torch_driver_when_a_rank_loses_its_communicator
     env = dict(os.environ, MI_BENCH_FORCE_DEVICE="0", MI_RCCL_LIB=stub, MASTER_ADDR="127.0.0.1", MI_BENCH_FAIL_NATIVE_ON_RANK="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", "29587", os.path.join(ROOT, "bench.py"),
-           "--gpus", "2", "--files", "20000", "--steps", "2", "--warmup", "1", "--backend", "gloo"]
+           "--gpus", "2", "--files", "20000", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full"]
     j = _bench_line(subprocess.run(cmd, env=env, cwd=ROOT, capture_output=True, text=True, timeout=800))
     assert j["config"]["exchange"] == "torch" and "simulated failure" in j["config"]["exchange_note"]
     assert j["config"]["rccl_ranks"] is None                      # gloo counted the ranks, not RCCL: the line cannot claim it

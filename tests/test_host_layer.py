@@ -557,7 +557,7 @@ def test_mem_layer_test_go_cases_replayed(tmp_path):
     assert h[:13] == b"tmp/testDest/" and h[13] == 0 and h[156:157] == b"5"
     h = M.layer_header_bytes({"relpath": "/tmp/testDest", "kind": M.KIND_FILE, "mode": 0o100600, "size": 0})
     assert h[:12] == b"tmp/testDest" and h[12] == 0 and h[156:157] == b"0"
-    h = M.layer_header_bytes({"relpath": "/tmp/testDest", "kind": M.KIND_SYMLINK, "mode": 0o120777, "link_target": str(src)})
+    h = M.layer_header_bytes({"relpath": "/tmp/testDest", "kind": M.KIND_SYMLINK, "mode": 0o120777, "link_target": "/tmp/test"})
     assert h[:12] == b"tmp/testDest" and h[12] == 0 and h[156:157] == b"2"
     # TestAddHeader/Whiteout: dst "/tmp/.wh.testDest" -> whiteout of "/tmp/testDest", hdr.Name "tmp/.wh.testDest"
     zero = M.layer_header_bytes({"relpath": "/tmp/.wh.testDest", "kind": M.KIND_FILE, "mode": 0o100644, "size": 38,

@@ -528,8 +528,9 @@ def test_directories_whose_names_begin_alike_in_a_tars_arbitrary_order(tmp_path)
     """The tree keeps, per depth, the directory of the last lookup and a place among its children -- matched by the directory's
     whole path, not a prefix of it.  A tar may list "a", "ab", "abc" and "a/b", "a/bb" in any order, jumping between them; every
     entry must land below ITS directory, a later layer's changes on the right nodes, and the scan of the same tree finds nothing."""
-    D = lambda p: {"relpath": p, "kind": M.KIND_DIR, "mode": 0o40755, "mtime_sec": 100, "size": 0}                 # noqa: E731
-    F = lambda p, t=100: {"relpath": p, "kind": M.KIND_FILE, "mode": 0o100644, "mtime_sec": t, "size": 5}         # noqa: E731
+    own = {"uid": os.geteuid(), "gid": os.getegid()}                          # the owner of the tree written below
+    D = lambda p: {"relpath": p, "kind": M.KIND_DIR, "mode": 0o40755, "mtime_sec": 100, "size": 0, **own}          # noqa: E731
+    F = lambda p, t=100: {"relpath": p, "kind": M.KIND_FILE, "mode": 0o100644, "mtime_sec": t, "size": 5, **own}  # noqa: E731
     first = [D("a"), D("ab"), D("abc"), F("a/x"), F("ab/x"), F("abc/x"), F("a/y"), F("abc/y"), F("ab/y"), D("a/b"), D("a/bb"),
              F("a/bb/q"), F("a/b/q"), F("a/bb/r"), F("a/b/r"), F("abc/a"), F("a/a"), F("ab/a")]
     with M.MemFS(str(tmp_path)) as fs:

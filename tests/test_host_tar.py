@@ -1,7 +1,7 @@
 """CPU tests of the layer-tar reader (csrc/mi_tar.hip, no GPU): entries and file byte ranges of
 ustar / pax / GNU archives against Python's tarfile (an independent implementation of the same
-formats), plus the reference's own docker-made layer fixture when /root/reference is present
-(testdata/files/busybox/.../layer.tar)."""
+formats), plus the reference's own docker-made layer fixture (testdata/files/busybox/.../layer.tar, SURVEY.md 8c: the gunzip
+of the stored layer blob that tests/golden/sha256_reference_fixtures.json carries)."""
 import hashlib
 import io
 import os
@@ -11,7 +11,25 @@ import tarfile
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FIXTURE = "/root/reference/testdata/files/busybox/393ccd5c4dd90344c9d725125e13f636ce0087c62f5ca89050faaacbb9e3ed5b/layer.tar"
+GOLDEN = os.path.join(ROOT, "tests", "golden")
+
+
+def _reference_fixtures(tmp_path):
+    """(the reference's stored layer blob testdata/files/alpine/test_layer.tar, its gunzip testdata/files/busybox/393ccd5c.../
+    layer.tar) as files under tmp_path, from the blob in tests/golden/sha256_reference_fixtures.json"""
+    import base64
+    import json
+    import zlib
+    vec = json.load(open(os.path.join(GOLDEN, "sha256_reference_fixtures.json")))["vectors"][0]
+    assert vec["name"] == "alpine_layer_blob"
+    blob = base64.b64decode(vec["file_b64"])
+    assert hashlib.sha256(blob).hexdigest() == GZ_BLOB_SHA
+    d = tmp_path / "reference_fixtures"
+    d.mkdir(exist_ok=True)
+    gz_path, tar_path = str(d / "test_layer.tar"), str(d / "layer.tar")
+    open(gz_path, "wb").write(blob)
+    open(tar_path, "wb").write(zlib.decompress(blob, 31))
+    return gz_path, tar_path
 
 
 def _rel(name):
@@ -81,14 +99,14 @@ def _build(path, fmt):
         add("bin/busybox", data=os.urandom(70001), mode=0o755)
         add("bin/sh", tarfile.LNKTYPE, linkname="bin/busybox", mode=0o755)          # hard link
         add("bin/link", tarfile.SYMTYPE, linkname="/bin/busybox", mode=0o777)
-        add("etc/", tarfile.DIRTYPE)
+        add("etc/", tarfile.DIRTYPE, mode=0o755)                                     # (directories their owner can enter)
         add("etc/empty")
         add("etc/one", data=b"x")
         add("etc/block512", data=bytes(512))                                          # exactly one block
         add("etc/.wh.removed")                                                        # a whiteout marker
         add("dev/null", tarfile.CHRTYPE, dev=(1, 3), mode=0o666)
         add("dev/fifo", tarfile.FIFOTYPE)
-        add(long_dir + "/", tarfile.DIRTYPE)
+        add(long_dir + "/", tarfile.DIRTYPE, mode=0o755)
         add(long_dir + "/payload", data=b"long path payload", uid=1000, gid=2000)
         add("owner", data=b"o", uid=123456, gid=654321, mtime=1)
         if fmt != tarfile.USTAR_FORMAT:
@@ -141,10 +159,11 @@ def test_tar_pax_mtime_fraction_and_errors(tmp_path):
     assert ei.value.code == -5
 
 
-@pytest.mark.skipif(not os.path.exists(FIXTURE), reason="reference fixture not present (GPU box)")
-def test_reference_layer_fixture():
+def test_reference_layer_fixture(tmp_path):
     """The reference's docker-made busybox layer (390 entries, one binary and its hard links)."""
-    got = _compare_with_tarfile(FIXTURE)
+    _, fixture = _reference_fixtures(tmp_path)
+    assert hashlib.sha256(open(fixture, "rb").read()).hexdigest() == GZ_TAR_SHA
+    got = _compare_with_tarfile(fixture)
     assert len(got) == 390
     kinds = [g["kind"] for g in got]
     assert kinds.count(3) > 300 and kinds.count(1) >= 1
@@ -290,25 +309,24 @@ def test_apply_layer_matches_sequential_extraction(tmp_path):
 # ---- round 2: stored (gzip) layers, UpdateFromTarReader's filter, hard-link pass, isOnDisk ----
 import makisu_amd as M  # noqa: E402
 
-GZ_FIXTURE = "/root/reference/testdata/files/alpine/test_layer.tar"     # a gzip blob despite its name
 GZ_BLOB_SHA = "393ccd5c4dd90344c9d725125e13f636ce0087c62f5ca89050faaacbb9e3ed5b"   # testutil.SampleLayerTarDigest
 GZ_TAR_SHA = "4ac76077f2c741c856a2419dfdb0804b18e48d2e1a9ce9c6a3f0605a2078caba"    # its gunzip
 
 
-@pytest.mark.skipif(not os.path.exists(GZ_FIXTURE), reason="reference fixture not present (GPU box)")
 def test_reference_gzip_layer_blob(tmp_path):
     """The reference's stored layer blob (lib/utils/testutil/constants.go:28): listed through the
     streaming inflate, inflated with both digests, and equal to the plain-tar fixture's listing."""
-    gz = M.tar_entries(GZ_FIXTURE)
-    plain = M.tar_entries(FIXTURE)
+    gz_fixture, fixture = _reference_fixtures(tmp_path)           # (the blob is a gzip despite its name: test_layer.tar)
+    gz = M.tar_entries(gz_fixture)
+    plain = M.tar_entries(fixture)
     assert len(gz) == len(plain) == 390
     assert gz == plain                                      # same entries, same uncompressed offsets
     out = str(tmp_path / "layer.tar")
-    r = M.tar_inflate(GZ_FIXTURE, out)
+    r = M.tar_inflate(gz_fixture, out)
     assert r["blob_digest"].hex() == GZ_BLOB_SHA and r["tar_digest"].hex() == GZ_TAR_SHA
-    assert r["tar_bytes"] == os.path.getsize(out) == os.path.getsize(FIXTURE)
-    assert open(out, "rb").read() == open(FIXTURE, "rb").read()
-    assert M.tar_inflate(GZ_FIXTURE)["tar_digest"].hex() == GZ_TAR_SHA      # digests only
+    assert r["tar_bytes"] == os.path.getsize(out) == os.path.getsize(fixture)
+    assert open(out, "rb").read() == open(fixture, "rb").read()
+    assert M.tar_inflate(gz_fixture)["tar_digest"].hex() == GZ_TAR_SHA      # digests only
 
 
 def test_gzip_layer_roundtrip_and_errors(tmp_path):

@@ -40,8 +40,13 @@ def tree(tmp_path):
     # every kind utils.IsSpecialFile names (lib/utils/utils.go:161-163); device nodes where this process may make them
     import socket
     sk = socket.socket(socket.AF_UNIX)
-    sk.bind(str(b / "a" / "sock"))
-    sk.close()
+    cwd = os.getcwd()
+    os.chdir(b / "a")                                   # bound by its name: a socket's path is limited to 107 bytes
+    try:
+        sk.bind("sock")
+    finally:
+        os.chdir(cwd)
+        sk.close()
     try:
         os.mknod(b / "a" / "chr", 0o600 | stat.S_IFCHR, os.makedev(1, 3))
         os.mknod(b / "z" / "blk", 0o600 | stat.S_IFBLK, os.makedev(7, 0))
