@@ -19,6 +19,13 @@
 //           collision, the row goes on probing from the next slot in another round.
 // No thread ever reads digest bytes another thread of the same launch may still be writing, and
 // never trusts a slot's bytes without its tag, so recycled device memory cannot fake a match.
+// Rounds: of k new digests that share their first 8 bytes one claims a slot per round, the others
+// fail verify and move on, so the group takes k rounds.  Every round each probing row either
+// finishes or moves forward at least one slot, and the table stays under half full, so no row can
+// walk more than `cap` slots: `cap` rounds always suffice, and more is an error.  Every return
+// after the first probe round adds the rows placed so far to `count`, which therefore always
+// equals the occupied slots; export and growth copy out at most `count` digests and fail with
+// MI_ERR_STATE when the table holds a different number.
 // Duplicate rows inherit the flag of the row they point to.  The table is rebuilt at twice
 // the size when it gets more than half full.
 #include "mi_internal.h"
@@ -124,12 +131,15 @@ void index_inherit_kernel(const i64* __restrict__ dup_of, u64 n, u8* __restrict_
     if (d >= 0) known[i] = known[d];                         // d < i and d is a unique row
 }
 
+// appends every occupied slot's digest to out[0, limit); the cursor counts them all, so the host
+// sees a table that holds more than `limit` without a write past the buffer
 __global__ __launch_bounds__(256)
 void index_export_kernel(const u64* __restrict__ state, const u8* __restrict__ slots, u64 cap,
-                         u8* __restrict__ out, u64* __restrict__ cursor) {
+                         u8* __restrict__ out, u64 limit, u64* __restrict__ cursor) {
     const u64 s = (u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= cap || state[s] == 0ull) return;
     const u64 at = atomicAdd((unsigned long long*)cursor, 1ull);
+    if (at >= limit) return;
     ((u32x4*)(out + 32 * at))[0] = ((const u32x4*)(slots + 32 * s))[0];
     ((u32x4*)(out + 32 * at))[1] = ((const u32x4*)(slots + 32 * s))[1];
 }
@@ -170,8 +180,12 @@ int index_grow(mi_index* x, u64 min_cap) {
         HIPCHK(c, old.ensure(have * 32));
         HIPCHK(c, hipMemsetAsync(x->counter.p, 0, 8, c->stream));
         hipLaunchKernelGGL(index_export_kernel, dim3((u32)((x->cap + 255) / 256)), dim3(256), 0, c->stream,
-                           x->state.as<u64>(), x->slots.as<u8>(), x->cap, old.as<u8>(), x->counter.as<u64>());
+                           x->state.as<u64>(), x->slots.as<u8>(), x->cap, old.as<u8>(), have, x->counter.as<u64>());
+        HIPCHK(c, hipMemcpyAsync(c->h_word, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (c->h_word[0] != have)                           // the table is left as it was
+            return fail(c, MI_ERR_STATE, "chunk index holds %llu digests, counted %llu",
+                        (unsigned long long)c->h_word[0], (unsigned long long)have);
     }
     x->state.release();
     x->slots.release();
@@ -204,29 +218,38 @@ int index_insert(mi_index* x, const u8* d_digests, const i64* d_dup_of, u64 n, u
     u64* d_cnt = x->counter.as<u64>();
     hipLaunchKernelGGL(index_begin_kernel, dim3(per_row), dim3(256), 0, c->stream, d_digests, d_dup_of, n,
                        x->cap - 1, x->row_state.as<u8>(), x->row_slot.as<u64>());
-    for (int round = 0;; ++round) {
+    // from here on the table holds every row placed so far: each return adds them (counter[0] as
+    // last read) to x->count
+    u64 added = 0;
+    int rc = MI_OK;
+    hipError_t e = hipSuccess;
+    for (u64 round = 0;; ++round) {
         hipLaunchKernelGGL(index_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_digests, n,
                            x->state.as<u64>(), x->slots.as<u8>(), x->cap - 1, x->row_state.as<u8>(),
                            x->row_slot.as<u64>(), d_known, d_cnt);
         hipLaunchKernelGGL(index_verify_kernel, dim3(per_row), dim3(256), 0, c->stream, d_digests, n,
                            x->slots.as<u8>(), x->cap - 1, x->row_state.as<u8>(), x->row_slot.as<u64>(),
                            d_known, d_cnt + 1);
-        HIPCHK(c, hipMemcpyAsync(c->h_word, x->counter.p, 16, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
+        e = hipMemcpyAsync(c->h_word, x->counter.p, 16, hipMemcpyDeviceToHost, c->stream);
+        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
+        if (e != hipSuccess) break;
+        added = c->h_word[0];
         if (c->h_word[1] == 0) break;                       // no 64-bit tag collisions (the normal case)
-        if (round > 64) return fail(c, MI_ERR_HIP, "chunk index: probing does not converge");
-        HIPCHK(c, hipMemsetAsync(d_cnt + 1, 0, 8, c->stream));
+        if (round >= x->cap) { rc = fail(c, MI_ERR_HIP, "chunk index: probing does not converge"); break; }
+        e = hipMemsetAsync(d_cnt + 1, 0, 8, c->stream);
+        if (e != hipSuccess) break;
     }
-    if (d_dup_of && d_known)
+    if (!rc && e == hipSuccess && d_dup_of && d_known) {
         hipLaunchKernelGGL(index_inherit_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, c->stream,
                            d_dup_of, n, d_known);
-    HIPCHK(c, hipMemcpyAsync(c->h_word, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipGetLastError());
-    const u64 added = c->h_word[0];
+        e = hipStreamSynchronize(c->stream);
+    }
+    if (!rc && e == hipSuccess) e = hipGetLastError();
+    if (!rc && e != hipSuccess)
+        rc = fail(c, e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "chunk index insert: %s", hipGetErrorString(e));
     x->count += added;
     *n_new = added;
-    return MI_OK;
+    return rc;
 }
 
 }  // namespace
@@ -333,10 +356,14 @@ int mi_index_export(mi_index* x, void* out, uint64_t cap_digests) {
     HIPCHK(c, tmp.ensure(x->count * 32));
     HIPCHK(c, hipMemsetAsync(x->counter.p, 0, 8, c->stream));
     hipLaunchKernelGGL(index_export_kernel, dim3((u32)((x->cap + 255) / 256)), dim3(256), 0, c->stream,
-                       x->state.as<u64>(), x->slots.as<u8>(), x->cap, tmp.as<u8>(), x->counter.as<u64>());
-    hipError_t e = hipMemcpyAsync(out, tmp.p, x->count * 32, hipMemcpyDeviceToHost, c->stream);
+                       x->state.as<u64>(), x->slots.as<u8>(), x->cap, tmp.as<u8>(), x->count, x->counter.as<u64>());
+    hipError_t e = hipMemcpyAsync(c->h_word, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out, tmp.p, x->count * 32, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, MI_ERR_HIP, "mi_index_export: %s", hipGetErrorString(e));
+    if (c->h_word[0] != x->count)
+        return fail(c, MI_ERR_STATE, "mi_index_export: the index holds %llu digests, counted %llu",
+                    (unsigned long long)c->h_word[0], (unsigned long long)x->count);
     return MI_OK;
 }
 

@@ -16,7 +16,12 @@ holding none, C4's eight `index mod 8` shards (20 000 files each), and the Zipf 
 split into 8 parts (`split_threshold` 32 MiB; the owners agree on the boundary cuts over a gloo group or, in
 one process, through resolve_parts_local) -- `dup_of`, `first_global`, `n_total`, `n_unique` against the
 oracle's marking of the rank-major concatenation; and `bench.py --gpus 8` launched BARE (no torchrun) prints a
-C4 line of the library's own exchange with `rccl_ranks: 8`."""
+C4 line of the library's own exchange with `rccl_ranks: 8`.
+
+Case "skew": every digest of the job belongs to rank 0 (single-chunk files chosen on the host so that the all-to-all
+form's owner_of gives 0 at every rank count up to 8), with repeats across ranks and, at n >= 3, a rank without rows --
+one owner marks the whole job and the others receive nothing."""
+import hashlib
 import os
 import subprocess
 import sys
@@ -55,6 +60,38 @@ def rank_files(rank, n):
     return sizes, cids
 
 
+def owner(digest, n):
+    """The owner rank of a digest in the all-to-all form (csrc/mi_comm.hip owner_of), restated:
+    ((LE u64 of bytes 8..15) >> 32) * n >> 32."""
+    return ((int.from_bytes(digest[8:16], "little") >> 32) * n) >> 32
+
+
+_SKEW = []
+
+
+def skew_blobs(count):
+    """`count` distinct files shorter than min_size (one chunk each) whose SHA-256 has owner 0 at 8 ranks (and so
+    at every smaller rank count)."""
+    i = 0
+    while len(_SKEW) < count:
+        blob = (hashlib.sha256(b"skew %d" % i).digest() * 64)[: 1 + (i * 211) % 2000]
+        if owner(hashlib.sha256(blob).digest(), 8) == 0:
+            _SKEW.append(blob)
+        i += 1
+    return _SKEW[:count]
+
+
+def skew_files(rank, n):
+    """A rank's files in case "skew": rank 0 the most, each later rank some of its own, some of its predecessor's and
+    some of rank 0's, one in-rank repeat; the last rank none (n >= 3)."""
+    if n >= 3 and rank == n - 1:
+        return []
+    pool = skew_blobs(300)
+    if rank == 0:
+        return pool[:120] + pool[:1]
+    return pool[100 + 20 * rank: 130 + 20 * rank] + pool[5 * rank: 5 * rank + 10] + pool[100 + 20 * rank: 101 + 20 * rank]
+
+
 CHILD_COMMON = r"""
 import os, sys, time
 import numpy as np
@@ -62,7 +99,7 @@ sys.path.insert(0, %(root)r)
 sys.path.insert(0, os.path.join(%(root)r, "tests"))
 import torch  # noqa: F401
 import makisu_amd
-from test_gpu_native_exchange import rank_files, SEED
+from test_gpu_native_exchange import rank_files, skew_files, SEED
 """
 
 CHILD_COMMON += r"""
@@ -80,6 +117,10 @@ def fill(case, b, rank, n):
         sizes, cids = rank_files(rank, n)
         if sizes:
             b.add_synthetic(sizes, cids, seed=SEED)
+        return []
+    if case == "skew":
+        for i, blob in enumerate(skew_files(rank, n)):
+            b.add_bytes(blob, tag=i)
         return []
     return W.fill_batch(b, shard_of(case, rank, n))
 """
@@ -182,6 +223,12 @@ def _check(oracle, d, n, case="ragged"):
         assert (n < 3) or counts[-1] == 0
         assert want_unique < len(allrows)
         assert any((o["dup"] >= 0).any() and r > 0 for r, o in enumerate(outs))
+    elif case == "skew":
+        assert counts == [len(skew_files(r, n)) for r in range(n)]          # one chunk per file
+        assert all(owner(d.tobytes(), n) == 0 for d in allrows)              # rank 0 marks the whole job
+        assert (n < 3) or counts[-1] == 0
+        assert want_unique < len(allrows)
+        assert all((o["dup"] >= 0).any() for r, o in enumerate(outs) if r > 0 and counts[r])
     elif case == "c4":
         assert min(counts) > 100000 and len(allrows) - want_unique <= 2     # distinct contents (1-byte tails may coincide)
     else:
@@ -190,7 +237,7 @@ def _check(oracle, d, n, case="ragged"):
     return counts
 
 
-CASES = [(2, "ragged"), (3, "ragged"), (8, "ragged"), (8, "c4"), (8, "c5")]
+CASES = [(2, "ragged"), (3, "ragged"), (8, "ragged"), (8, "c4"), (8, "c5"), (2, "skew"), (8, "skew")]
 FORMS = ["allgather", "alltoall"]          # mi_dedup_allgather[_all]; mi_dedup_alltoall[_all] -- the hash-partitioned form, held
                                            # against the oracle AND, in the same process, against the all-gather form's column
 
