@@ -8,10 +8,11 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmakisu_mi.so")
-SOURCES = ["mi_api.hip", "gear_cdc.hip", "sha256.hip", "tables.hip", "crc32.hip", "mi_tree.hip", "mi_comm.hip",
+SOURCES = ["mi_api.hip", "mi_group.hip", "gear_cdc.hip", "sha256.hip", "tables.hip", "crc32.hip", "mi_tree.hip", "mi_comm.hip",
            "mi_index.hip", "mi_alloc.hip", "mi_arena.hip", "mi_tar.hip", "mi_stage.hip", "mi_layer.hip", "mi_memfs.hip"]
-HEADERS = ["mi_common.h", "mi_internal.h", "mi_local.h", "host_sha256.h", "mi_hostpath.h", "mi_memtree.h", os.path.join("..", "..", "include", "makisu_mi.h"),
-           os.path.join("..", "..", "include", "makisu_mi_host.h")]
+# every header there is, listed from the directories: a new one cannot be forgotten
+INCLUDE = os.path.join(HERE, "..", "include")
+HEADERS = sorted(os.path.join(d, h) for d in (CSRC, INCLUDE) for h in os.listdir(d) if h.endswith(".h"))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-result",
          "-fno-gpu-rdc"]
@@ -26,7 +27,7 @@ def needs_build():
     if not os.path.exists(LIB):
         return True
     t = os.path.getmtime(LIB)
-    deps = [os.path.join(CSRC, s) for s in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    deps = [os.path.join(CSRC, s) for s in SOURCES] + HEADERS + [os.path.abspath(__file__)]
     return any(os.path.getmtime(d) > t for d in deps)
 
 
@@ -53,4 +54,9 @@ def build(force=False, verbose=False):
 
 
 if __name__ == "__main__":
-    print(build(force=True, verbose=True))
+    import sys
+    if sys.argv[1:] == ["--list"]:      # for the sanitizer builds (tools/*_host_tests.sh): "<source path> <its extra flags>" per line
+        for src in SOURCES:
+            print(" ".join([os.path.join(CSRC, src)] + EXTRA.get(src, [])))
+    else:
+        print(build(force=True, verbose=True))

@@ -58,6 +58,11 @@ int fail(mi_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+std::string ctx_error(mi_ctx* c) {
+    std::lock_guard<std::mutex> g(g_err_mu);
+    return c->err;
+}
+
 }  // namespace mi
 
 namespace {
@@ -174,23 +179,8 @@ int ensure_stager(mi_ctx* c) {
 }
 // host-fed bytes are on their way (a tree walk has begun): the reader threads set up while the walk lists its first
 // directories; the first block or path that reaches them waits for whoever is not ready yet
-// ---- a group of batches behind one handle (mi_internal.h: members) -----------------------------------------------------------
-static inline bool is_group(const mi_batch* b) { return !b->members.empty(); }
-constexpr u32 kGroupSplit = 0xFFFFFFFFu;             // row_member of a file that is split over the members as parts
-constexpr u64 kGroupAtShift = 48, kGroupAtMask = (1ull << kGroupAtShift) - 1;       // a group's "arena offset": member << 48 | offset
-static int group_fail(mi_batch* h, size_t k, int rc) {
-    std::string m;
-    { std::lock_guard<std::mutex> g(g_err_mu); m = h->members[k]->ctx->err; }
-    return mi::fail(h->ctx, rc, "gpu %zu of %zu: %s", k, h->members.size(), m.c_str());
-}
-static size_t group_least_loaded(const mi_batch* h) {
-    size_t k = 0;
-    for (size_t i = 1; i < h->members.size(); ++i) if (h->member_bytes[i] < h->member_bytes[k]) k = i;
-    return k;
-}
-
 extern "C" void mi_batch_expect_host_bytes(mi_batch* b) {
-    if (is_group(b)) { for (mi_batch* m : b->members) mi_batch_expect_host_bytes(m); return; }
+    if (b->group) return group_expect_host_bytes(b);
     mi_ctx* c = b->ctx;
     if (!c->stager) c->stager = stager_create(c, c->stage_threads, c->staging_bytes);
 }
@@ -893,8 +883,6 @@ int mi_ctx_destroy(mi_ctx* c) {
     for (auto e : c->ev) if (e) (void)hipEventDestroy(e);
     if (c->sha_done) (void)hipEventDestroy(c->sha_done);
     if (c->h_word) (void)hipHostFree(c->h_word);
-    c->gear_table.release(); c->heads.release(); c->crc_consts.release();
-    c->dd_table.release(); c->dd_slot.release(); c->dd_nuniq.release(); c->dd_tag.release();
     if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return MI_OK;
@@ -917,7 +905,6 @@ int mi_sha_valu_roof(mi_ctx* c, uint32_t waves_per_simd, uint32_t blocks, double
     *bytes_per_second = measure_sha_valu_roof(c->prop.multiProcessorCount, (int)waves_per_simd, blocks,
                                               scratch.as<u32>(), c->stream, c->ev[0], c->ev[1]);
     const hipError_t e = hipGetLastError();
-    scratch.release();
     if (e != hipSuccess || *bytes_per_second <= 0) return fail(c, MI_ERR_HIP, "mi_sha_valu_roof: %s", hipGetErrorString(e));
     return MI_OK;
 }
@@ -937,8 +924,6 @@ int mi_batch_begin(mi_ctx* c, uint64_t n_files_hint, uint64_t bytes_hint, mi_bat
     HIPCHK(c, hipSetDevice(c->device));
     mi_batch* b = new mi_batch();
     b->ctx = c;
-    memset(&b->stats, 0, sizeof b->stats);
-    memset(&b->stage_stats, 0, sizeof b->stage_stats);
     b->files.reserve(n_files_hint);
     b->keep_sums = c->file_sums;
     hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
@@ -1037,65 +1022,7 @@ int mi_batch_add_path(mi_batch* b, const char* path, uint64_t size, uint64_t use
 int mi_batch_add_paths(mi_batch* b, uint64_t n, const char* const* paths, const uint64_t* sizes,
                        const uint64_t* user_tags) {
     if (!b || (n && (!paths || !sizes))) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        // each file to the member with the fewest bytes so far (the streaming form of longest-processing-time-first: the walk
-        // hands files over as it finds them); a member's files keep the walk's order among themselves
-        const size_t nm = b->members.size();
-        std::vector<std::vector<const char*>> mp(nm);
-        std::vector<std::vector<u64>> ms(nm), mt(nm);
-        static const u64 split_min = [] {
-            const char* e = getenv("MI_COMMIT_SPLIT_MIB");
-            const long v = e && *e ? atol(e) : 256;
-            return v <= 0 ? ~0ull : (u64)v << 20;
-        }();
-        for (u64 i = 0; i < n; ++i) {
-            if (sizes[i] >= split_min && sizes[i] >= 2 * mi_sum::kChunk) {
-                // A file of 256 MiB and more is SPLIT: one part per member, at most -- each part to the member with
-                // the fewest bytes so far, staged over that GPU's own link behind its halo (mi_batch_add_path_part).  Parts begin
-                // on MiB boundaries of the file, so every 1 MiB chunk the tar writer checks lies in ONE part's own range.  The
-                // parts' owners agree on the boundary cuts when the group runs (group_resolve_parts).
-                u64 np = std::min<u64>(nm, sizes[i] / (split_min / 2 ? split_min / 2 : 1));
-                if (np < 2) np = 2;
-                const u64 step = (sizes[i] / np + mi_sum::kChunk - 1) / mi_sum::kChunk * mi_sum::kChunk;
-                mi_batch::Split sp;
-                sp.size = sizes[i];
-                for (u64 begin = 0; begin < sizes[i]; begin += step) {
-                    const u64 end = std::min(begin + step, (u64)sizes[i]);
-                    const size_t k = group_least_loaded(b);
-                    // (the member's earlier pending files first: a part is added at once, its row must follow theirs)
-                    if (!mp[k].empty()) {
-                        const int rc0 = mi_batch_add_paths(b->members[k], mp[k].size(), mp[k].data(), ms[k].data(), mt[k].data());
-                        if (rc0) return group_fail(b, k, rc0);
-                        mp[k].clear(); ms[k].clear(); mt[k].clear();
-                    }
-                    const u64 row = b->members[k]->files.size();
-                    const int rc = mi_batch_add_path_part(b->members[k], paths[i], sizes[i], begin, end, user_tags ? user_tags[i] : 0);
-                    if (rc) return group_fail(b, k, rc);
-                    b->member_bytes[k] += end - begin;
-                    sp.parts.push_back({(u32)k, row, begin, end});
-                }
-                b->row_member.push_back(kGroupSplit);
-                b->row_row.push_back(b->splits.size());
-                b->splits.push_back(std::move(sp));
-                b->total_bytes += sizes[i];
-                continue;
-            }
-            const size_t k = group_least_loaded(b);
-            b->member_bytes[k] += sizes[i] + 4096;                 // (a file costs something even when it is empty: rows, a descriptor)
-            b->row_member.push_back((u32)k);
-            b->row_row.push_back(b->members[k]->files.size() + mp[k].size());
-            mp[k].push_back(paths[i]);
-            ms[k].push_back(sizes[i]);
-            mt[k].push_back(user_tags ? user_tags[i] : 0);
-            b->total_bytes += sizes[i];
-        }
-        for (size_t k = 0; k < nm; ++k) {
-            if (mp[k].empty()) continue;
-            const int rc = mi_batch_add_paths(b->members[k], mp[k].size(), mp[k].data(), ms[k].data(), mt[k].data());
-            if (rc) return group_fail(b, k, rc);
-        }
-        return MI_OK;
-    }
+    if (b->group) return group_add_paths(b, n, paths, sizes, user_tags);
     mi_ctx* c = b->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) return MI_OK;
@@ -1132,15 +1059,7 @@ int mi_batch_add_paths(mi_batch* b, uint64_t n, const char* const* paths, const 
 // (mi_batch_add_placed): where a file lies in the arena has nothing to do with its index.
 extern "C" int mi_batch_add_block(mi_batch* b, const void* src, uint64_t len, void (*release)(void*), void* release_arg,
                                   uint64_t* at_out) {
-    if (b && is_group(b)) {                          // the whole block -- a directory's small files -- to ONE member
-        const size_t k = group_least_loaded(b);
-        uint64_t at = 0;
-        const int rc = mi_batch_add_block(b->members[k], src, len, release, release_arg, &at);
-        if (rc) return group_fail(b, k, rc);
-        b->member_bytes[k] += len;
-        if (at_out) *at_out = ((u64)k << kGroupAtShift) | at;
-        return MI_OK;
-    }
+    if (b && b->group) return group_add_block(b, src, len, release, release_arg, at_out);
     std::shared_ptr<void> keep(release_arg, release ? release : +[](void*) {});
     if (!b || !src || !at_out) return MI_ERR_INVALID;
     mi_ctx* c = b->ctx;
@@ -1163,27 +1082,7 @@ extern "C" int mi_batch_add_block(mi_batch* b, const void* src, uint64_t len, vo
 extern "C" int mi_batch_add_placed(mi_batch* b, uint64_t n, const uint64_t* arena_off, const uint64_t* sizes,
                                    const uint64_t* tags, const uint64_t* sums) {
     if (!b || (n && (!arena_off || !sizes))) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // rows of blocks that went to different members, in the walk's order
-        const size_t nm = b->members.size();
-        std::vector<std::vector<u64>> mo(nm), ms(nm), mt(nm), mq(nm);
-        for (u64 i = 0; i < n; ++i) {
-            const size_t k = (size_t)(arena_off[i] >> kGroupAtShift);
-            if (k >= nm) return fail(b->ctx, MI_ERR_INVALID, "mi_batch_add_placed: no such member");
-            b->row_member.push_back((u32)k);
-            b->row_row.push_back(b->members[k]->files.size() + mo[k].size());
-            mo[k].push_back(arena_off[i] & kGroupAtMask);
-            ms[k].push_back(sizes[i]);
-            mt[k].push_back(tags ? tags[i] : 0);
-            if (sums) { mq[k].push_back(sums[2 * i]); mq[k].push_back(sums[2 * i + 1]); }
-            b->total_bytes += sizes[i];
-        }
-        for (size_t k = 0; k < nm; ++k) {
-            if (mo[k].empty()) continue;
-            const int rc = mi_batch_add_placed(b->members[k], mo[k].size(), mo[k].data(), ms[k].data(), mt[k].data(), sums ? mq[k].data() : nullptr);
-            if (rc) return group_fail(b, k, rc);
-        }
-        return MI_OK;
-    }
+    if (b->group) return group_add_placed(b, n, arena_off, sizes, tags, sums);
     if (b->staged) return fail(b->ctx, MI_ERR_STATE, "batch already ran; begin a new batch");
     for (u64 i = 0; i < n; ++i) {
         if (sizes[i] > b->arena_used || arena_off[i] > b->arena_used - sizes[i])          // (no sum: it could wrap)
@@ -1199,9 +1098,12 @@ extern "C" int mi_batch_add_placed(mi_batch* b, uint64_t n, const uint64_t* aren
     }
     return MI_OK;
 }
-extern "C" int mi_batch_keeps_sums(mi_batch* b) { return b && (is_group(b) ? b->members[0]->keep_sums : b->keep_sums) ? 1 : 0; }
+extern "C" int mi_batch_keeps_sums(mi_batch* b) {
+    if (b && b->group) return group_keeps_sums(b);
+    return b && b->keep_sums ? 1 : 0;
+}
 extern "C" void mi_batch_keep_sums(mi_batch* b, int on) {
-    if (b && is_group(b)) { if (b->row_member.empty()) for (mi_batch* m : b->members) mi_batch_keep_sums(m, on); return; }
+    if (b && b->group) return group_keep_sums(b, on);
     if (b && b->files.empty()) b->keep_sums = on != 0;
 }
 
@@ -1213,14 +1115,7 @@ int mi_batch_reserve(mi_batch* b, uint64_t more_files, uint64_t more_bytes) { re
 int mi_batch_reserve_ahead(mi_batch* b, uint64_t more_files, uint64_t more_bytes) { return batch_reserve(b, more_files, more_bytes, true); }
 static int batch_reserve(mi_batch* b, uint64_t more_files, uint64_t more_bytes, bool ahead) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // every member its share and a quarter (the split is by bytes, not exact)
-        const u64 nm = b->members.size();
-        for (size_t k = 0; k < nm; ++k) {
-            const int rc = batch_reserve(b->members[k], more_files / nm + 1, more_bytes / nm + more_bytes / (4 * nm), ahead);
-            if (rc) return group_fail(b, k, rc);
-        }
-        return MI_OK;
-    }
+    if (b->group) return group_reserve(b, more_files, more_bytes, ahead);
     mi_ctx* c = b->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     if (b->staged) return fail(c, MI_ERR_STATE, "batch already ran; begin a new batch");
@@ -1556,75 +1451,9 @@ int mi_batch_wait(mi_batch* b) {
     return wait_pipeline(b);
 }
 
-// The parts of the group's split files agree on their boundary cuts (the parts protocol of include/makisu_mi.h, all owners in
-// this process): every member that holds parts makes its cuts under an assumed entry; then, round by round, every part but a
-// file's first is told its predecessor's last cut and the members re-select where that differed -- until no exit moved (one
-// round on ordinary data, at most parts-per-file).
-static int group_resolve_parts(mi_batch* h) {
-    const size_t nm = h->members.size();
-    std::vector<char> holds(nm, 0);
-    for (const mi_batch::Split& sp : h->splits) for (const mi_batch::SplitPart& pt : sp.parts) holds[pt.member] = 1;
-    {
-        std::vector<int> rcs(nm, MI_OK);
-        std::vector<std::thread> th;
-        for (size_t k = 0; k < nm; ++k) if (holds[k]) th.emplace_back([&, k] { rcs[k] = mi_batch_scan_cuts(h->members[k]); });
-        for (auto& t : th) t.join();
-        for (size_t k = 0; k < nm; ++k) if (rcs[k]) return group_fail(h, k, rcs[k]);
-    }
-    for (int round = 0; round < 70; ++round) {
-        std::vector<std::vector<mi_part_state>> st(nm);
-        for (size_t k = 0; k < nm; ++k) {
-            if (!holds[k]) continue;
-            uint64_t np = 0;
-            mi_batch_parts(h->members[k], nullptr, 0, &np);
-            st[k].resize(np ? np : 1);
-            const int rc = mi_batch_parts(h->members[k], st[k].data(), np, &np);
-            if (rc) return group_fail(h, k, rc);
-            st[k].resize(np);
-        }
-        auto state_of = [&](const mi_batch::SplitPart& pt) -> const mi_part_state* {
-            for (const mi_part_state& x : st[pt.member]) if (x.file_index == pt.row) return &x;
-            return nullptr;
-        };
-        bool redo = false;
-        for (const mi_batch::Split& sp : h->splits)
-            for (size_t i = 1; i < sp.parts.size(); ++i) {
-                const mi_part_state *prev = state_of(sp.parts[i - 1]), *cur = state_of(sp.parts[i]);
-                if (!prev || !cur) return mi::fail(h->ctx, MI_ERR_STATE, "a split file's part is not among its member's parts");
-                if (prev->exit != cur->entry) redo = true;
-                if (prev->exit != cur->entry || !cur->entry_confirmed) {
-                    const int rc = mi_batch_set_part_entry(h->members[sp.parts[i].member], sp.parts[i].row, prev->exit);
-                    if (rc) return group_fail(h, sp.parts[i].member, rc);
-                }
-            }
-        for (size_t k = 0; k < nm; ++k)
-            if (holds[k]) { const int rc = mi_batch_fix_cuts(h->members[k]); if (rc) return group_fail(h, k, rc); }
-        if (!redo) return MI_OK;
-    }
-    return mi::fail(h->ctx, MI_ERR_STATE, "the parts of a split file did not agree on their boundary cuts in 70 rounds");
-}
-
 int mi_batch_run(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // every member on a thread of its own: one GPU each
-        const size_t nm = b->members.size();
-        if (!b->splits.empty()) {
-            const int rc = group_resolve_parts(b);
-            if (rc) return rc;
-        }
-        std::vector<int> rcs(nm, MI_OK);
-        std::vector<std::thread> th;
-        for (size_t k = 1; k < nm; ++k) th.emplace_back([&, k] { rcs[k] = mi_batch_run(b->members[k]); });
-        rcs[0] = mi_batch_run(b->members[0]);
-        for (auto& t : th) t.join();
-        b->n_chunks = 0;
-        for (size_t k = 0; k < nm; ++k) {
-            if (rcs[k]) return group_fail(b, k, rcs[k]);
-            b->n_chunks += b->members[k]->n_chunks;
-        }
-        b->ran = true;
-        return MI_OK;
-    }
+    if (b->group) return group_run(b);
     if (b->ran || b->in_flight)
         return fail(b->ctx, MI_ERR_STATE, "batch already ran; use mi_batch_rerun");
     int rc = mi_batch_submit(b);
@@ -1646,21 +1475,7 @@ int mi_batch_rerun(mi_batch* b) {
 static void read_windows_drop(mi_batch* b);
 int mi_batch_reset(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        for (size_t k = 0; k < b->members.size(); ++k) {
-            const int rc = mi_batch_reset(b->members[k]);
-            if (rc) return group_fail(b, k, rc);
-        }
-        if (b->tree) { mi_batch_tree_free(b->tree); b->tree = nullptr; }
-        b->row_member.clear();
-        b->row_row.clear();
-        b->splits.clear();
-        b->member_bytes.assign(b->members.size(), 0);
-        b->total_bytes = 0;
-        b->n_chunks = 0;
-        b->ran = false;
-        return MI_OK;
-    }
+    if (b->group) return group_reset(b);
     mi_ctx* c = b->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     if (b->in_flight) return fail(c, MI_ERR_STATE, "batch is in flight; mi_batch_wait first");
@@ -1711,12 +1526,7 @@ const char* mi_batch_stage_note(mi_batch* b) {
 
 int mi_batch_counts(mi_batch* b, uint64_t* n_files, uint64_t* n_chunks, uint64_t* n_bytes) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        if (n_files) *n_files = b->row_member.size();
-        if (n_chunks) *n_chunks = b->n_chunks;
-        if (n_bytes) *n_bytes = b->total_bytes;
-        return MI_OK;
-    }
+    if (b->group) return group_counts(b, n_files, n_chunks, n_bytes);
     if (n_files) *n_files = b->files.size();
     if (n_chunks) *n_chunks = b->n_chunks;
     if (n_bytes) *n_bytes = b->total_bytes;
@@ -1801,36 +1611,7 @@ int mi_batch_read_back(mi_batch* b, void* out, uint64_t cap) {
 // the chunk rows mi_batch_files / _chunks bring along.
 int mi_batch_roots(mi_batch* b, uint8_t* out, uint64_t cap) {
     if (!b || (!out && cap)) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // the members' roots, put back into the walk's order
-        if (!b->ran) return fail(b->ctx, MI_ERR_STATE, "roots requested before mi_batch_run");
-        const u64 nf = b->row_member.size();
-        if (cap < nf) return fail(b->ctx, MI_ERR_CAPACITY, "root buffer holds %llu rows, need %llu", (unsigned long long)cap, (unsigned long long)nf);
-        std::vector<std::vector<u8>> mr(b->members.size());
-        for (size_t k = 0; k < b->members.size(); ++k) {
-            const u64 n = b->members[k]->files.size();
-            mr[k].resize(n * 32 + 32);
-            const int rc = mi_batch_roots(b->members[k], mr[k].data(), n);
-            if (rc) return group_fail(b, k, rc);
-        }
-        for (u64 g = 0; g < nf; ++g) {
-            if (b->row_member[g] != kGroupSplit) { memcpy(out + 32 * g, mr[b->row_member[g]].data() + 32 * b->row_row[g], 32); continue; }
-            // a split file's root: mi_chunk_root over its parts' chunk digests put end to end (include/makisu_mi.h, "parts")
-            std::vector<u8> dg;
-            for (const mi_batch::SplitPart& pt : b->splits[b->row_row[g]].parts) {
-                const mi_file_result* fr = nullptr;
-                const mi_chunk_result* cr = nullptr;
-                uint64_t n1 = 0, n2 = 0;
-                int rc = mi_batch_files_view(b->members[pt.member], &fr, &n1);
-                if (!rc) rc = mi_batch_chunks_view(b->members[pt.member], &cr, &n2);
-                if (rc) return group_fail(b, pt.member, rc);
-                const mi_file_result& f = fr[pt.row];
-                for (u64 j = 0; j < f.n_chunks; ++j) { const u8* d = cr[f.first_chunk + j].sha256; dg.insert(dg.end(), d, d + 32); }
-            }
-            const int rc = mi_chunk_root(dg.data(), dg.size() / 32, out + 32 * g);
-            if (rc) return fail(b->ctx, rc, "the root of a split file");
-        }
-        return MI_OK;
-    }
+    if (b->group) return group_roots(b, out, cap);
     mi_ctx* c = b->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     if (!b->ran) return fail(c, MI_ERR_STATE, "roots requested before mi_batch_run");
@@ -1881,48 +1662,11 @@ static void read_windows_drop(mi_batch* b) {
     }
     b->rb_next = kReadWinMin;
 }
+// Bytes [at, at + len) of the arena, which lie in row f, through the windows.
 // while_staging: the caller is the pipelined commit (mi_memfs.hip) -- the batch is still being staged and scanned by another
 // thread; the file's bytes are waited for (stager_wait_landed), nothing else of the batch's state is touched
-// own_range: the row is a PART and `offset` a FILE offset inside the part's own range [begin, end) (a split file of a batch group)
-static int read_file_impl(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, bool while_staging, bool own_range = false) {
-    if (!b || (!dst && len)) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // from the GPU that holds the file -- a split file: from the GPUs that hold its parts
-        if (file_index >= b->row_member.size()) return fail(b->ctx, MI_ERR_INVALID, "mi_batch_read_file: no file %llu", (unsigned long long)file_index);
-        if (b->row_member[file_index] == kGroupSplit) {
-            const mi_batch::Split& sp = b->splits[b->row_row[file_index]];
-            if (offset > sp.size || len > sp.size - offset) return fail(b->ctx, MI_ERR_INVALID, "mi_batch_read_file: outside split file %llu", (unsigned long long)file_index);
-            u8* d = (u8*)dst;
-            for (const mi_batch::SplitPart& pt : sp.parts) {
-                if (!len) break;
-                if (offset >= pt.end) continue;
-                const u64 take = std::min(len, pt.end - offset);
-                const int rc = read_file_impl(b->members[pt.member], pt.row, offset, d, take, while_staging, true);
-                if (rc) return group_fail(b, pt.member, rc);
-                d += take;
-                offset += take;
-                len -= take;
-            }
-            return MI_OK;
-        }
-        const size_t k = b->row_member[file_index];
-        const int rc = read_file_impl(b->members[k], b->row_row[file_index], offset, dst, len, while_staging);
-        return rc ? group_fail(b, k, rc) : MI_OK;
-    }
+static int read_arena(mi_batch* b, const mi_batch::FileRec& f, u64 at, void* dst, u64 len, bool while_staging) {
     mi_ctx* c = b->ctx;
-    if (!while_staging && (!b->staged || b->in_flight))
-        return fail(c, MI_ERR_STATE, "mi_batch_read_file: the batch is not staged, or in flight");
-    if (file_index >= b->files.size()) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: no file %llu", (unsigned long long)file_index);
-    const mi_batch::FileRec& f = b->files[file_index];
-    if (f.part >= 0) {
-        if (!own_range) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: file %llu is a part", (unsigned long long)file_index);
-        const PartRec& pr = b->parts[f.part];
-        if (offset < pr.begin || offset > pr.end || len > pr.end - offset)
-            return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside the part [%llu, %llu)", (unsigned long long)offset,
-                        (unsigned long long)len, (unsigned long long)pr.begin, (unsigned long long)pr.end);
-        offset -= f.origin;                          // from here on: an offset inside the staged range
-    } else if (offset > f.size || len > f.size - offset)
-        return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside file %llu of %llu bytes", (unsigned long long)offset,
-                    (unsigned long long)len, (unsigned long long)file_index, (unsigned long long)f.size);
     if (!len) return MI_OK;
     HIPCHK(c, hipSetDevice(c->device));
     {
@@ -1951,7 +1695,6 @@ static int read_file_impl(mi_batch* b, uint64_t file_index, uint64_t offset, voi
         b->rb_bytes += want;
         return MI_OK;
     };
-    u64 at = f.off + offset;
     u8* d = (u8*)dst;
     while (len) {
         mi_batch::ReadWin* w = &b->rb[b->rb_cur];
@@ -2011,6 +1754,42 @@ static int read_file_impl(mi_batch* b, uint64_t file_index, uint64_t offset, voi
     }
     return MI_OK;
 }
+// what every read of a row begins with; *f: the row
+static int read_row(mi_batch* b, uint64_t file_index, bool while_staging, const mi_batch::FileRec** f) {
+    mi_ctx* c = b->ctx;
+    if (!while_staging && (!b->staged || b->in_flight))
+        return fail(c, MI_ERR_STATE, "mi_batch_read_file: the batch is not staged, or in flight");
+    if (file_index >= b->files.size()) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: no file %llu", (unsigned long long)file_index);
+    *f = &b->files[file_index];
+    return MI_OK;
+}
+static int read_file_impl(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, bool while_staging) {
+    if (!b || (!dst && len)) return MI_ERR_INVALID;
+    if (b->group) return group_read_file(b, file_index, offset, dst, len, while_staging);
+    mi_ctx* c = b->ctx;
+    const mi_batch::FileRec* f = nullptr;
+    const int rc = read_row(b, file_index, while_staging, &f);
+    if (rc) return rc;
+    if (f->part >= 0) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: file %llu is a part", (unsigned long long)file_index);
+    if (offset > f->size || len > f->size - offset)
+        return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside file %llu of %llu bytes", (unsigned long long)offset,
+                    (unsigned long long)len, (unsigned long long)file_index, (unsigned long long)f->size);
+    return read_arena(b, *f, f->off + offset, dst, len, while_staging);
+}
+// (mi_internal.h) the row is a PART and `offset` a FILE offset inside the part's own range [begin, end): a split file of a batch group
+int mi_batch_read_part(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, int while_staging) {
+    if (!b || (!dst && len)) return MI_ERR_INVALID;
+    mi_ctx* c = b->ctx;
+    const mi_batch::FileRec* f = nullptr;
+    const int rc = read_row(b, file_index, while_staging, &f);
+    if (rc) return rc;
+    if (f->part < 0) return fail(c, MI_ERR_INVALID, "file %llu is not a part", (unsigned long long)file_index);
+    const PartRec& pr = b->parts[f->part];
+    if (offset < pr.begin || offset > pr.end || len > pr.end - offset)
+        return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside the part [%llu, %llu)", (unsigned long long)offset,
+                    (unsigned long long)len, (unsigned long long)pr.begin, (unsigned long long)pr.end);
+    return read_arena(b, *f, f->off + (offset - f->origin), dst, len, while_staging);     // (the staged range begins at file offset `origin`)
+}
 int mi_batch_read_file(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len) {
     return read_file_impl(b, file_index, offset, dst, len, false);
 }
@@ -2019,16 +1798,7 @@ int mi_batch_read_file_landed(mi_batch* b, uint64_t file_index, uint64_t offset,
 }
 
 void mi_batch_read_stats(mi_batch* b, double* wait_s, double* fetch_s, uint64_t* fetches, uint64_t* bytes) {
-    if (b && is_group(b)) {
-        double w = 0, f = 0;
-        uint64_t nf = 0, nb = 0;
-        for (mi_batch* m : b->members) { w += m->rb_wait_s; f += m->rb_fetch_s; nf += m->rb_fetches; nb += m->rb_bytes; }
-        if (wait_s) *wait_s = w;
-        if (fetch_s) *fetch_s = f;
-        if (fetches) *fetches = nf;
-        if (bytes) *bytes = nb;
-        return;
-    }
+    if (b && b->group) return group_read_stats(b, wait_s, fetch_s, fetches, bytes);
     if (wait_s) *wait_s = b ? b->rb_wait_s : 0;
     if (fetch_s) *fetch_s = b ? b->rb_fetch_s : 0;
     if (fetches) *fetches = b ? b->rb_fetches : 0;
@@ -2037,23 +1807,10 @@ void mi_batch_read_stats(mi_batch* b, double* wait_s, double* fetch_s, uint64_t*
 // the layer writer's check (mi_layer.hip): the sums of chunk k (1 MiB of the FILE) of a row as they were taken where the bytes were
 // read; *has = 0: the batch keeps none for this row.  A split file's chunk lies in the own range of exactly one part (parts begin
 // on MiB boundaries of the file).
-static const mi_batch::SplitPart* split_part_of(const mi_batch::Split& sp, u64 file_off) {
-    for (const mi_batch::SplitPart& pt : sp.parts) if (file_off >= pt.begin && file_off < pt.end) return &pt;
-    return nullptr;
-}
 int mi_batch_chunk_sum(mi_batch* b, uint64_t file_index, uint64_t k, uint64_t* sum_a, uint64_t* sum_b, int* has) {
     if (!b || !has) return MI_ERR_INVALID;
     *has = 0;
-    if (is_group(b)) {
-        if (file_index >= b->row_member.size()) return MI_ERR_INVALID;
-        if (b->row_member[file_index] == kGroupSplit) {
-            const mi_batch::Split& sp = b->splits[b->row_row[file_index]];
-            const mi_batch::SplitPart* pt = split_part_of(sp, k * mi_sum::kChunk);
-            if (!pt) return sp.size == 0 ? MI_OK : MI_ERR_INVALID;
-            return mi_batch_chunk_sum(b->members[pt->member], pt->row, k, sum_a, sum_b, has);
-        }
-        return mi_batch_chunk_sum(b->members[b->row_member[file_index]], b->row_row[file_index], k, sum_a, sum_b, has);
-    }
+    if (b->group) return group_chunk_sum(b, file_index, k, sum_a, sum_b, has);
     if (file_index >= b->files.size()) return MI_ERR_INVALID;
     const mi_batch::FileRec& f = b->files[file_index];
     if (!f.sums) return MI_OK;
@@ -2067,34 +1824,19 @@ int mi_batch_chunk_sum(mi_batch* b, uint64_t file_index, uint64_t k, uint64_t* s
 // the read-back windows (two pinned 8 MiB buffers, a stream, two events) ahead of the first read: mi_memfs_reserve_device
 int mi_batch_prepare_read(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        for (size_t k = 0; k < b->members.size(); ++k) { const int rc = mi_batch_prepare_read(b->members[k]); if (rc) return group_fail(b, k, rc); }
-        return MI_OK;
-    }
+    if (b->group) return group_prepare_read(b);
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
     return read_windows(b);
 }
 void mi_batch_drop_windows(mi_batch* b) {
-    if (b && is_group(b)) { for (mi_batch* m : b->members) read_windows_drop(m); return; }
+    if (b && b->group) return group_drop_windows(b);
     if (b) read_windows_drop(b);
 }
 // A chunk that came back from HBM with other sums than it went with, twice: WHICH hop?  The chunk once more, by a plain copy
 // into memory of this call's own (not the windows, not their stream): the same sums as at the source -- HBM holds the right
 // bytes and the read-back windows delivered others; other sums -- the arena does not hold what the file had when it was read.
 int mi_batch_explain_chunk(mi_batch* b, uint64_t file_index, uint64_t chunk, char* msg, uint64_t cap) {
-    if (b && is_group(b)) {
-        if (file_index >= b->row_member.size() || !msg || cap < 16) return MI_ERR_INVALID;
-        u32 member = b->row_member[file_index];
-        u64 row = b->row_row[file_index];
-        if (member == kGroupSplit) {
-            const mi_batch::SplitPart* pt = split_part_of(b->splits[row], chunk * mi_sum::kChunk);
-            if (!pt) return MI_ERR_INVALID;
-            member = pt->member;
-            row = pt->row;
-        }
-        const int n = snprintf(msg, (size_t)cap, "gpu %u: ", member);
-        return mi_batch_explain_chunk(b->members[member], row, chunk, msg + n, cap - (uint64_t)n);
-    }
+    if (b && b->group) return group_explain_chunk(b, file_index, chunk, msg, cap);
     if (!b || !msg || !cap || file_index >= b->files.size()) return MI_ERR_INVALID;
     mi_ctx* c = b->ctx;
     const mi_batch::FileRec& f = b->files[file_index];
@@ -2118,25 +1860,14 @@ int mi_batch_explain_chunk(mi_batch* b, uint64_t file_index, uint64_t chunk, cha
     return MI_OK;
 }
 int mi_batch_file_size(mi_batch* b, uint64_t file_index, uint64_t* size) {       // (internal: mi_layer.hip)
-    if (b && is_group(b)) {
-        if (file_index >= b->row_member.size() || !size) return MI_ERR_INVALID;
-        if (b->row_member[file_index] == kGroupSplit) { *size = b->splits[b->row_row[file_index]].size; return MI_OK; }
-        return mi_batch_file_size(b->members[b->row_member[file_index]], b->row_row[file_index], size);
-    }
+    if (b && b->group) return group_file_size(b, file_index, size);
     if (!b || !size || file_index >= b->files.size() || b->files[file_index].part >= 0) return MI_ERR_INVALID;
     *size = b->files[file_index].size;
     return MI_OK;
 }
 int mi_batch_arena_info(mi_batch* b, uint64_t* bytes, uint64_t* pieces, uint64_t* moves) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        uint64_t tb = 0, tp = 0, tm = 0;
-        for (mi_batch* m : b->members) { uint64_t x = 0, y = 0, z = 0; mi_batch_arena_info(m, &x, &y, &z); tb += x; tp += y; tm += z; }
-        if (bytes) *bytes = tb;
-        if (pieces) *pieces = tp;
-        if (moves) *moves = tm;
-        return MI_OK;
-    }
+    if (b->group) return group_arena_info(b, bytes, pieces, moves);
     u64 mapped = 0, n = 0;
     arena_counts(&b->arena, &mapped, &n, nullptr);
     if (bytes) *bytes = b->arena.vm ? mapped : b->arena.bytes;
@@ -2146,19 +1877,14 @@ int mi_batch_arena_info(mi_batch* b, uint64_t* bytes, uint64_t* pieces, uint64_t
 }
 int mi_batch_arena_room(mi_batch* b, uint64_t* bytes) {
     if (!b || !bytes) return MI_ERR_INVALID;
-    if (is_group(b)) {                               // what every member can count on: the smallest
-        *bytes = ~0ull;
-        for (mi_batch* m : b->members) if (m->arena.bytes < *bytes) *bytes = m->arena.bytes;
-        return MI_OK;
-    }
+    if (b->group) return group_arena_room(b, bytes);
     *bytes = b->arena.bytes;
     return MI_OK;
 }
 const char* mi_last_error_of_batch(mi_batch* b) {                // (a copy of the caller's own: see mi::fail)
     static thread_local std::string mine;
     if (!b) return "";
-    std::lock_guard<std::mutex> g(g_err_mu);
-    mine = b->ctx->err;
+    mine = ctx_error(b->ctx);
     return mine.c_str();
 }
 
@@ -2168,55 +1894,9 @@ void mi_set_error(mi_batch* b, const char* msg) {                // b NULL: the 
     if (b) b->ctx->err = msg; else g_create_err = msg;
 }
 
-// One handle over n batches, one per ctx (hidden: mi_memfs_commit_layer_n's batch).  The head belongs to ctxs[0] (its errors are
-// reported there, "gpu k of n: ..." naming the member); it has no device state of its own.
-int mi_batch_group_begin(mi_ctx* const* ctxs, uint32_t n, mi_batch** out) {
-    if (!ctxs || n < 2 || n > 64 || !out) return MI_ERR_INVALID;
-    for (uint32_t i = 0; i < n; ++i) {
-        if (!ctxs[i]) return MI_ERR_INVALID;
-        for (uint32_t j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return fail(ctxs[0], MI_ERR_INVALID, "a batch group needs %u DIFFERENT ctxs", n);
-    }
-    mi_batch* h = new mi_batch();
-    h->ctx = ctxs[0];
-    memset(&h->stats, 0, sizeof h->stats);
-    memset(&h->stage_stats, 0, sizeof h->stage_stats);
-    ++h->ctx->live_children;
-    for (uint32_t i = 0; i < n; ++i) {
-        mi_batch* m = nullptr;
-        const int rc = mi_batch_begin(ctxs[i], 0, 0, &m);
-        if (rc) {
-            std::string e;
-            { std::lock_guard<std::mutex> g(g_err_mu); e = ctxs[i]->err; }
-            for (mi_batch* x : h->members) mi_batch_free(x);
-            h->members.clear();
-            --h->ctx->live_children;
-            delete h;
-            return fail(ctxs[0], rc, "gpu %u of %u: %s", i, n, e.c_str());
-        }
-        h->members.push_back(m);
-    }
-    h->member_bytes.assign(n, 0);
-    *out = h;
-    return MI_OK;
-}
-uint64_t mi_batch_group_splits(mi_batch* b) { return b ? b->splits.size() : 0; }
-int mi_batch_group_members(mi_batch* b, mi_batch* const** members, const uint64_t** bytes, uint64_t* n) {
-    if (!b || !n) return MI_ERR_INVALID;
-    *n = b->members.size();
-    if (members) *members = b->members.data();
-    if (bytes) *bytes = b->member_bytes.data();
-    return MI_OK;
-}
-
 int mi_batch_free(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
-    if (is_group(b)) {
-        if (b->tree) { mi_batch_tree_free(b->tree); b->tree = nullptr; }
-        for (mi_batch* m : b->members) mi_batch_free(m);
-        --b->ctx->live_children;
-        delete b;
-        return MI_OK;
-    }
+    if (b->group) return group_free(b);
     if (b->tree) { mi_batch_tree_free(b->tree); b->tree = nullptr; }
     mi_ctx* c = b->ctx;
     (void)hipSetDevice(c->device);
@@ -2226,7 +1906,6 @@ int mi_batch_free(mi_batch* b) {
     }
     (void)staging_sync(b);                      // reader threads may still hold pieces of this batch
     if (b->fsha_latch) { (void)stager_hash_wait(c, b->fsha_latch); b->fsha_latch = nullptr; }
-    b->fsha_len.release();
     for (int i = 0; i < 2; ++i) {
         if (b->ring_ev[i]) (void)hipEventDestroy(b->ring_ev[i]);
         if (b->ring[i]) (void)hipHostFree(b->ring[i]);
@@ -2245,18 +1924,6 @@ int mi_batch_free(mi_batch* b) {
         if (w.ev) (void)hipEventDestroy(w.ev);
     }
     if (b->h_files) (void)hipHostFree(b->h_files);
-    DevBuf* bufs[] = {&b->root_addr, &b->root_cnt, &b->rseg_cnt, &b->rseg_first, &b->rseg_total,
-                      &b->root_items_off, &b->root_items_len, &b->root_level[0], &b->root_level[1],
-                      &b->root_level[2], &b->root_level[3], &b->root_level[4], &b->root_addr2, &b->root_cnt2,
-                      &b->group_file, &b->group_index, &b->group_recs, &b->tile_lists, &b->tile_fast, &b->large_list,
-                      &b->large_group0, &b->seg_file, &b->seg_slot, &b->seg_n, &b->seg_first, &b->seg_group,
-                      &b->file_seg0, &b->ends32, &b->tile_file, &b->first_tile, &b->tile_raw, &b->crc_d, &b->ctl, &b->dd_table, &b->dd_slot,
-                      &b->q_off, &b->q_len, &b->q_id, &b->small_list, &b->file_off, &b->file_size, &b->cids,
-                      &b->n_chunks_d, &b->first, &b->scratch,
-                      &b->chunk_off, &b->chunk_len, &b->chunk_file, &b->chunk_start, &b->digests, &b->item_off, &b->item_len, &b->roots,
-                      &b->file_sha, &b->dup_of, &b->file_flags, &b->part_file, &b->part_group0, &b->part_halo,
-                      &b->part_entry, &b->rows_d, &b->file_rows_d, &b->file_base, &b->span_off, &b->span_len, &b->span_sums, &b->dense_list};
-    for (DevBuf* d : bufs) d->release();
     arena_release(&b->arena);
     delete b;
     return MI_OK;
@@ -2453,7 +2120,6 @@ int mi_sha256_many(mi_ctx* c, const void* data, const uint64_t* offsets, const u
         if (e == hipSuccess) e = hipMemcpy(dst, d_out.p, ng * 32, hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(c, MI_ERR_HIP, "mi_sha256_many: %s", hipGetErrorString(e));
     }
-    d_data.release(); d_off.release(); d_len.release(); d_out.release();
     if (!rc && !to_host.empty())
         for (u64 k = 0; k < ng; ++k) memcpy(out + 32 * g_idx[k], g_out.data() + 32 * k, 32);
     return rc;

@@ -379,12 +379,9 @@ struct Shares {                          // the all-to-all form's state of one c
     u64 n_recv = 0, n_total = 0;
     // before / after: the split | all-to-all #1 | (marking + answers) | all-to-all #2 | (scatter)
     hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    void release() {
-        for (auto& e : ev) { if (e) (void)hipEventDestroy(e); e = nullptr; }
-        for (DevBuf* d : {&hist, &cnt_send, &cnt_all, &send_dg, &send_row, &recv_dg, &recv_row, &ans, &back, &meta}) d->release();
+    ~Shares() {
+        for (auto e : ev) if (e) (void)hipEventDestroy(e);
         if (pin) (void)hipHostFree(pin);
-        pin = nullptr;
-        pin_words = 0;
     }
 };
 Shares* shares_of(mi_ctx* c) {
@@ -635,8 +632,7 @@ int mi_comm_destroy(mi_ctx* c) {
     }
     if (c->comm_scratch) {
         Exchange* x = (Exchange*)c->comm_scratch;
-        x->counts.release(); x->slab.release(); x->gathered.release(); x->compact.release(); x->dup.release();
-        if (x->sh) { x->sh->release(); delete x->sh; }
+        delete x->sh;
         if (x->pin) (void)hipHostFree(x->pin);
         for (auto e : x->ev) if (e) (void)hipEventDestroy(e);
         delete x;

@@ -38,11 +38,6 @@ typedef u32 u32x4 __attribute__((ext_vector_type(4)));
 
 namespace {
 
-// a DevBuf that frees itself: temporaries stay leak-free on every error return
-struct ScopedBuf : DevBuf {
-    ~ScopedBuf() { release(); }
-};
-
 __device__ __forceinline__ bool digest_eq32(const u8* a, const u8* b) {
     const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
     const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
@@ -174,7 +169,7 @@ int index_grow(mi_index* x, u64 min_cap) {
     while (cap < min_cap) cap <<= 1;
     if (cap == x->cap) return MI_OK;
     // export the current content, reallocate, re-insert
-    ScopedBuf old;
+    DevBuf old;
     const u64 have = x->count;
     if (have) {
         HIPCHK(c, old.ensure(have * 32));
@@ -275,8 +270,6 @@ void mi_index_free(mi_index* x) {
     if (!x) return;
     (void)hipSetDevice(x->ctx->device);
     (void)hipStreamSynchronize(x->ctx->stream);
-    x->state.release(); x->slots.release(); x->counter.release(); x->scratch.release(); x->dup.release();
-    x->row_state.release(); x->row_slot.release();
     --x->ctx->live_children;
     delete x;
 }
@@ -324,7 +317,7 @@ int mi_index_add_digests(mi_index* x, const void* digests, uint64_t n, uint8_t* 
     if (n_new) *n_new = 0;
     if (n_known) *n_known = 0;
     if (n == 0) return MI_OK;
-    ScopedBuf d;
+    DevBuf d;
     HIPCHK(c, d.ensure(n * 32));
     HIPCHK(c, x->scratch.ensure(n + 16));
     HIPCHK(c, x->dup.ensure(n * 8 + 16));
@@ -352,7 +345,7 @@ int mi_index_export(mi_index* x, void* out, uint64_t cap_digests) {
     if (cap_digests < x->count) return fail(c, MI_ERR_CAPACITY, "export buffer holds %llu digests, need %llu",
                                             (unsigned long long)cap_digests, (unsigned long long)x->count);
     if (x->count == 0) return MI_OK;
-    ScopedBuf tmp;
+    DevBuf tmp;
     HIPCHK(c, tmp.ensure(x->count * 32));
     HIPCHK(c, hipMemsetAsync(x->counter.p, 0, 8, c->stream));
     hipLaunchKernelGGL(index_export_kernel, dim3((u32)((x->cap + 255) / 256)), dim3(256), 0, c->stream,
@@ -375,7 +368,7 @@ int mi_index_import(mi_index* x, const void* digests, uint64_t n, uint64_t* n_ne
     if (n == 0) return MI_OK;
     // imported digests may repeat each other or the table's content: mark them first so only
     // unique rows probe (the kernel's no-equal-probers precondition)
-    ScopedBuf d, dup;
+    DevBuf d, dup;
     HIPCHK(c, d.ensure(n * 32));
     HIPCHK(c, dup.ensure(n * 8));
     HIPCHK(c, hipMemcpy(d.p, digests, n * 32, hipMemcpyHostToDevice));

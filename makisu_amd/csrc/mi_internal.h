@@ -1,5 +1,5 @@
 // mi_internal.h -- engine-internal state shared by the host translation units
-// (mi_api.hip: pipeline and C ABI; mi_comm.hip: RCCL digest exchange).  Not installed.
+// (mi_api.hip: pipeline and C ABI; mi_group.hip: one handle over n batches; mi_comm.hip: RCCL digest exchange).  Not installed.
 #pragma once
 
 #include "../../include/makisu_mi.h"
@@ -13,6 +13,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <utility>
 #include <vector>
 
 namespace mi {
@@ -23,9 +24,15 @@ bool       guard_alloc();
 hipError_t dev_alloc(void** p, size_t bytes);
 hipError_t dev_free(void* p);
 
+// Device memory with an owner: freed when the owner goes.  Whoever deletes the owner has made the owner's device current and
+// synchronised its streams first (mi_batch_free, mi_ctx_destroy, mi_index_free, mi_comm_destroy end in `delete`).
 struct DevBuf {
     void* p = nullptr;
     size_t bytes = 0;
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p(o.p), bytes(o.bytes) { o.p = nullptr; o.bytes = 0; }
+    DevBuf& operator=(DevBuf&& o) noexcept { std::swap(p, o.p); std::swap(bytes, o.bytes); return *this; }
+    ~DevBuf() { release(); }
     hipError_t ensure(size_t want) {
         if (want <= bytes) return hipSuccess;
         if (p) { (void)dev_free(p); p = nullptr; bytes = 0; }
@@ -79,6 +86,31 @@ struct PartRec {
 
 // sets the ctx's (or, for c == nullptr, the create-time) error message; returns code
 int fail(mi_ctx* c, int code, const char* fmt, ...);
+std::string ctx_error(mi_ctx* c);      // a copy of the ctx's message, taken under the lock every writer holds
+
+// mi_group.hip: what each mi_batch_* entry point of that name does for a GROUP HEAD (h->group set) instead
+struct Group;
+void group_expect_host_bytes(mi_batch* h);
+int  group_add_paths(mi_batch* h, u64 n, const char* const* paths, const u64* sizes, const u64* user_tags);
+int  group_add_block(mi_batch* h, const void* src, u64 len, void (*release)(void*), void* release_arg, u64* at_out);
+int  group_add_placed(mi_batch* h, u64 n, const u64* arena_off, const u64* sizes, const u64* tags, const u64* sums);
+int  group_keeps_sums(mi_batch* h);
+void group_keep_sums(mi_batch* h, int on);
+int  group_reserve(mi_batch* h, u64 more_files, u64 more_bytes, bool ahead);
+int  group_run(mi_batch* h);
+int  group_reset(mi_batch* h);
+int  group_counts(mi_batch* h, u64* n_files, u64* n_chunks, u64* n_bytes);
+int  group_roots(mi_batch* h, u8* out, u64 cap);
+int  group_read_file(mi_batch* h, u64 file_index, u64 offset, void* dst, u64 len, bool while_staging);
+void group_read_stats(mi_batch* h, double* wait_s, double* fetch_s, u64* fetches, u64* bytes);
+int  group_chunk_sum(mi_batch* h, u64 file_index, u64 k, u64* sum_a, u64* sum_b, int* has);
+int  group_prepare_read(mi_batch* h);
+void group_drop_windows(mi_batch* h);
+int  group_explain_chunk(mi_batch* h, u64 file_index, u64 chunk, char* msg, u64 cap);
+int  group_file_size(mi_batch* h, u64 file_index, u64* size);
+int  group_arena_info(mi_batch* h, u64* bytes, u64* pieces, u64* moves);
+int  group_arena_room(mi_batch* h, u64* bytes);
+int  group_free(mi_batch* h);
 
 // One host->device copy of a host-fed batch, with the sums of the bytes it carried
 // (MI_FLAG_VERIFY_STAGING): words w_0..w_{n-1} = the span as little-endian u64, the tail
@@ -165,7 +197,7 @@ struct mi_ctx {
 };
 
 struct mi_batch {
-    mi_ctx* ctx;
+    mi_ctx* ctx = nullptr;
     struct FileRec { mi::u64 off, size, tag; int part = -1; mi_sum::FileSum* sums = nullptr; mi::u64 origin = 0; };   // part: index into `parts`; sums: per 1 MiB
                                                                    // chunk, taken where the bytes were read (keep_sums); origin: the FILE
                                                                    // offset of the row's first staged byte (a part: begin - halo; else 0) --
@@ -178,18 +210,9 @@ struct mi_batch {
     bool parts_dirty = false;                // a confirmed entry differs from the one the cuts were made with
     mi::u64 total_bytes = 0;     // sum of sizes
     mi::u64 arena_used = 0;      // next free arena offset
-    // A GROUP HEAD (mi_batch_group_begin; mi_memfs_commit_layer_n): no arena, no stream -- a handle behind which the file rows of a
-    // walk are spread over one batch per ctx (one per GPU), each block / file going to the member with the fewest bytes so far.  The
-    // walk and the commit see ONE batch: group row g is row row_row[g] of members[row_member[g]].
-    std::vector<mi_batch*> members;
-    std::vector<mi::u32> row_member;
-    std::vector<mi::u64> row_row;
-    std::vector<mi::u64> member_bytes;
-    // a file of MI_COMMIT_SPLIT_MIB (256) MiB and more is SPLIT over the members as parts (mi_batch_add_path_part: the parts protocol):
-    // group row g with row_member[g] == kGroupSplit is splits[row_row[g]]
-    struct SplitPart { mi::u32 member; mi::u64 row, begin, end; };
-    struct Split { mi::u64 size; std::vector<SplitPart> parts; };
-    std::vector<Split> splits;
+    std::unique_ptr<mi::Group> group;        // set: a GROUP HEAD (mi_group.hip) -- no arena, no stream, only `ctx` and `tree` below are its own
+    mi_batch();                              // (both in mi_group.hip, where mi::Group is complete)
+    ~mi_batch();
     mi::Arena arena;
     bool keep_sums = false;      // every host-fed file row carries the sums of its bytes as they were READ (mi_filesum.h): what the layer
     mi_sum::Pool sum_pool;       // writer checks the bytes it frames against (MI_FLAG_FILE_SUMS; always for a MemFS handle's batch)
@@ -214,7 +237,7 @@ struct mi_batch {
     std::string stage_note;      // what the first verification mismatch looked like (even if repaired)
     std::mutex span_mu;          // guards the three below (reader threads + the inline window)
     std::vector<mi::StageSpan> stage_spans;   // MI_FLAG_VERIFY_STAGING: every copy, for the final pass
-    mi_stage_stats stage_stats;
+    mi_stage_stats stage_stats = {};
     mi::DevBuf span_off, span_len, span_sums;
     double ms_h2d = 0;
     // pipeline state: every batch owns a stream, so two batches can be in flight and the
@@ -224,7 +247,7 @@ struct mi_batch {
     mi::u64* h_counts = nullptr;             // pinned: [0] = chunk count, [1] = unique count
     bool staged = false, in_flight = false, ran = false, results_valid = false;
     mi::u64 n_chunks = 0, total_slots = 0;
-    mi_stats stats;
+    mi_stats stats = {};
     // CDC segments (gear_cdc.hip): a small file or one 256 KiB group of a large file
     mi::DevBuf small_list;                   // segments that are files <= one tile (wave per file)
     mi::DevBuf dense_list;                   // ... of them, those the bitmap-free kernel could not list (+ count)
@@ -273,7 +296,9 @@ struct mi_batch {
     bool h_roots_valid = false;
 };
 
-
+// mi_api.hip, for mi_group.hip: mi_batch_read_file[_landed] of a row that is a PART -- `offset` is a FILE offset and
+// [offset, offset + len) lies inside the part's own range [begin, end)
+extern "C" MI_LOCAL int mi_batch_read_part(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, int while_staging);
 
 #define HIPCHK(c, call)                                                                     \
     do {                                                                                    \

@@ -9,11 +9,11 @@ OUT=${MI_ASAN_DIR:-/tmp/mi_asan}
 RT=$(ls /opt/rocm/lib/llvm/lib/clang/*/lib/linux/libclang_rt.asan-x86_64.so | head -1)
 mkdir -p "$OUT"
 FLAGS="--offload-arch=gfx950 -O1 -g -std=c++17 -fPIC -fno-gpu-rdc -fsanitize=address,undefined -fno-gpu-sanitize -shared-libsan -fno-omit-frame-pointer"
-for f in mi_api gear_cdc sha256 tables crc32 mi_tree mi_comm mi_index mi_alloc mi_arena mi_tar mi_stage mi_layer mi_memfs; do
-    extra=""
-    [ "$f" = sha256 ] && extra="-mllvm -amdgpu-atomic-optimizer-strategy=None"
-    /opt/rocm/bin/hipcc $FLAGS $extra -c "$ROOT/makisu_amd/csrc/$f.hip" -o "$OUT/$f.o" &
-done
+rm -f "$OUT"/*.o
+# the sources and their per-file extra flags: makisu_amd/build.py's
+while read -r src extra; do
+    /opt/rocm/bin/hipcc $FLAGS $extra -c "$src" -o "$OUT/$(basename "$src" .hip).o" &
+done < <(python "$ROOT/makisu_amd/build.py" --list)
 wait
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -fno-gpu-rdc -fsanitize=address,undefined -fno-gpu-sanitize \
     -shared-libsan "$OUT"/*.o -ldl -lpthread -lz -o "$OUT/libmakisu_mi.so"
