@@ -1663,7 +1663,7 @@ static void read_windows_drop(mi_batch* b) {
     b->rb_next = kReadWinMin;
 }
 // Bytes [at, at + len) of the arena, which lie in row f, through the windows.
-// while_staging: the caller is the pipelined commit (mi_memfs.hip) -- the batch is still being staged and scanned by another
+// while_staging: the caller is the pipelined commit (mi_commit.hip) -- the batch is still being staged and scanned by another
 // thread; the file's bytes are waited for (stager_wait_landed), nothing else of the batch's state is touched
 static int read_arena(mi_batch* b, const mi_batch::FileRec& f, u64 at, void* dst, u64 len, bool while_staging) {
     mi_ctx* c = b->ctx;

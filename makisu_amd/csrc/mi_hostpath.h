@@ -1,6 +1,6 @@
 // mi_hostpath.h -- what the host-side restatements of lib/snapshot share: the walk's entry record, Go's path rules
 // (path.Clean / filepath.Join, pathutils.AbsPath / IsDescendantOfAny), the mount table of lib/mountutils.  Header-only;
-// no device code.  Users: mi_tree.hip (walks, stateless diffs), mi_memfs.hip (MemFS, copy ops, untar).
+// no device code.  Users: mi_tree.hip (walks, stateless diffs), mi_copyfs.h and its users (mi_memfs.hip: MemFS, untar; mi_copyops.hip; mi_commit.hip).
 #pragma once
 #include "../../include/makisu_mi.h"
 #include "mi_local.h"
@@ -221,7 +221,7 @@ inline std::string rel_to(const std::string& base, const std::string& path) {   
 // Sorting paths the way Go compares strings (bytewise), for inputs that arrive nearly sorted -- a walk's order, a layer's
 // keys in the order a walk put them in: a STABLE NATURAL MERGE SORT of indices.  Maximal non-decreasing runs are found
 // first and merged pairwise, so the cost is a few passes instead of log2(n) (users: mi_entries_commit_order in
-// mi_tree.hip, the layer's commit order in mi_memfs.hip).
+// mi_tree.hip, the layer's commit order in mi_copyfs.h).
 struct KeyRef { const char* p; uint32_t len; };
 inline bool key_less(const KeyRef& a, const KeyRef& b) {       // bytewise, like Go's string comparison
     const uint32_t m = a.len < b.len ? a.len : b.len;

@@ -29,8 +29,8 @@
 // (1 = the sequential walker below, the reference's shape) overrides the thread count.
 //
 // Also here, on entry lists and without state: the commit order, tario.IsSimilarHeader, the scan's layer diff
-// (mi_snapshot_diff) and the layer merge (mi_entries_apply_layer).  MemFS itself, the copy ops and what surrounds a
-// COPY step: mi_memfs.hip.
+// (mi_snapshot_diff) and the layer merge (mi_entries_apply_layer).  MemFS itself: mi_memfs.hip; the copy ops and what
+// surrounds a COPY step: mi_copyops.hip; the commit: mi_commit.hip.
 #include "mi_memtree.h"
 #include "mi_filesum.h"     // the sums of a small file's bytes, taken where the directory reader read them
 
@@ -868,7 +868,7 @@ static void walk_root(Walker* w, const std::string& root) {
                 (unsigned long long)block_pool().n_carved, (unsigned long long)block_pool().n_own, g_inline_peak.load() / 1e6, (unsigned long long)g_inline_files.load());
 }
 
-// the walk the copy ops need (mi_memfs.hip): one source, scan rules, no blacklist
+// the walk the copy ops need (mi_copyops.hip): one source, scan rules, no blacklist
 int scan_walk_collect(const std::string& src, const std::string& link_root, Tree* out, std::string* err) {
     Walker w;
     w.batch = nullptr;
@@ -951,7 +951,7 @@ int mi_batch_add_tree(mi_batch* b, const char* root, const char* rel_base, const
     void** slot = mi_batch_tree_slot(b);
     if (!*slot) *slot = new Tree();
     Tree* t = (Tree*)*slot;
-    t->want_stamps = true;                                       // (a commit records the inodes it hashed: mi_memfs.hip)
+    t->want_stamps = true;                                       // (a commit records the inodes it hashed: mi_commit.hip)
     if (t->stamps.size() < t->entries.size()) { t->stamps.resize(t->entries.size()); t->known.resize(t->entries.size()); }
     mi_walk::Walker w;
     w.batch = b;

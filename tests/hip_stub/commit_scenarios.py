@@ -652,7 +652,33 @@ def scenario_oversize_copy(tmp, eng):
     print("OK oversize_copy")
 
 
+def scenario_reserved(tmp, eng):
+    """mi_memfs_reserve_device makes the batch the handle's commits USE: reserve, a scanning commit, a change, a second scanning
+    commit, close -- one arena for all of it (the test reads MI_ARENA_TRACE: one address range reserved, one given back; a first
+    commit that throws the reserved batch away and begins another shows two and two); the tars are the header-only commit's"""
+    root = os.path.join(tmp, "reserved_root")
+    files = make_tree(root, seed=61, mtime=MTIME)
+    with M.MemFS(root) as fs, M.MemFS(root) as plain:
+        fs.reserve_device(eng, len(files), sum(map(len, files.values())))
+        res, raw = commit_to_bytes(fs, tmp, "rv0.tar", must_scan=True, engine=eng)
+        _, raw0 = commit_to_bytes(plain, tmp, "rv0p.tar", must_scan=True)
+        assert raw == raw0 and {n: d for n, m, d in tar_members(raw) if m.isfile()} == files
+        assert res["stats"]["arena_moves"] == 0, res["stats"]
+        rel = "d03/nested/deeper/f003.bin"
+        new = os.urandom(len(files[rel]) + 11)
+        write_file(os.path.join(root, rel), new, 0o644, MTIME + 2)
+        os.utime(os.path.join(root, "d03/nested/deeper"), (MTIME, MTIME))
+        res, raw = commit_to_bytes(fs, tmp, "rv1.tar", must_scan=True, engine=eng)
+        _, raw0 = commit_to_bytes(plain, tmp, "rv1p.tar", must_scan=True)
+        assert raw == raw0 and [(n, d) for n, m, d in tar_members(raw) if m.isfile()] == [(rel, new)]
+    print("OK reserved")
+
+
 if __name__ == "__main__":
+    if len(sys.argv) > 3 and sys.argv[3] == "reserved":
+        with M.Engine(n_streams=int(sys.argv[2]), staging_bytes=1 << 20) as eng:
+            scenario_reserved(sys.argv[1], eng)
+        sys.exit(0)
     if len(sys.argv) > 3 and sys.argv[3] == "known_tree":
         with M.Engine(n_streams=int(sys.argv[2]), staging_bytes=1 << 20) as eng:
             scenario_known_tree(sys.argv[1], eng)

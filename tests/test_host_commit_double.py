@@ -128,3 +128,16 @@ def test_an_arena_that_cannot_be_mapped_fails_the_commit_and_nothing_hangs(hip_d
     p = subprocess.run([sys.executable, os.path.join(STUB_DIR, "commit_scenarios.py"), str(tmp_path), "4", "mapper_fails"], env=env,
                        capture_output=True, text=True, timeout=300)
     assert p.returncode == 0 and "OK mapper_fails" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]
+
+
+def test_the_reserved_batch_is_the_one_the_commits_use(hip_double, tmp_path):  # noqa: F811
+    """mi_memfs_reserve_device, two scanning commits, close: ONE arena -- MI_ARENA_TRACE shows one address range reserved and one
+    given back (mi_commit_stats cannot show it: arena_moves is counted from the batch the commit ends up with, and a batch begun
+    in place of the reserved one has not moved either); the tars are the header-only commit's"""
+    env = dict(os.environ, LD_PRELOAD=(os.environ.get("LD_PRELOAD", "") + " " + hip_double).strip(), MI_ARENA_TRACE="1")
+    p = subprocess.run([sys.executable, os.path.join(STUB_DIR, "commit_scenarios.py"), str(tmp_path), "4", "reserved"], env=env,
+                       capture_output=True, text=True, timeout=600)
+    assert p.returncode == 0 and "OK reserved" in p.stdout, p.stdout[-1500:] + p.stderr[-3000:]
+    trace = [ln for ln in p.stderr.splitlines() if ln.startswith("mi_arena: ")]
+    assert len([ln for ln in trace if ln.startswith("mi_arena: reserved")]) == 1, trace
+    assert len([ln for ln in trace if ln.startswith("mi_arena: released")]) == 1, trace

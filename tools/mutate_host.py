@@ -9,8 +9,9 @@ The report lists the survivors with their line; what was made of them is in tool
 
   python tools/mutate_host.py makisu_amd/csrc/mi_tar.hip --tests tests/test_host_tar.py tests/test_host_tar_fuzz.py \
       --n 60 --jobs 4 --seed 1 [--lines 100-300]
-  a header: python tools/mutate_host.py makisu_amd/csrc/mi_memtree.h --unit makisu_amd/csrc/mi_memfs.hip --tests ...
-      (the unit that includes it is compiled from a copy beside the mutated header, so that ITS include finds the mutant)
+  a header: python tools/mutate_host.py makisu_amd/csrc/mi_copyfs.h --unit makisu_amd/csrc/mi_memfs.hip --tests ...
+      (the unit that includes it -- one of mi_memfs.hip, mi_copyops.hip, mi_commit.hip for mi_copyfs.h and what it includes -- is
+      compiled from a copy beside the mutated header, with the other headers, so that every include finds the mutant)
 """
 import argparse
 import os
@@ -92,6 +93,10 @@ def run_mutant(k, args, src_lines, site, objs_other, flags):
     if args.unit:                                              # a header: the including unit, copied beside the mutant
         unit = os.path.join(work, os.path.basename(args.unit))
         shutil.copy(args.unit, unit)
+        src_dir = os.path.dirname(os.path.abspath(args.source))   # ... and the other headers too: one that includes the source
+        for h in os.listdir(src_dir):                              # (mi_copyfs.h -> mi_memtree.h) looks beside ITSELF first
+            if h.endswith(".h") and h != base:
+                shutil.copy(os.path.join(src_dir, h), os.path.join(work, h))
     obj = os.path.join(work, os.path.basename(unit).replace(".hip", ".o"))
     lib = os.path.join(work, "libmakisu_mi.so")
     tag = "%s:%d  [%s]  %s  ->  %s" % (base, ln, name, line.strip()[:110], new_line.strip()[:110])
