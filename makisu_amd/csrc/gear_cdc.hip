@@ -93,11 +93,11 @@ constexpr u32 kNoCand = 0xFFFFFFFFu;
 __device__ __forceinline__ u32 lane_value(u32 v, int src) { return (u32)__builtin_amdgcn_readlane((int)v, src); }
 
 // ---- fast path for cut selection: a tile's candidates as ONE sorted 64-entry list ----------
-// While marking, a lane also packs up to three candidates of its run into one VGPR (10-bit
-// run offsets, count in bits 30..31).  If no lane overflowed and the tile has <= 64
-// candidates (mask 13 bits: ~8 expected), the wave compacts them -- ballot + popcount prefix
-// sums over the 2-bit counts -- into a sorted list in LDS; selection then needs one ballot per
-// cut instead of a bitmap search.  Otherwise the bitmap (exact for any density) is used.
+// While marking, a lane also packs up to six candidates of its run into two VGPRs (three per
+// register: 10-bit run offsets, count in bits 30..31).  If no lane overflowed and the tile has
+// <= 64 candidates (mask 13 bits: ~8 expected), the wave compacts them -- ballot + popcount prefix
+// sums over the three bits of the per-lane count -- into a sorted list in LDS; selection then needs
+// one ballot per cut instead of a bitmap search.  Otherwise the bitmap (exact for any density) is used.
 struct CandPack { u32 a, b; };                           // candidates 0..2 in a, 3..5 in b (10-bit run offsets, count in bits 30..31)
 __device__ __forceinline__ void cand_push(CandPack& pk, bool& ovf, u32 o) {
     const u32 ca = pk.a >> 30;
@@ -306,10 +306,11 @@ __device__ __forceinline__ bool select_tile(const u32* bitmap, const u32* list, 
     return false;
 }
 
-// Slow path of the list construction: a tile whose lanes overflowed their 3 packed candidates
-// (about 6 in 10 000 tiles on random data) still has few candidates in total; rebuild the sorted
-// list from the bitmap -- lane i owns words [32 i, 32 i + 32) = its own 1 KiB run.  False
-// (wave-uniform) when the tile really holds more than 64 candidates.
+// Slow path of the list construction: a tile in which a lane overflowed its 6 packed candidates
+// (seven in one 1 KiB run: about 1 run in 10^10 on random data at the default mask, so only
+// planted content gets here -- tests/test_gpu_gear_planted.py) may still have few candidates in
+// total; rebuild the sorted list from the bitmap -- lane i owns words [32 i, 32 i + 32) = its own
+// 1 KiB run.  False (wave-uniform) when the tile really holds more than 64 candidates.
 __device__ __forceinline__ bool list_from_bitmap(const u32* bitmap, int lane, u32* list) {
     u32 cnt = 0;
 #pragma unroll 4
