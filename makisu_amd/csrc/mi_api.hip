@@ -10,7 +10,9 @@
 //   SHA queue  : q_off[], q_len[] (u64), q_id[] (u32): chunk descriptors, longest first
 //   file out   : roots[] (32 B), file_sha[] (32 B, optional), crc[] (u32, optional)
 // One HIP stream per BATCH for its pipeline (two batches may be in flight), one per ctx for
-// ctx-level work, n_streams copy streams for staging.
+// ctx-level work, n_streams copy streams for staging.  Streams, events and pinned buffers have owners, as device memory
+// has (mi_internal.h): mi_batch_free and mi_ctx_destroy are about state and order, and end in `delete`.
+// mi_batch_read_file and its kin -- staged bytes back through pinned windows -- are mi_readback.hip.
 // There is no CPU fallback anywhere in this file.
 #include "mi_internal.h"
 #include "mi_hostpath.h"      // mi_io
@@ -82,7 +84,7 @@ constexpr size_t kCtlBytes = kCtlRolesOff + 2 * kShaRoleWords * sizeof(u32);
 // buffers go through the ctx's reader threads (mi_stage.hip).
 int staging_sync(mi_batch* b) {
     mi_ctx* c = b->ctx;
-    if (b->ring_stream) HIPCHK(c, hipStreamSynchronize(b->ring_stream));
+    if (b->window.stream) HIPCHK(c, hipStreamSynchronize(b->window.stream));
     if (c->stager) return stager_drain(c->stager, b);
     return MI_OK;
 }
@@ -103,6 +105,7 @@ int staging_sync(mi_batch* b) {
 //    MI_ARENA=malloc (A/B).  told: an eighth on top instead of a half.
 // ahead: the caller is a walk whose enumeration runs ahead of what it hands over (mi_batch_reserve_ahead): told, and piecewise.
 int arena_reserve(mi_batch* b, u64 want, bool told = false, bool ahead = false) {
+    static const bool trace = [] { const char* v = getenv("MI_ARENA_TRACE"); return v && *v == '1'; }();
     mi_ctx* c = b->ctx;
     want += 4096;                                   // slack: tile loads may touch 15 B past a file
     if (want <= b->arena.bytes) return MI_OK;
@@ -118,8 +121,7 @@ int arena_reserve(mi_batch* b, u64 want, bool told = false, bool ahead = false) 
         bool no_addresses = false;
         const int rc = arena_promise(c, &b->arena, want, &no_addresses);
         if (!no_addresses) return rc;
-        static const bool say = [] { const char* v = getenv("MI_ARENA_TRACE"); return v && *v == '1'; }();
-        if (say) fprintf(stderr, "mi_arena: no address range left (%s): this batch's arena is one allocation\n", mi_last_error(c));
+        if (trace) fprintf(stderr, "mi_arena: no address range left (%s): this batch's arena is one allocation\n", mi_last_error(c));
         b->arena_plain = true;
     }
     int rc = staging_sync(b);                       // copies in flight target the old arena
@@ -127,7 +129,6 @@ int arena_reserve(mi_batch* b, u64 want, bool told = false, bool ahead = false) 
     HIPCHK(c, hipStreamSynchronize(c->stream));
     u64 alloc = guard_alloc() ? ((want + 255) & ~255ull) : want + (told ? want / 8 : want / 2);   // under the guard: the 4 KiB and no more
     void* np = nullptr;
-    static const bool trace = [] { const char* v = getenv("MI_ARENA_TRACE"); return v && *v == '1'; }();
     if (trace) fprintf(stderr, "mi_arena: %s %.1f MB -> %.1f MB (used %.1f)\n", told ? "told" : "grow", b->arena.bytes / 1e6, alloc / 1e6, b->arena_used / 1e6);
     hipError_t e = dev_alloc(&np, alloc);
     if (e != hipSuccess) { alloc = want; HIPCHK(c, dev_alloc(&np, alloc)); }
@@ -153,17 +154,6 @@ int arena_reserve(mi_batch* b, u64 want, bool told = false, bool ahead = false) 
 // allocation is what makes a fresh batch expensive: ~3 ms per 8 MiB)
 constexpr u64 kRingBytes = 2ull << 20;
 
-int ensure_ring(mi_batch* b) {
-    mi_ctx* c = b->ctx;
-    if (b->ring[0]) return MI_OK;
-    HIPCHK(c, hipStreamCreateWithFlags(&b->ring_stream, hipStreamNonBlocking));
-    for (int i = 0; i < 2; ++i) {
-        HIPCHK(c, hipHostMalloc(&b->ring[i], kRingBytes, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&b->ring_ev[i], hipEventDisableTiming));
-    }
-    return MI_OK;
-}
-
 int ensure_stager(mi_ctx* c) {
     if (!c->stager) c->stager = stager_create(c, c->stage_threads, c->staging_bytes);
     if (!c->stager_checked) {
@@ -185,64 +175,75 @@ extern "C" void mi_batch_expect_host_bytes(mi_batch* b) {
     if (!c->stager) c->stager = stager_create(c, c->stage_threads, c->staging_bytes);
 }
 
-int staging_flush(mi_batch* b) {
+}  // namespace
+
+int InlineWindow::flush(mi_batch* b) {
     mi_ctx* c = b->ctx;
-    if (b->win_fill == 0) return MI_OK;
+    if (fill == 0) return MI_OK;
     {
-        StageSpan sp{b->win_start, b->win_fill, 0, 0, kStageInlineThread};
-        if (c->verify_staging) stage_sum_host(b->ring[b->cur], b->win_fill, &sp.s1, &sp.s2);
+        StageSpan sp{start, fill, 0, 0, kStageInlineThread};
+        if (c->verify_staging) stage_sum_host(slab[cur].p, fill, &sp.s1, &sp.s2);
         std::lock_guard<std::mutex> g(b->span_mu);
         ++b->stage_stats.spans;
-        b->stage_stats.bytes += b->win_fill;
+        b->stage_stats.bytes += fill;
         if (c->verify_staging) b->stage_spans.push_back(sp);   // summed on the GPU when staging ends
     }
     {
-        const int rc = arena_wait_mapped(c, &b->arena, b->win_start + b->win_fill);
+        const int rc = arena_wait_mapped(c, &b->arena, start + fill);
         if (rc) return rc;
     }
-    HIPCHK(c, hipMemcpyAsync((u8*)b->arena.p + b->win_start, b->ring[b->cur], b->win_fill,
-                             hipMemcpyHostToDevice, b->ring_stream));
-    HIPCHK(c, hipEventRecord(b->ring_ev[b->cur], b->ring_stream));
+    HIPCHK(c, hipMemcpyAsync((u8*)b->arena.p + start, slab[cur].p, fill, hipMemcpyHostToDevice, stream));
+    HIPCHK(c, hipEventRecord(ev[cur], stream));
     b->staged_any = true;
-    b->cur ^= 1;
-    HIPCHK(c, hipEventSynchronize(b->ring_ev[b->cur]));        // the slab we are about to reuse
-    b->win_start += b->win_fill;
-    b->win_fill = 0;
+    cur ^= 1;
+    HIPCHK(c, hipEventSynchronize(ev[cur]));                   // the slab we are about to reuse
+    start += fill;
+    fill = 0;
     return MI_OK;
 }
 
-// Appends `len` bytes of caller memory at arena offset `at` through the batch's pinned window.
-int staging_append(mi_batch* b, u64 at, const u8* src, u64 len) {
-    int rc = ensure_ring(b);
-    if (rc) return rc;
-    if (b->win_fill == 0) b->win_start = at;
-    if (at != b->win_start + b->win_fill) {
+int InlineWindow::append(mi_batch* b, u64 at, const u8* src, u64 len) {
+    mi_ctx* c = b->ctx;
+    int rc = MI_OK;
+    if (!slab[0].p) {
+        InlineWindow w;                     // built here and moved in whole: a failure leaves nothing behind, the next call begins again
+        HIPCHK(c, w.stream.create());
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, w.slab[i].ensure(kRingBytes));
+            HIPCHK(c, w.ev[i].create(hipEventDisableTiming));
+        }
+        *this = std::move(w);
+    }
+    if (fill == 0) start = at;
+    if (at != start + fill) {
         // only alignment padding may be bridged: a larger gap is a file the reader threads are
         // staging, and zero-filling across it would overwrite their bytes
-        const u64 gap = at - (b->win_start + b->win_fill);
-        if (at < b->win_start + b->win_fill || gap >= kFileAlign || b->win_fill + gap > kRingBytes) {
-            rc = staging_flush(b);
+        const u64 gap = at - (start + fill);
+        if (at < start + fill || gap >= kFileAlign || fill + gap > kRingBytes) {
+            rc = flush(b);
             if (rc) return rc;
-            b->win_start = at;
+            start = at;
         } else {
-            memset((u8*)b->ring[b->cur] + b->win_fill, 0, gap);
-            b->win_fill += gap;
+            memset(slab[cur].as<u8>() + fill, 0, gap);
+            fill += gap;
         }
     }
     while (len) {
-        if (b->win_fill == kRingBytes) {
-            rc = staging_flush(b);
+        if (fill == kRingBytes) {
+            rc = flush(b);
             if (rc) return rc;
         }
-        u64 take = kRingBytes - b->win_fill;
+        u64 take = kRingBytes - fill;
         if (take > len) take = len;
-        memcpy((u8*)b->ring[b->cur] + b->win_fill, src, take);
+        memcpy(slab[cur].as<u8>() + fill, src, take);
         src += take;
-        b->win_fill += take;
+        fill += take;
         len -= take;
     }
     return MI_OK;
 }
+
+namespace {
 
 int batch_add_common(mi_batch* b, u64 len, u64 tag, u64* at, u64 origin = 0) {
     if (!b) return MI_ERR_INVALID;
@@ -396,7 +397,7 @@ int submit_pipeline_enqueue(mi_batch* b) {
     b->stats.n_files = nf;
     b->stats.ms_h2d = b->ms_h2d;
     b->n_chunks = 0;
-    b->h_counts[0] = b->h_counts[1] = 0;
+    b->h_counts.as<u64>()[0] = b->h_counts.as<u64>()[1] = 0;
     if (nf == 0) return MI_OK;
     if (nf >= 0x7FFFFFFFull) return fail(c, MI_ERR_INVALID, "too many files in one batch");
     for (const PartRec& p : b->parts)
@@ -558,7 +559,7 @@ int submit_pipeline_enqueue(mi_batch* b) {
     } else {
         HIPCHK(c, hipMemsetAsync(b->dup_of.p, 0xFF, cap * 8, s));
     }
-    HIPCHK(c, hipMemcpyAsync(&b->h_counts[0], ctl, 16, hipMemcpyDeviceToHost, s));   // {total, n_unique}
+    HIPCHK(c, hipMemcpyAsync(b->h_counts.p, ctl, 16, hipMemcpyDeviceToHost, s));   // {total, n_unique}
     HIPCHK(c, hipEventRecord(b->ev[5], s));
     HIPCHK(c, hipGetLastError());
     if ((c->cfg.flags & MI_FLAG_FILE_SHA256) && !b->fsha_host.empty()) {
@@ -588,13 +589,13 @@ int wait_pipeline(mi_batch* b) {
         const int rc = stager_hash_wait(c, l);
         if (rc) return rc;
     }
-    const u64 total = b->h_counts[0];
+    const u64 total = b->h_counts.as<u64>()[0];
     if (total > b->total_slots)
         return fail(c, MI_ERR_HIP, "chunk count %llu exceeds its bound %llu",
                     (unsigned long long)total, (unsigned long long)b->total_slots);
     b->n_chunks = total;
     b->stats.n_chunks = total;
-    b->stats.n_unique = (c->cfg.flags & MI_FLAG_NO_DEDUP) ? total : b->h_counts[1];
+    b->stats.n_unique = (c->cfg.flags & MI_FLAG_NO_DEDUP) ? total : b->h_counts.as<u64>()[1];
     if (!b->files.empty()) {
         b->stats.ms_cdc = ev_ms(b->ev[0], b->ev[1]);
         b->stats.ms_sort = ev_ms(b->ev[1], b->ev[2]);
@@ -619,33 +620,19 @@ int fetch_results(mi_batch* b) {
         // the file rows are packed by a kernel too: one copy behind the chunk rows' (same stream, one wait for both) instead
         // of three to five synchronous column copies and a repacking loop on the host
         static_assert(sizeof(mi_file_result) == 96, "pack_file_rows_kernel writes 96-byte rows");
-        if (nf > b->h_files_cap) {
-            if (b->h_files) (void)hipHostFree(b->h_files);
-            b->h_files = nullptr;
-            b->h_files_cap = 0;
-            const size_t want = nf + nf / 8 + 16;
-            HIPCHK(c, hipHostMalloc((void**)&b->h_files, want * sizeof(mi_file_result), hipHostMallocDefault));
-            b->h_files_cap = want;
-        }
+        if (nf * sizeof(mi_file_result) > b->h_files.bytes) HIPCHK(c, b->h_files.ensure((nf + nf / 8 + 16) * sizeof(mi_file_result)));
         HIPCHK(c, b->file_rows_d.ensure(nf * sizeof(mi_file_result)));
         launch_pack_file_rows(nf, b->file_size.as<u64>(), b->first.as<u64>(), b->n_chunks_d.as<u32>(),
                               (c->cfg.flags & MI_FLAG_FILE_CRC32) ? b->crc_d.as<u32>() : nullptr, b->roots.as<u8>(),
                               (c->cfg.flags & MI_FLAG_FILE_SHA256) ? b->file_sha.as<u8>() : nullptr, b->file_rows_d.p, b->stream);
-        HIPCHK(c, hipMemcpyAsync(b->h_files, b->file_rows_d.p, nf * sizeof(mi_file_result), hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(c, hipMemcpyAsync(b->h_files.p, b->file_rows_d.p, nf * sizeof(mi_file_result), hipMemcpyDeviceToHost, b->stream));
     }
     if (nc) {
         // rows are packed by a kernel; ONE device-to-host copy into the batch's pinned buffer
         static_assert(sizeof(mi_chunk_result) == 64, "pack_chunk_rows_kernel writes 64-byte rows");
         const size_t bytes = nc * sizeof(mi_chunk_result);
         HIPCHK(c, b->rows_d.ensure(bytes));
-        if (bytes > b->rows_h_bytes) {
-            if (b->rows_h) (void)hipHostFree(b->rows_h);
-            b->rows_h = nullptr;
-            b->rows_h_bytes = 0;
-            const size_t want = bytes + bytes / 8;
-            HIPCHK(c, hipHostMalloc(&b->rows_h, want, hipHostMallocDefault));
-            b->rows_h_bytes = want;
-        }
+        if (bytes > b->rows_h.bytes) HIPCHK(c, b->rows_h.ensure(bytes + bytes / 8));
         const u64* d_base = nullptr;
         if (!b->parts.empty()) {                         // parts report offsets inside the whole file
             std::vector<u64> base(nf, 0);
@@ -656,7 +643,7 @@ int fetch_results(mi_batch* b) {
         }
         launch_pack_chunk_rows(nc, b->chunk_file.as<u32>(), b->chunk_start.as<u64>(), b->chunk_len.as<u64>(),
                                b->dup_of.as<i64>(), b->digests.as<u8>(), d_base, b->rows_d.p, b->stream);
-        HIPCHK(c, hipMemcpyAsync(b->rows_h, b->rows_d.p, bytes, hipMemcpyDeviceToHost, b->stream));
+        HIPCHK(c, hipMemcpyAsync(b->rows_h.p, b->rows_d.p, bytes, hipMemcpyDeviceToHost, b->stream));
     }
     if (nf || nc) {
         HIPCHK(c, hipStreamSynchronize(b->stream));
@@ -664,9 +651,9 @@ int fetch_results(mi_batch* b) {
     }
     if ((c->cfg.flags & MI_FLAG_FILE_SHA256) && b->fsha_host_out.size() == b->fsha_host.size() * 32)
         for (size_t i = 0; i < b->fsha_host.size(); ++i)   // the long files' digests come from the host side of the pass
-            memcpy(b->h_files[b->fsha_host[i]].file_sha256, b->fsha_host_out.data() + 32 * i, 32);
+            memcpy(b->h_files.as<mi_file_result>()[b->fsha_host[i]].file_sha256, b->fsha_host_out.data() + 32 * i, 32);
     for (u64 f = 0; f < nf; ++f) {                      // what only the host knows: the caller's tag; a part's own range
-        mi_file_result& r = b->h_files[f];
+        mi_file_result& r = b->h_files.as<mi_file_result>()[f];
         r.user_tag = b->files[f].tag;
         if (b->files[f].part >= 0) {                    // a part: its own range; no whole-file values
             const PartRec& p = b->parts[b->files[f].part];
@@ -761,15 +748,10 @@ int mi_ctx_create(const mi_config* cfg, mi_ctx** out) {
         mi_ctx_destroy(c);
         return rc;
     }
-    // Plain creation on purpose: a stream made with hipStreamCreateWithPriority -- even at the
-    // default priority -- changes how the runtime spreads the later (batch) streams over the
-    // hardware queues, and the batches in flight stop overlapping (measured: 6.2 vs 5.87 ms
-    // per C2 step under the ROCm 7.0 runtime PyTorch bundles).
-    CREATE_CHK(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-    CREATE_CHK(hipHostMalloc((void**)&c->h_word, 64, hipHostMallocDefault));
-    for (auto& e : c->ev) e = nullptr;
-    for (auto& e : c->ev) CREATE_CHK(hipEventCreate(&e));
-    CREATE_CHK(hipEventCreateWithFlags(&c->sha_done, hipEventDisableTiming));
+    CREATE_CHK(c->stream.create());
+    CREATE_CHK(c->h_word.ensure(64));
+    for (auto& e : c->ev) CREATE_CHK(e.create());
+    CREATE_CHK(c->sha_done.create(hipEventDisableTiming));
     if (const char* e = getenv("MI_SHA_SERIALIZE")) c->serialize_sha = atoi(e) != 0;
     // host-fed staging (mi_stage.hip): slab bytes and reader threads; both lazily allocated
     c->staging_bytes = cfg->staging_bytes ? cfg->staging_bytes : (8ull << 20);
@@ -880,10 +862,6 @@ int mi_ctx_destroy(mi_ctx* c) {
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     stager_destroy(c->stager);
     c->stager = nullptr;
-    for (auto e : c->ev) if (e) (void)hipEventDestroy(e);
-    if (c->sha_done) (void)hipEventDestroy(c->sha_done);
-    if (c->h_word) (void)hipHostFree(c->h_word);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
     delete c;
     return MI_OK;
 }
@@ -926,9 +904,9 @@ int mi_batch_begin(mi_ctx* c, uint64_t n_files_hint, uint64_t bytes_hint, mi_bat
     b->ctx = c;
     b->files.reserve(n_files_hint);
     b->keep_sums = c->file_sums;
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    for (auto& ev : b->ev) if (e == hipSuccess) e = hipEventCreate(&ev);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&b->h_counts, 16, hipHostMallocDefault);
+    hipError_t e = b->stream.create();
+    for (auto& ev : b->ev) if (e == hipSuccess) e = ev.create();
+    if (e == hipSuccess) e = b->h_counts.ensure(16);
     ++c->live_children;                                 // mi_batch_free undoes it (error paths included)
     if (e != hipSuccess) {
         int rc = fail(c, MI_ERR_HIP, "mi_batch_begin: %s", hipGetErrorString(e));
@@ -959,7 +937,7 @@ int mi_batch_add_bytes(mi_batch* b, const void* data, uint64_t len, uint64_t use
     mi_sum::FileSum* sums = b->files.back().sums;
     if (len < kInlineBytes) {
         if (sums) mi_sum::row_add(data, len, 0, sums);           // (the caller's buffer: where these bytes were last known good)
-        rc = staging_append(b, at, (const u8*)data, len);
+        rc = b->window.append(b, at, (const u8*)data, len);
     } else {
         rc = ensure_stager(c);
         if (!rc) rc = stager_put_bytes(c->stager, b, at, data, len, sums);   // returns when `data` has been consumed
@@ -1029,7 +1007,7 @@ int mi_batch_add_paths(mi_batch* b, uint64_t n, const char* const* paths, const 
     if (b->staged) return fail(c, MI_ERR_STATE, "batch already ran; begin a new batch");
     for (u64 i = 0; i < n; ++i)
         if (!paths[i]) return fail(c, MI_ERR_INVALID, "mi_batch_add_paths: path %llu is NULL", (unsigned long long)i);
-    int rc = staging_flush(b);                    // the inline window may hold bytes of earlier small adds
+    int rc = b->window.flush(b);                    // the inline window may hold bytes of earlier small adds
     if (rc) return rc;
     const auto t0 = std::chrono::steady_clock::now();
     // one reservation for all of them (arena_reserve may move the arena: nothing may be in flight into it)
@@ -1065,7 +1043,7 @@ extern "C" int mi_batch_add_block(mi_batch* b, const void* src, uint64_t len, vo
     mi_ctx* c = b->ctx;
     HIPCHK(c, hipSetDevice(c->device));
     if (b->staged) return fail(c, MI_ERR_STATE, "batch already ran; begin a new batch");
-    int rc = staging_flush(b);                    // the inline window may hold bytes of earlier small adds
+    int rc = b->window.flush(b);                    // the inline window may hold bytes of earlier small adds
     if (rc) return rc;
     const u64 at = align_up(b->arena_used, kFileAlign);
     rc = arena_reserve(b, at + align_up(len, kFileAlign));
@@ -1145,7 +1123,7 @@ int mi_batch_add_synthetic(mi_batch* b, uint64_t n_files, const uint64_t* sizes,
     HIPCHK(c, hipSetDevice(c->device));
     if (b->staged) return fail(c, MI_ERR_STATE, "batch already ran; begin a new batch");
     // synthetic files are generated on the device at run time; flush any host window first
-    int rc = staging_flush(b);
+    int rc = b->window.flush(b);
     if (rc) return rc;
     SynthSpec sp;
     sp.f0 = b->files.size();
@@ -1301,7 +1279,7 @@ static int stage_batch(mi_batch* b) {
     mi_ctx* c = b->ctx;
     if (b->staged) return MI_OK;
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = staging_flush(b);
+    int rc = b->window.flush(b);
     if (rc) return rc;
     rc = staging_sync(b);                       // everything the reader threads hold has landed
     if (rc) return rc;
@@ -1451,28 +1429,29 @@ int mi_batch_wait(mi_batch* b) {
     return wait_pipeline(b);
 }
 
+static int submit_and_wait(mi_batch* b) {
+    int rc = mi_batch_submit(b);
+    if (rc) { b->in_flight = false; return rc; }
+    return mi_batch_wait(b);
+}
+
 int mi_batch_run(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
     if (b->group) return group_run(b);
     if (b->ran || b->in_flight)
         return fail(b->ctx, MI_ERR_STATE, "batch already ran; use mi_batch_rerun");
-    int rc = mi_batch_submit(b);
-    if (rc) { b->in_flight = false; return rc; }
-    return mi_batch_wait(b);
+    return submit_and_wait(b);
 }
 
 int mi_batch_rerun(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
     if (!b->ran) return fail(b->ctx, MI_ERR_STATE, "mi_batch_rerun before mi_batch_run");
-    int rc = mi_batch_submit(b);
-    if (rc) { b->in_flight = false; return rc; }
-    return mi_batch_wait(b);
+    return submit_and_wait(b);
 }
 
 // Empties the batch for the next set of files; every device allocation (arena, tables) and the
 // pinned window stay, so a host that scans layer after layer pays hipMalloc -- and the driver's
 // clearing of fresh VRAM, which competes with the H2D copies for the SDMA engines -- once.
-static void read_windows_drop(mi_batch* b);
 int mi_batch_reset(mi_batch* b) {
     if (!b) return MI_ERR_INVALID;
     if (b->group) return group_reset(b);
@@ -1497,13 +1476,12 @@ int mi_batch_reset(mi_batch* b) {
     b->parts.clear();
     b->cuts_ready = b->parts_dirty = false;
     b->total_bytes = b->arena_used = 0;
-    b->cur = 0;
-    b->win_start = b->win_fill = 0;
+    b->window.reset();
     b->staged_any = false;
     b->ms_h2d = 0;
     b->staged = b->ran = b->results_valid = false;
     b->h_roots_valid = false;
-    read_windows_drop(b);                               // the windows held bytes of the old arena contents
+    b->readback.drop();                                 // the windows held bytes of the old arena contents
     b->stage_unordered = false;
     b->n_chunks = b->total_slots = 0;
     b->n_h_files = 0;
@@ -1541,7 +1519,7 @@ int mi_batch_files(mi_batch* b, mi_file_result* out, uint64_t cap) {
     if (cap < b->n_h_files)
         return fail(b->ctx, MI_ERR_CAPACITY, "file result buffer holds %llu rows, need %zu",
                     (unsigned long long)cap, b->n_h_files);
-    if (b->n_h_files) memcpy(out, b->h_files, b->n_h_files * sizeof(mi_file_result));
+    if (b->n_h_files) memcpy(out, b->h_files.p, b->n_h_files * sizeof(mi_file_result));
     return MI_OK;
 }
 
@@ -1550,7 +1528,7 @@ int mi_batch_files_view(mi_batch* b, const mi_file_result** rows, uint64_t* n_fi
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
     int rc = fetch_results(b);
     if (rc) return rc;
-    *rows = b->n_h_files ? b->h_files : nullptr;
+    *rows = b->n_h_files ? b->h_files.as<mi_file_result>() : nullptr;
     if (n_files) *n_files = b->n_h_files;
     return MI_OK;
 }
@@ -1563,7 +1541,7 @@ int mi_batch_chunks(mi_batch* b, mi_chunk_result* out, uint64_t cap) {
     if (cap < b->n_chunks)
         return fail(b->ctx, MI_ERR_CAPACITY, "chunk result buffer holds %llu rows, need %llu",
                     (unsigned long long)cap, (unsigned long long)b->n_chunks);
-    if (b->n_chunks) memcpy(out, b->rows_h, b->n_chunks * sizeof(mi_chunk_result));
+    if (b->n_chunks) memcpy(out, b->rows_h.p, b->n_chunks * sizeof(mi_chunk_result));
     return MI_OK;
 }
 
@@ -1572,7 +1550,7 @@ int mi_batch_chunks_view(mi_batch* b, const mi_chunk_result** rows, uint64_t* n_
     HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
     int rc = fetch_results(b);
     if (rc) return rc;
-    *rows = b->n_chunks ? (const mi_chunk_result*)b->rows_h : nullptr;
+    *rows = b->n_chunks ? b->rows_h.as<mi_chunk_result>() : nullptr;
     if (n_chunks) *n_chunks = b->n_chunks;
     return MI_OK;
 }
@@ -1626,239 +1604,6 @@ int mi_batch_roots(mi_batch* b, uint8_t* out, uint64_t cap) {
     return MI_OK;
 }
 
-// Bytes [offset, offset + len) of file `file_index` as they lie in HBM, through pinned windows: a copy brings more than was
-// asked for (files that were staged together lie together; a layer's files are asked for in nearly that order); its length
-// doubles while reads continue where the last window ended -- 256 KiB when a layer picks single files out of a tree, 8 MiB when
-// it streams -- and a reader that streams finds the NEXT range already on its way into the second window: the copy of one
-// overlaps the consumption of the other (round 6: with one window every 1 MiB the tar writer asked for was a copy of 1 MiB it
-// waited for -- 6 192 of them for 48 x 128 MiB -- and while eight reader threads kept PCIe busy each wait was long enough to
-// leave the layer's SHA-256 thread without work: 0.03-0.11 s of a 2.7 s commit, profiles/r06_commit_large_before.txt).
-constexpr u64 kReadWinBytes = 8ull << 20, kReadWinMin = 256ull << 10;
-static int read_windows(mi_batch* b) {
-    mi_ctx* c = b->ctx;
-    if (b->rb[0].p) return MI_OK;
-    HIPCHK(c, hipStreamCreateWithFlags(&b->rb_stream, hipStreamNonBlocking));
-    for (auto& w : b->rb) {
-        HIPCHK(c, hipHostMalloc(&w.p, kReadWinBytes, hipHostMallocDefault));
-        HIPCHK(c, hipEventCreateWithFlags(&w.ev, hipEventDisableTiming));
-        w.len = 0;
-        w.pending = false;
-    }
-    b->rb_next = kReadWinMin;
-    return MI_OK;
-}
-// a copy into a window has completed.  MI_STAGE_FAULT=readback:N[:K] (tests): the N-th .. N+K-1-th arrive with a byte flipped
-static void window_arrived(mi_batch* b, void* p, u64 len) {
-    mi_ctx* c = b->ctx;
-    const long long k = (long long)b->rb_copies++;
-    if (c->fault_readback >= 0 && k >= c->fault_readback && k < c->fault_readback + c->fault_readback_n && len) ((u8*)p)[len / 2] ^= 0x20;
-}
-// nothing of the windows is valid any more (the arena's contents changed); a copy under way is waited for
-static void read_windows_drop(mi_batch* b) {
-    for (auto& w : b->rb) {
-        if (w.pending) (void)hipEventSynchronize(w.ev);
-        w.pending = false;
-        w.len = 0;
-    }
-    b->rb_next = kReadWinMin;
-}
-// Bytes [at, at + len) of the arena, which lie in row f, through the windows.
-// while_staging: the caller is the pipelined commit (mi_commit.hip) -- the batch is still being staged and scanned by another
-// thread; the file's bytes are waited for (stager_wait_landed), nothing else of the batch's state is touched
-static int read_arena(mi_batch* b, const mi_batch::FileRec& f, u64 at, void* dst, u64 len, bool while_staging) {
-    mi_ctx* c = b->ctx;
-    if (!len) return MI_OK;
-    HIPCHK(c, hipSetDevice(c->device));
-    {
-        const int rc = read_windows(b);
-        if (rc) return rc;
-    }
-    const bool staging = while_staging && c->stager;
-    // the range behind `from` on its way into window `w` (not waited for): as far as the batch's bytes have landed
-    auto prefetch = [&](mi_batch::ReadWin& w, u64 from) -> int {
-        w.len = 0;
-        if (from >= b->arena_used) return MI_OK;
-        u64 want = std::min(b->rb_next, b->arena_used - from);
-        if (staging) {
-            const u64 landed = stager_landed(c->stager, b);
-            if (landed != ~0ull) {
-                if (landed <= from) return MI_OK;
-                want = std::min(want, landed - from);
-            }
-        }
-        HIPCHK(c, hipMemcpyAsync(w.p, b->arena.as<u8>() + from, want, hipMemcpyDeviceToHost, b->rb_stream));
-        HIPCHK(c, hipEventRecord(w.ev, b->rb_stream));
-        w.start = from;
-        w.len = want;
-        w.pending = true;
-        ++b->rb_fetches;
-        b->rb_bytes += want;
-        return MI_OK;
-    };
-    u8* d = (u8*)dst;
-    while (len) {
-        mi_batch::ReadWin* w = &b->rb[b->rb_cur];
-        if (!(w->len && at >= w->start && at < w->start + w->len)) {
-            mi_batch::ReadWin* nx = &b->rb[b->rb_cur ^ 1];
-            const bool follows = w->len && at == w->start + w->len;     // the reader continues where the window ended: it streams
-            if (nx->len && at >= nx->start && at < nx->start + nx->len) {
-                if (nx->pending) {
-                    const auto tf = std::chrono::steady_clock::now();
-                    HIPCHK(c, hipEventSynchronize(nx->ev));
-                    b->rb_fetch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count();
-                    nx->pending = false;
-                    window_arrived(b, nx->p, nx->len);
-                }
-                b->rb_cur ^= 1;
-                if (follows) b->rb_next = std::min(b->rb_next * 2, kReadWinBytes);
-                const int rc = prefetch(*w, nx->start + nx->len);        // the window just left takes what follows the new one
-                if (rc) return rc;
-                continue;
-            }
-            if (nx->pending) { HIPCHK(c, hipEventSynchronize(nx->ev)); nx->pending = false; }
-            nx->len = 0;
-            b->rb_next = follows ? std::min(b->rb_next * 2, kReadWinBytes) : kReadWinMin;
-            u64 want = std::max(b->rb_next, std::min(len, kReadWinBytes));
-            want = std::min(want, b->arena_used - at);
-            if (staging) {
-                // what was asked for is waited for; the window then takes what ELSE has landed behind it (the neighbours that
-                // will be asked for next) and nothing that is still on its way
-                const u64 need = std::min(len, std::min(kReadWinBytes, f.off + f.size - at));
-                u64 landed = ~0ull;
-                const auto tw = std::chrono::steady_clock::now();
-                const int rc = stager_wait_landed(c->stager, b, at + need, &landed);
-                b->rb_wait_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tw).count();
-                if (rc) return rc;
-                if (landed != ~0ull) want = std::min(want, std::max(need, landed > at ? landed - at : 0));
-            }
-            const auto tf = std::chrono::steady_clock::now();
-            HIPCHK(c, hipMemcpyAsync(w->p, b->arena.as<u8>() + at, want, hipMemcpyDeviceToHost, b->rb_stream));
-            HIPCHK(c, hipStreamSynchronize(b->rb_stream));
-            b->rb_fetch_s += std::chrono::duration<double>(std::chrono::steady_clock::now() - tf).count();
-            window_arrived(b, w->p, want);
-            w->start = at;
-            w->len = want;
-            w->pending = false;
-            ++b->rb_fetches;
-            b->rb_bytes += want;
-            if (follows || want < len) {                                 // streaming (or a read longer than a window): the next range
-                const int rc = prefetch(*nx, at + want);                 // sets out while this one is consumed
-                if (rc) return rc;
-            }
-        }
-        const u64 take = std::min(len, w->start + w->len - at);
-        memcpy(d, (const u8*)w->p + (at - w->start), take);
-        d += take;
-        at += take;
-        len -= take;
-    }
-    return MI_OK;
-}
-// what every read of a row begins with; *f: the row
-static int read_row(mi_batch* b, uint64_t file_index, bool while_staging, const mi_batch::FileRec** f) {
-    mi_ctx* c = b->ctx;
-    if (!while_staging && (!b->staged || b->in_flight))
-        return fail(c, MI_ERR_STATE, "mi_batch_read_file: the batch is not staged, or in flight");
-    if (file_index >= b->files.size()) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: no file %llu", (unsigned long long)file_index);
-    *f = &b->files[file_index];
-    return MI_OK;
-}
-static int read_file_impl(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, bool while_staging) {
-    if (!b || (!dst && len)) return MI_ERR_INVALID;
-    if (b->group) return group_read_file(b, file_index, offset, dst, len, while_staging);
-    mi_ctx* c = b->ctx;
-    const mi_batch::FileRec* f = nullptr;
-    const int rc = read_row(b, file_index, while_staging, &f);
-    if (rc) return rc;
-    if (f->part >= 0) return fail(c, MI_ERR_INVALID, "mi_batch_read_file: file %llu is a part", (unsigned long long)file_index);
-    if (offset > f->size || len > f->size - offset)
-        return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside file %llu of %llu bytes", (unsigned long long)offset,
-                    (unsigned long long)len, (unsigned long long)file_index, (unsigned long long)f->size);
-    return read_arena(b, *f, f->off + offset, dst, len, while_staging);
-}
-// (mi_internal.h) the row is a PART and `offset` a FILE offset inside the part's own range [begin, end): a split file of a batch group
-int mi_batch_read_part(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len, int while_staging) {
-    if (!b || (!dst && len)) return MI_ERR_INVALID;
-    mi_ctx* c = b->ctx;
-    const mi_batch::FileRec* f = nullptr;
-    const int rc = read_row(b, file_index, while_staging, &f);
-    if (rc) return rc;
-    if (f->part < 0) return fail(c, MI_ERR_INVALID, "file %llu is not a part", (unsigned long long)file_index);
-    const PartRec& pr = b->parts[f->part];
-    if (offset < pr.begin || offset > pr.end || len > pr.end - offset)
-        return fail(c, MI_ERR_INVALID, "mi_batch_read_file: [%llu, +%llu) is outside the part [%llu, %llu)", (unsigned long long)offset,
-                    (unsigned long long)len, (unsigned long long)pr.begin, (unsigned long long)pr.end);
-    return read_arena(b, *f, f->off + (offset - f->origin), dst, len, while_staging);     // (the staged range begins at file offset `origin`)
-}
-int mi_batch_read_file(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len) {
-    return read_file_impl(b, file_index, offset, dst, len, false);
-}
-int mi_batch_read_file_landed(mi_batch* b, uint64_t file_index, uint64_t offset, void* dst, uint64_t len) {   // (hidden: mi_local.h)
-    return read_file_impl(b, file_index, offset, dst, len, true);
-}
-
-void mi_batch_read_stats(mi_batch* b, double* wait_s, double* fetch_s, uint64_t* fetches, uint64_t* bytes) {
-    if (b && b->group) return group_read_stats(b, wait_s, fetch_s, fetches, bytes);
-    if (wait_s) *wait_s = b ? b->rb_wait_s : 0;
-    if (fetch_s) *fetch_s = b ? b->rb_fetch_s : 0;
-    if (fetches) *fetches = b ? b->rb_fetches : 0;
-    if (bytes) *bytes = b ? b->rb_bytes : 0;
-}
-// the layer writer's check (mi_layer.hip): the sums of chunk k (1 MiB of the FILE) of a row as they were taken where the bytes were
-// read; *has = 0: the batch keeps none for this row.  A split file's chunk lies in the own range of exactly one part (parts begin
-// on MiB boundaries of the file).
-int mi_batch_chunk_sum(mi_batch* b, uint64_t file_index, uint64_t k, uint64_t* sum_a, uint64_t* sum_b, int* has) {
-    if (!b || !has) return MI_ERR_INVALID;
-    *has = 0;
-    if (b->group) return group_chunk_sum(b, file_index, k, sum_a, sum_b, has);
-    if (file_index >= b->files.size()) return MI_ERR_INVALID;
-    const mi_batch::FileRec& f = b->files[file_index];
-    if (!f.sums) return MI_OK;
-    const u64 k0 = f.origin / mi_sum::kChunk;
-    if (k < k0 || k - k0 >= mi_sum::chunks_of(f.origin % mi_sum::kChunk + f.size)) return MI_ERR_INVALID;
-    *has = 1;
-    if (sum_a) *sum_a = f.sums[k - k0].a.load(std::memory_order_relaxed);
-    if (sum_b) *sum_b = f.sums[k - k0].b.load(std::memory_order_relaxed);
-    return MI_OK;
-}
-// the read-back windows (two pinned 8 MiB buffers, a stream, two events) ahead of the first read: mi_memfs_reserve_device
-int mi_batch_prepare_read(mi_batch* b) {
-    if (!b) return MI_ERR_INVALID;
-    if (b->group) return group_prepare_read(b);
-    HIPCHK(b->ctx, hipSetDevice(b->ctx->device));
-    return read_windows(b);
-}
-void mi_batch_drop_windows(mi_batch* b) {
-    if (b && b->group) return group_drop_windows(b);
-    if (b) read_windows_drop(b);
-}
-// A chunk that came back from HBM with other sums than it went with, twice: WHICH hop?  The chunk once more, by a plain copy
-// into memory of this call's own (not the windows, not their stream): the same sums as at the source -- HBM holds the right
-// bytes and the read-back windows delivered others; other sums -- the arena does not hold what the file had when it was read.
-int mi_batch_explain_chunk(mi_batch* b, uint64_t file_index, uint64_t chunk, char* msg, uint64_t cap) {
-    if (b && b->group) return group_explain_chunk(b, file_index, chunk, msg, cap);
-    if (!b || !msg || !cap || file_index >= b->files.size()) return MI_ERR_INVALID;
-    mi_ctx* c = b->ctx;
-    const mi_batch::FileRec& f = b->files[file_index];
-    const u64 off = chunk * mi_sum::kChunk;                             // in the FILE; the row's bytes begin at f.origin
-    const u64 k0 = f.origin / mi_sum::kChunk;
-    if (!f.sums || off < f.origin - f.origin % mi_sum::kChunk || off >= f.origin + f.size) return MI_ERR_INVALID;
-    const u64 from = off > f.origin ? off : f.origin;                   // (a part's first chunk may begin before its staged bytes)
-    const u64 len = std::min(off + mi_sum::kChunk, f.origin + f.size) - from;
-    std::vector<u8> again(len);
-    (void)hipSetDevice(c->device);
-    const hipError_t e = hipMemcpy(again.data(), b->arena.as<u8>() + f.off + (from - f.origin), len, hipMemcpyDeviceToHost);
-    u64 a = 0, bb = 0;
-    if (e == hipSuccess) mi_sum::chunk_add(again.data(), (size_t)len, (size_t)(from - off), &a, &bb);
-    const u64 wa = f.sums[chunk - k0].a.load(), wb = f.sums[chunk - k0].b.load();
-    snprintf(msg, (size_t)cap, "arena [%llu, +%llu) (file %llu, bytes [%llu, +%llu)): sums where the bytes were read %016llx/%016llx; %s",
-             (unsigned long long)(f.off + (from - f.origin)), (unsigned long long)len, (unsigned long long)file_index, (unsigned long long)from, (unsigned long long)len,
-             (unsigned long long)wa, (unsigned long long)wb,
-             e != hipSuccess ? "a third copy failed" :
-             a == wa && bb == wb ? "a plain copy out of HBM has them: the arena holds the file's bytes, the hop HBM -> pinned read-back window delivered others, twice"
-                                 : "a plain copy out of HBM has others too: the arena does not hold what the file held when it was read (the hop pinned slab -> HBM, or HBM itself)");
-    return MI_OK;
-}
 int mi_batch_file_size(mi_batch* b, uint64_t file_index, uint64_t* size) {       // (internal: mi_layer.hip)
     if (b && b->group) return group_file_size(b, file_index, size);
     if (!b || !size || file_index >= b->files.size() || b->files[file_index].part >= 0) return MI_ERR_INVALID;
@@ -1906,26 +1651,12 @@ int mi_batch_free(mi_batch* b) {
     }
     (void)staging_sync(b);                      // reader threads may still hold pieces of this batch
     if (b->fsha_latch) { (void)stager_hash_wait(c, b->fsha_latch); b->fsha_latch = nullptr; }
-    for (int i = 0; i < 2; ++i) {
-        if (b->ring_ev[i]) (void)hipEventDestroy(b->ring_ev[i]);
-        if (b->ring[i]) (void)hipHostFree(b->ring[i]);
-    }
-    if (b->ring_stream) (void)hipStreamDestroy(b->ring_stream);
     (void)hipStreamSynchronize(c->stream);
     --c->live_children;
-    if (b->stream) { (void)hipStreamSynchronize(b->stream); (void)hipStreamDestroy(b->stream); }
-    for (auto e : b->ev) if (e) (void)hipEventDestroy(e);
-    if (b->h_counts) (void)hipHostFree(b->h_counts);
-    if (b->rows_h) (void)hipHostFree(b->rows_h);
-    read_windows_drop(b);
-    if (b->rb_stream) { (void)hipStreamSynchronize(b->rb_stream); (void)hipStreamDestroy(b->rb_stream); }   // (before its events go)
-    for (auto& w : b->rb) {
-        if (w.p) (void)hipHostFree(w.p);
-        if (w.ev) (void)hipEventDestroy(w.ev);
-    }
-    if (b->h_files) (void)hipHostFree(b->h_files);
+    if (b->stream) (void)hipStreamSynchronize(b->stream);
+    b->readback.drop();                         // a copy into a window reads the arena: over before the arena goes
     arena_release(&b->arena);
-    delete b;
+    delete b;                                   // (everything the batch owns goes with it: mi_internal.h)
     return MI_OK;
 }
 
@@ -1953,7 +1684,7 @@ int mi_context_checksum(mi_batch* b, const void* prefix, uint64_t prefix_len,
             if ((u64)e.file_index >= b->n_h_files)
                 return fail(c, MI_ERR_INVALID, "entry %llu: file index %lld out of range",
                             (unsigned long long)i, (long long)e.file_index);
-            const mi_file_result& fr = b->h_files[(size_t)e.file_index];
+            const mi_file_result& fr = b->h_files.as<mi_file_result>()[(size_t)e.file_index];
             crc = crc32_host_combine(crc, fr.crc32, fr.size);
         }
     }
@@ -1974,10 +1705,10 @@ int mi_dedup_mark(mi_ctx* c, const void* d_digests, uint64_t n, void* d_dup_of, 
     launch_dedup_mark((const u8*)d_digests, n, nullptr, c->dd_table.as<u32>(), c->dd_slot.as<u32>(), cap,
                       (i64*)d_dup_of, c->dd_nuniq.as<u64>(), true, c->stream);
     HIPCHK(c, hipEventRecord(c->ev[1], c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->h_word, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_word.p, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    const u64 nu = *c->h_word;
+    const u64 nu = *c->h_word.as<u64>();
     c->stats.ms_dedup = ev_ms(c->ev[0], c->ev[1]);
     c->stats.n_unique = nu;
     if (n_unique) *n_unique = nu;
@@ -2009,10 +1740,10 @@ int mi_dedup_mark_range(mi_ctx* c, const void* d_digests, uint64_t n_total, uint
                         uint64_t own_n, void* d_dup_of_own, uint64_t* n_own_first) {
     int rc = mi_dedup_mark_range_enqueue(c, d_digests, n_total, own_first, own_n, d_dup_of_own);
     if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->h_word, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_word.p, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    const u64 nf = *c->h_word;
+    const u64 nf = *c->h_word.as<u64>();
     c->stats.ms_dedup = ev_ms(c->ev[0], c->ev[1]);
     if (n_own_first) *n_own_first = nf;
     return MI_OK;

@@ -78,7 +78,8 @@ struct ArenaVm {
     int err = MI_OK;
     std::string err_msg;
     std::thread th;
-    hipStream_t fill_stream = nullptr;
+    Stream fill_stream;
+    MI_LOCAL ~ArenaVm() = default;                             // (hidden, like the owner type it holds)
 
     hipError_t map_at(void* base, u64 at, const Piece& pc) {
         hipError_t e = hipMemMap((u8*)base + at, pc.bytes, 0, pc.h, 0);
@@ -105,7 +106,7 @@ struct ArenaVm {
             bool made = e == hipSuccess;
             if (made) { call = "hipMemMap / hipMemSetAccess"; e = map_at(va, at, pc); }
             if (e == hipSuccess && fill) {
-                if (!fill_stream) e = hipStreamCreateWithFlags(&fill_stream, hipStreamNonBlocking);
+                e = fill_stream.create();
                 if (e == hipSuccess) e = hipMemsetAsync((u8*)va + at, 0xA5, take, fill_stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(fill_stream);
                 if (e != hipSuccess) (void)hipMemUnmap((u8*)va + at, take);
@@ -264,7 +265,6 @@ void arena_release(Arena* a) {
             (void)hipMemRelease(pc.h);
             at += pc.bytes;
         }
-        if (vm->fill_stream) (void)hipStreamDestroy(vm->fill_stream);
         if (arena_trace()) fprintf(stderr, "mi_arena: released %.1f MB in %zu pieces; %.1f MB of addresses at %p retired\n", at / 1e6, vm->pieces.size(), vm->reserved / 1e6, vm->va);
         delete vm;
     }

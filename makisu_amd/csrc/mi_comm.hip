@@ -102,24 +102,13 @@ struct Shares;                          // the all-to-all form's buffers (below)
 struct Exchange {
     Shares* sh = nullptr;
     DevBuf counts, slab, gathered, compact, dup;
-    u64* pin = nullptr;                 // pinned: [0] this rank's scalar, [1 .. nranks] gathered scalars
-    size_t pin_words = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};   // before the slab all-gather / after it / after the marking
+    PinBuf pin;                         // pinned u64s: [0] this rank's scalar, [1 .. nranks] gathered scalars
+    Event ev[3];                        // before the slab all-gather / after it / after the marking
     bool timed = false;                 // the three events of the last exchange were recorded
     bool a2a = false;                   // ... the last exchange was the all-to-all form: its seven events (Shares::ev) count
 };
 int ensure_events(mi_ctx* c, Exchange* x) {
-    for (auto& e : x->ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
-    return MI_OK;
-}
-int ensure_pin(mi_ctx* c, Exchange* x) {
-    const size_t want = (size_t)c->comm_nranks + 1;
-    if (x->pin_words >= want) return MI_OK;
-    if (x->pin) (void)hipHostFree(x->pin);
-    x->pin = nullptr;
-    HIPCHK(c, hipHostMalloc((void**)&x->pin, want * 8, hipHostMallocDefault));
-    x->pin_words = want;
+    for (auto& e : x->ev) HIPCHK(c, e.create());
     return MI_OK;
 }
 Exchange* exchange_of(mi_ctx* c) {
@@ -132,11 +121,10 @@ int exchange_counts_enqueue(mi_batch* b) {
     mi_ctx* c = b->ctx;
     Exchange* x = exchange_of(c);
     HIPCHK(c, x->counts.ensure(8 * (size_t)(c->comm_nranks + 1)));
-    int rc = ensure_pin(c, x);
-    if (rc) return rc;
+    HIPCHK(c, x->pin.ensure(8 * ((size_t)c->comm_nranks + 1)));
     u64* d_counts = x->counts.as<u64>();
-    x->pin[0] = b->n_chunks;                               // pinned: the async copy needs no sync
-    HIPCHK(c, hipMemcpyAsync(d_counts + c->comm_nranks, x->pin, 8, hipMemcpyHostToDevice, c->stream));
+    x->pin.as<u64>()[0] = b->n_chunks;                               // pinned: the async copy needs no sync
+    HIPCHK(c, hipMemcpyAsync(d_counts + c->comm_nranks, x->pin.p, 8, hipMemcpyHostToDevice, c->stream));
     NCCLCHK(c, rccl()->AllGather(d_counts + c->comm_nranks, d_counts, 1, ncclUint64,
                                  (ncclComm_t)c->comm, c->stream));
     return MI_OK;
@@ -147,10 +135,10 @@ int exchange_counts_read(mi_batch* b, std::vector<u64>& counts, u64* max_out) {
     mi_ctx* c = b->ctx;
     Exchange* x = exchange_of(c);
     counts.resize((size_t)c->comm_nranks);
-    HIPCHK(c, hipMemcpyAsync(x->pin + 1, x->counts.p, 8 * counts.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(x->pin.as<u64>() + 1, x->counts.p, 8 * counts.size(), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     u64 m = 0;
-    for (size_t r = 0; r < counts.size(); ++r) { counts[r] = x->pin[1 + r]; m = counts[r] > m ? counts[r] : m; }
+    for (size_t r = 0; r < counts.size(); ++r) { counts[r] = x->pin.as<u64>()[1 + r]; m = counts[r] > m ? counts[r] : m; }
     *max_out = m;
     return MI_OK;
 }
@@ -234,11 +222,11 @@ int sum_over_ranks_enqueue(mi_ctx* c) {
 }
 int sum_over_ranks_finish(mi_ctx* c, u64* sum) {
     Exchange* x = exchange_of(c);
-    HIPCHK(c, hipMemcpyAsync(x->pin + 1, x->counts.p, 8 * (size_t)c->comm_nranks, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(x->pin.as<u64>() + 1, x->counts.p, 8 * (size_t)c->comm_nranks, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));            // sync 2 of 2
     HIPCHK(c, hipGetLastError());
     *sum = 0;
-    for (int r = 0; r < c->comm_nranks; ++r) *sum += x->pin[1 + r];
+    for (int r = 0; r < c->comm_nranks; ++r) *sum += x->pin.as<u64>()[1 + r];
     return MI_OK;
 }
 
@@ -373,16 +361,11 @@ namespace {
 
 struct Shares {                          // the all-to-all form's state of one ctx (next to its Exchange)
     DevBuf hist, cnt_send, cnt_all, send_dg, send_row, recv_dg, recv_row, ans, back, meta;
-    u64* pin = nullptr;
-    size_t pin_words = 0;
+    PinBuf pin;
     std::vector<u64> to, from, soff, roff, first;             // rows per peer and where they lie (send order / received set)
     u64 n_recv = 0, n_total = 0;
     // before / after: the split | all-to-all #1 | (marking + answers) | all-to-all #2 | (scatter)
-    hipEvent_t ev[7] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    ~Shares() {
-        for (auto e : ev) if (e) (void)hipEventDestroy(e);
-        if (pin) (void)hipHostFree(pin);
-    }
+    Event ev[7];
 };
 Shares* shares_of(mi_ctx* c) {
     Exchange* x = exchange_of(c);
@@ -406,24 +389,17 @@ int shares_split_enqueue(mi_batch* b) {
     const u64 rows = b->n_chunks;
     if (rows >= 0xFFFFFFFFull) return fail(c, MI_ERR_INVALID, "dedup set too large");
     const size_t words = (size_t)(n + 1) * n + 2 * (size_t)n + 2;
-    if (s->pin_words < words) {
-        if (s->pin) (void)hipHostFree(s->pin);
-        s->pin = nullptr;
-        s->pin_words = 0;
-        HIPCHK(c, hipHostMalloc((void**)&s->pin, words * 8, hipHostMallocDefault));
-        s->pin_words = words;
-    }
+    HIPCHK(c, s->pin.ensure(words * 8));
     const u32 n_blocks = (u32)((rows + 255) / 256);
     HIPCHK(c, s->cnt_send.ensure(8 * (size_t)(n + 1)));
     HIPCHK(c, s->cnt_all.ensure(8 * (size_t)(n + 1) * n));
     HIPCHK(c, s->hist.ensure(4 * (size_t)n * (n_blocks ? n_blocks : 1)));
     HIPCHK(c, s->send_dg.ensure(rows * 32 + 32));
     HIPCHK(c, s->send_row.ensure(rows * 4 + 16));
-    for (auto& e : s->ev)
-        if (!e) HIPCHK(c, hipEventCreate(&e));
+    for (auto& e : s->ev) HIPCHK(c, e.create());
     exchange_of(c)->timed = false;
-    s->pin[0] = rows;
-    HIPCHK(c, hipMemcpyAsync(s->cnt_send.p, s->pin, 8, hipMemcpyHostToDevice, c->stream));
+    s->pin.as<u64>()[0] = rows;
+    HIPCHK(c, hipMemcpyAsync(s->cnt_send.p, s->pin.p, 8, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipEventRecord(s->ev[0], c->stream));
     if (rows == 0) {
         HIPCHK(c, hipMemsetAsync(s->cnt_send.as<u64>() + 1, 0, 8 * (size_t)n, c->stream));
@@ -467,7 +443,7 @@ int shares_plan(mi_batch* b, const u64* m) {
     HIPCHK(c, s->ans.ensure(s->n_recv * 8 + 16));
     HIPCHK(c, s->back.ensure(b->n_chunks * 8 + 16));
     HIPCHK(c, s->meta.ensure(8 * (2 * n + 1)));
-    u64* pm = s->pin + (n + 1) * n + 1;                        // (behind the matrix's place in the pinned block)
+    u64* pm = s->pin.as<u64>() + (n + 1) * n + 1;                        // (behind the matrix's place in the pinned block)
     for (size_t q = 0; q <= n; ++q) pm[q] = s->roff[q];
     for (size_t q = 0; q < n; ++q) pm[n + 1 + q] = s->first[q];
     HIPCHK(c, hipMemcpyAsync(s->meta.p, pm, 8 * (2 * n + 1), hipMemcpyHostToDevice, c->stream));
@@ -632,9 +608,7 @@ int mi_comm_destroy(mi_ctx* c) {
     }
     if (c->comm_scratch) {
         Exchange* x = (Exchange*)c->comm_scratch;
-        delete x->sh;
-        if (x->pin) (void)hipHostFree(x->pin);
-        for (auto e : x->ev) if (e) (void)hipEventDestroy(e);
+        delete x->sh;                          // (c->stream, which every exchange ran on, is drained: mi_ctx_destroy)
         delete x;
         c->comm_scratch = nullptr;
     }
@@ -651,7 +625,7 @@ int mi_comm_exchange_ms(mi_ctx* c, double* ms_gather, double* ms_marking) {
     if (!x || !x->timed) return MI_OK;                     // no exchange yet, or one without rows
     HIPCHK(c, hipSetDevice(c->device));
     if (x->a2a) {                                              // the wire: both all-to-alls; the rest: split, marking + answers, scatter
-        const hipEvent_t* e = x->sh->ev;
+        const Event* e = x->sh->ev;
         HIPCHK(c, hipEventSynchronize(e[6]));
         float t[6] = {0, 0, 0, 0, 0, 0};
         for (int i = 0; i < 6; ++i)
@@ -740,10 +714,10 @@ int mi_dedup_allgather_all(mi_batch** batches, int n, uint64_t* n_total, uint64_
     for (int i = 0; i < n; ++i) {              // ... then read: the counts are in this process, no collective
         mi_ctx* c = batches[i]->ctx;
         (void)hipSetDevice(c->device);
-        HIPCHK(c, hipMemcpyAsync(c->h_word, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_word.p, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
-        unique_sum += *c->h_word;              // every rank counted its own first occurrences
+        unique_sum += *c->h_word.as<u64>();              // every rank counted its own first occurrences
     }
     if (n_unique) *n_unique = unique_sum;
     return MI_OK;
@@ -763,9 +737,9 @@ int mi_dedup_alltoall(mi_batch* b, uint64_t* n_total, uint64_t* n_unique, uint64
     if (rc) return rc;
     Shares* s = shares_of(c);
     NCCLCHK(c, rccl()->AllGather(s->cnt_send.p, s->cnt_all.p, n + 1, ncclUint64, (ncclComm_t)c->comm, c->stream));
-    HIPCHK(c, hipMemcpyAsync(s->pin + 1, s->cnt_all.p, 8 * (n + 1) * n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(s->pin.as<u64>() + 1, s->cnt_all.p, 8 * (n + 1) * n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));                // sync 1 of 2: what goes where is a host decision
-    rc = shares_plan(b, s->pin + 1);
+    rc = shares_plan(b, s->pin.as<u64>() + 1);
     if (rc) return rc;
     for (int back = 0; back < 2; ++back) {
         NCCLCHK(c, rccl()->GroupStart());
@@ -776,8 +750,7 @@ int mi_dedup_alltoall(mi_batch* b, uint64_t* n_total, uint64_t* n_unique, uint64
     }
     Exchange* x = exchange_of(c);
     HIPCHK(c, x->counts.ensure(8 * (n + 1)));
-    rc = ensure_pin(c, x);
-    if (rc) return rc;
+    HIPCHK(c, x->pin.ensure(8 * (n + 1)));
     rc = sum_over_ranks_enqueue(c);
     if (rc) return rc;
     u64 sum = 0;
@@ -815,9 +788,9 @@ int mi_dedup_alltoall_all(mi_batch** batches, int n, uint64_t* n_total, uint64_t
         mi_ctx* c = batches[i]->ctx;
         Shares* s = shares_of(c);
         HIPCHK(c, hipSetDevice(c->device));
-        HIPCHK(c, hipMemcpyAsync(s->pin + 1, s->cnt_send.p, 8 * w, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(s->pin.as<u64>() + 1, s->cnt_send.p, 8 * w, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(&m[(size_t)i * w], s->pin + 1, 8 * w);
+        memcpy(&m[(size_t)i * w], s->pin.as<u64>() + 1, 8 * w);
     }
     for (int i = 0; i < n; ++i) {                              // allocations and uploads: outside the groups
         HIPCHK(batches[i]->ctx, hipSetDevice(batches[i]->ctx->device));
@@ -843,10 +816,10 @@ int mi_dedup_alltoall_all(mi_batch** batches, int n, uint64_t* n_total, uint64_t
     for (int i = 0; i < n; ++i) {                              // every owner counted the distinct digests it owns
         mi_ctx* c = batches[i]->ctx;
         (void)hipSetDevice(c->device);
-        HIPCHK(c, hipMemcpyAsync(c->h_word, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_word.p, c->dd_nuniq.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipGetLastError());
-        unique_sum += *c->h_word;
+        unique_sum += *c->h_word.as<u64>();
     }
     if (n_total) *n_total = shares_of(c0)->n_total;
     if (n_unique) *n_unique = unique_sum;

@@ -343,7 +343,7 @@ int group_read_file(mi_batch* h, u64 file_index, u64 offset, void* dst, u64 len,
 void group_read_stats(mi_batch* h, double* wait_s, double* fetch_s, u64* fetches, u64* bytes) {
     double w = 0, f = 0;
     uint64_t nf = 0, nb = 0;
-    for (mi_batch* m : h->group->members) { w += m->rb_wait_s; f += m->rb_fetch_s; nf += m->rb_fetches; nb += m->rb_bytes; }
+    for (mi_batch* m : h->group->members) { w += m->readback.wait_s; f += m->readback.fetch_s; nf += m->readback.fetches; nb += m->readback.bytes; }
     if (wait_s) *wait_s = w;
     if (fetch_s) *fetch_s = f;
     if (fetches) *fetches = nf;

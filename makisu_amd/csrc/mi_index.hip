@@ -176,11 +176,11 @@ int index_grow(mi_index* x, u64 min_cap) {
         HIPCHK(c, hipMemsetAsync(x->counter.p, 0, 8, c->stream));
         hipLaunchKernelGGL(index_export_kernel, dim3((u32)((x->cap + 255) / 256)), dim3(256), 0, c->stream,
                            x->state.as<u64>(), x->slots.as<u8>(), x->cap, old.as<u8>(), have, x->counter.as<u64>());
-        HIPCHK(c, hipMemcpyAsync(c->h_word, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_word.p, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
-        if (c->h_word[0] != have)                           // the table is left as it was
+        if (c->h_word.as<u64>()[0] != have)                           // the table is left as it was
             return fail(c, MI_ERR_STATE, "chunk index holds %llu digests, counted %llu",
-                        (unsigned long long)c->h_word[0], (unsigned long long)have);
+                        (unsigned long long)c->h_word.as<u64>()[0], (unsigned long long)have);
     }
     x->state.release();
     x->slots.release();
@@ -225,11 +225,11 @@ int index_insert(mi_index* x, const u8* d_digests, const i64* d_dup_of, u64 n, u
         hipLaunchKernelGGL(index_verify_kernel, dim3(per_row), dim3(256), 0, c->stream, d_digests, n,
                            x->slots.as<u8>(), x->cap - 1, x->row_state.as<u8>(), x->row_slot.as<u64>(),
                            d_known, d_cnt + 1);
-        e = hipMemcpyAsync(c->h_word, x->counter.p, 16, hipMemcpyDeviceToHost, c->stream);
+        e = hipMemcpyAsync(c->h_word.p, x->counter.p, 16, hipMemcpyDeviceToHost, c->stream);
         if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
         if (e != hipSuccess) break;
-        added = c->h_word[0];
-        if (c->h_word[1] == 0) break;                       // no 64-bit tag collisions (the normal case)
+        added = c->h_word.as<u64>()[0];
+        if (c->h_word.as<u64>()[1] == 0) break;                       // no 64-bit tag collisions (the normal case)
         if (round >= x->cap) { rc = fail(c, MI_ERR_HIP, "chunk index: probing does not converge"); break; }
         e = hipMemsetAsync(d_cnt + 1, 0, 8, c->stream);
         if (e != hipSuccess) break;
@@ -350,13 +350,13 @@ int mi_index_export(mi_index* x, void* out, uint64_t cap_digests) {
     HIPCHK(c, hipMemsetAsync(x->counter.p, 0, 8, c->stream));
     hipLaunchKernelGGL(index_export_kernel, dim3((u32)((x->cap + 255) / 256)), dim3(256), 0, c->stream,
                        x->state.as<u64>(), x->slots.as<u8>(), x->cap, tmp.as<u8>(), x->count, x->counter.as<u64>());
-    hipError_t e = hipMemcpyAsync(c->h_word, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream);
+    hipError_t e = hipMemcpyAsync(c->h_word.p, x->counter.p, 8, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipMemcpyAsync(out, tmp.p, x->count * 32, hipMemcpyDeviceToHost, c->stream);
     if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
     if (e != hipSuccess) return fail(c, MI_ERR_HIP, "mi_index_export: %s", hipGetErrorString(e));
-    if (c->h_word[0] != x->count)
+    if (c->h_word.as<u64>()[0] != x->count)
         return fail(c, MI_ERR_STATE, "mi_index_export: the index holds %llu digests, counted %llu",
-                    (unsigned long long)c->h_word[0], (unsigned long long)x->count);
+                    (unsigned long long)c->h_word.as<u64>()[0], (unsigned long long)x->count);
     return MI_OK;
 }
 

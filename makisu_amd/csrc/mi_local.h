@@ -7,7 +7,7 @@
 #define MI_LOCAL __attribute__((visibility("hidden")))
 
 extern "C" {
-// mi_api.hip
+// mi_api.hip (what reads staged bytes back -- _read_file_landed, _read_stats, _chunk_sum, the windows, _explain_chunk: mi_readback.hip)
 MI_LOCAL void        mi_set_error(mi_batch* b, const char* msg);     // b NULL: the message mi_last_error(NULL) returns
 MI_LOCAL void**      mi_batch_tree_slot(mi_batch* b);                // the batch's walk record (mi_tree.hip owns its type)
 MI_LOCAL int         mi_batch_file_size(mi_batch* b, uint64_t file_index, uint64_t* size);

@@ -270,16 +270,18 @@ void hash_range(const HashJob& job, u8* slab, u64 slab_bytes, hipStream_t stream
 void worker(Stager* st, u32 tid) {
     mi_ctx* c = st->ctx;
     (void)hipSetDevice(c->device);
-    hipStream_t stream = nullptr;
-    void* slab = nullptr;
-    u64* d_sums = nullptr;                                   // {off, len, s1, s2} on the device
-    u64* h_sums = nullptr;                                   // ... and pinned: [0..1] in, [2..3] out
-    bool ok = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking) == hipSuccess;
-    ok = ok && hipHostMalloc(&slab, st->slab_bytes, hipHostMallocDefault) == hipSuccess;
+    PinBuf slab_pin, sums_pin;
+    DevBuf sums_dev;
+    Stream stream;                                           // declared last, so it goes first: drained before what it copies through
+    bool ok = stream.create() == hipSuccess;
+    ok = ok && slab_pin.ensure(st->slab_bytes) == hipSuccess;
     if (c->verify_staging) {
-        ok = ok && hipMalloc((void**)&d_sums, 32) == hipSuccess;
-        ok = ok && hipHostMalloc((void**)&h_sums, 32, hipHostMallocDefault) == hipSuccess;
+        ok = ok && sums_dev.ensure(32) == hipSuccess;
+        ok = ok && sums_pin.ensure(32) == hipSuccess;
     }
+    void* const slab = slab_pin.p;
+    u64* const d_sums = sums_dev.as<u64>();                  // {off, len, s1, s2} on the device
+    u64* const h_sums = sums_pin.as<u64>();                  // ... and pinned: [0..1] in, [2..3] out
     {
         std::lock_guard<std::mutex> g(st->mu);
         if (ok) ++st->n_ok;
@@ -452,10 +454,6 @@ void worker(Stager* st, u32 tid) {
             if (wake) st->cv_done.notify_all();
         }
     }
-    if (slab) (void)hipHostFree(slab);
-    if (d_sums) (void)hipFree(d_sums);
-    if (h_sums) (void)hipHostFree(h_sums);
-    if (stream) (void)hipStreamDestroy(stream);
 }
 
 }  // namespace

@@ -19,6 +19,10 @@
 //     launch take n microseconds of stream time, to move the interleavings;
 //   * MI_HIP_STUB_COPY_US=<n>: every queued copy sleeps n microseconds before it copies (widens race windows).
 //   * MI_HIP_STUB_MALLOC_LIMIT_MB=<n>: hipMalloc of more than n MiB fails with hipErrorOutOfMemory (a tree larger than the device).
+//   * MI_HIP_STUB_HOSTMALLOC_FAIL=<bytes>:<k>: the k-th (0-based) hipHostMalloc of exactly that many bytes fails, once, with
+//     hipErrorOutOfMemory (pinned memory is the scarce allocation: the second slab of a pair that is built together).
+//   * what is alive is counted -- allocations (device and pinned), streams, events (mi_hip_stub_live_*): what a ctx made
+//     is gone when the ctx is.
 //   * the virtual-memory calls (the arena, mi_arena.hip): hipMemAddressReserve = mmap(PROT_NONE); a physical piece (hipMemCreate)
 //     is a memfd filled with 0xDD, hipMemMap maps it MAP_FIXED | MAP_SHARED into the range, hipMemUnmap puts PROT_NONE back --
 //     so a byte touched before the mapper got there, or after the pieces were let go of, is a SEGFAULT here, not a plausible
@@ -139,7 +143,19 @@ const long kLimitMb = env_us("MI_HIP_STUB_MALLOC_LIMIT_MB");
 std::atomic<long long> g_vm_bytes{0};                 // physical pieces alive (hipMemCreate - hipMemRelease)
 std::atomic<long> g_vm_pieces{0}, g_vm_ranges{0};
 struct VmHandle { size_t bytes; int fd; };
-std::atomic<long> g_live_allocs{0};
+std::atomic<long> g_live_allocs{0}, g_live_streams{0}, g_live_events{0};
+struct HostFail { size_t bytes = 0; long at = -1; };
+HostFail host_fail() {
+    static const HostFail f = [] {
+        HostFail v;
+        const char* e = getenv("MI_HIP_STUB_HOSTMALLOC_FAIL");
+        const char* k = e ? strchr(e, ':') : nullptr;
+        if (k) { v.bytes = (size_t)atoll(e); v.at = atol(k + 1); }
+        return v;
+    }();
+    return f;
+}
+std::atomic<long> g_host_fail_calls{0};
 std::atomic<long> g_big_mallocs{0};                  // hipMalloc calls of a MiB and more: arenas (re)allocated
 
 }  // namespace
@@ -179,6 +195,7 @@ hipError_t hipMalloc(void** p, size_t n) {
 }
 hipError_t hipFree(void* p) { if (p) { free(p); --g_live_allocs; } return hipSuccess; }
 hipError_t hipHostMalloc(void** p, size_t n, unsigned int) {
+    if (host_fail().at >= 0 && n == host_fail().bytes && g_host_fail_calls++ == host_fail().at) return hipErrorOutOfMemory;
     void* q = aligned_alloc(4096, (n + 4095) / 4096 * 4096 + 4096);
     if (!q) return hipErrorOutOfMemory;
     memset(q, 0xCC, n);
@@ -188,8 +205,8 @@ hipError_t hipHostMalloc(void** p, size_t n, unsigned int) {
 }
 hipError_t hipHostFree(void* p) { if (p) { free(p); --g_live_allocs; } return hipSuccess; }
 
-hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { *s = (hipStream_t) new Stream(); return hipSuccess; }
-hipError_t hipStreamDestroy(hipStream_t s) { if (s) { ((Stream*)s)->sync(); delete (Stream*)s; } return hipSuccess; }
+hipError_t hipStreamCreateWithFlags(hipStream_t* s, unsigned int) { *s = (hipStream_t) new Stream(); ++g_live_streams; return hipSuccess; }
+hipError_t hipStreamDestroy(hipStream_t s) { if (s) { ((Stream*)s)->sync(); delete (Stream*)s; --g_live_streams; } return hipSuccess; }
 hipError_t hipStreamSynchronize(hipStream_t s) { S(s)->sync(); return hipSuccess; }
 
 hipError_t hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind) {
@@ -208,9 +225,9 @@ hipError_t hipMemsetAsync(void* dst, int v, size_t n, hipStream_t s) {
     return hipSuccess;
 }
 
-hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t) new Event(); return hipSuccess; }
+hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { *e = (hipEvent_t) new Event(); ++g_live_events; return hipSuccess; }
 hipError_t hipEventCreate(hipEvent_t* e) { return hipEventCreateWithFlags(e, 0); }
-hipError_t hipEventDestroy(hipEvent_t e) { delete (Event*)e; return hipSuccess; }
+hipError_t hipEventDestroy(hipEvent_t e) { if (e) { delete (Event*)e; --g_live_events; } return hipSuccess; }
 hipError_t hipEventRecord(hipEvent_t e, hipStream_t s) {
     Event* ev = (Event*)e;
     uint64_t gen;
@@ -339,6 +356,8 @@ long mi_hip_stub_vm_ranges(void) { return g_vm_ranges.load(); }
 long long mi_hip_stub_vm_bytes(void) { return g_vm_bytes.load(); }
 
 long mi_hip_stub_live_allocations(void) { return g_live_allocs.load(); }
+long mi_hip_stub_live_streams(void) { return g_live_streams.load(); }
+long mi_hip_stub_live_events(void) { return g_live_events.load(); }
 long mi_hip_stub_big_mallocs(void) { return g_big_mallocs.load(); }
 
 }  // extern "C"

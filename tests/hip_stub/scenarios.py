@@ -348,6 +348,118 @@ def scenario_long_strings(tmp, threads, slab):
         assert got[-1] == hashlib.sha256(blobs[0]).digest()
 
 
+def _live():
+    """what the double counts as alive: allocations (device and pinned), streams, events, physical arena pieces"""
+    import ctypes
+    lib = ctypes.CDLL(None)
+    out = []
+    for name in ("mi_hip_stub_live_allocations", "mi_hip_stub_live_streams", "mi_hip_stub_live_events", "mi_hip_stub_vm_pieces"):
+        fn = getattr(lib, name)
+        fn.restype = ctypes.c_long
+        out.append(fn())
+    return out
+
+
+def scenario_owners(tmp, threads, slab):
+    """Everything a ctx and its batches make -- device and pinned memory, streams, events, arena pieces -- is gone when they are:
+    a ctx driven through every path that creates a resource, its batches freed (one of them while submitted), the ctx destroyed;
+    the double's counts are back where they were before mi_ctx_create."""
+    import hashlib
+    before = _live()
+    files = make_files(os.path.join(tmp, "own"), [100, slab + 7, 3 * slab + 1, 5000], 41)
+    rng = np.random.default_rng(43)
+    small = rng.integers(0, 256, 1000, dtype=np.uint8).tobytes()             # the inline window
+    large = rng.integers(0, 256, (2 << 20) + 5, dtype=np.uint8).tobytes()    # the reader threads
+    long_ = rng.integers(0, 256, (9 << 20) + 13, dtype=np.uint8).tobytes()   # too long for a GPU lane: hashed by the readers
+    eng = M.Engine(n_streams=threads, staging_bytes=slab, flags=M.FLAG_FILE_SHA256)
+    b0, b1 = eng.batch(), eng.batch()
+    b0.add_bytes(small)
+    b0.add_bytes(large)
+    b0.add_path(files[1][0])
+    b0.add_paths([p for p, _ in files[2:]])
+    b0.add_bytes(long_)
+    b0.run()
+    want = small + large + b"".join(d for _, d in files[1:]) + long_
+    check(b0, want, "owners, first fill")
+    rows = b0.files()
+    assert rows["file_sha256"][5].tobytes() == hashlib.sha256(long_).digest()
+    b0.chunks()
+    assert b0.read_file(0, 0, len(small)) == small                            # the read-back windows exist from here on
+    assert b0.read_file(1, 5, 70000) == large[5:70005]
+    assert b0.read_file(5, 0, len(long_)) == long_                            # streams through both windows
+    assert _live()[3] > 0, "the arena has no pieces: not the piecewise kind?"
+    b0.reset()                                                                # reset and a second fill
+    b0.add_bytes(small[::-1])
+    b0.add_path(files[0][0])
+    b1.add_bytes(large[:70000])
+    b1.add_path(files[3][0])
+    b0.submit()                                                               # two batches in flight
+    b1.submit()
+    b0.wait()
+    b1.wait()
+    check(b0, small[::-1] + files[0][1], "owners, second fill")
+    check(b1, large[:70000] + files[3][1], "owners, the other batch")
+    assert b0.read_file(0, 0, 10) == small[::-1][:10]
+    b2 = eng.batch()                                                          # a batch freed while submitted
+    b2.add_bytes(small)
+    b2.add_path(files[2][0])
+    b2.submit()
+    b2.free()
+    b0.free()
+    b1.free()
+    eng.close()
+    after = _live()
+    assert after == before, "allocations, streams, events, arena pieces alive: %r before mi_ctx_create, %r after mi_ctx_destroy" % (before, after)
+    assert after[3] == 0, after
+
+
+def scenario_half_built_ring(tmp, threads, slab):
+    """MI_HIP_STUB_HOSTMALLOC_FAIL=2097152:1 -- the SECOND slab of the inline window cannot be pinned: the small add that
+    wanted the window fails with MI_ERR_NOMEM and leaves no half-built window behind; the next one -- on the same batch, once
+    it is reset, and on a fresh batch of the ctx -- builds the window from nothing, and both slabs of it carry bytes"""
+    data = [os.urandom(n) for n in (1000, 70000, 5, (2 << 20) - 100, 300000, 1 << 19)]     # (more than one slab: both are used)
+    with M.Engine(n_streams=threads, staging_bytes=slab) as eng:
+        with eng.batch() as b:
+            try:
+                b.add_bytes(b"x" * 1000)
+            except M.MiError as e:
+                assert e.code == -4, str(e)
+            else:
+                raise SystemExit("the second slab was pinned: is MI_HIP_STUB_HOSTMALLOC_FAIL=2097152:1 set?")
+            b.reset()                                   # (the failed add's row goes; a window half-built would have stayed)
+            for d in data:
+                b.add_bytes(d)
+            b.run()
+            check(b, b"".join(data), "half_built, the same batch after the failure")
+        with eng.batch() as b:
+            for d in data[::-1]:
+                b.add_bytes(d)
+            b.run()
+            check(b, b"".join(data[::-1]), "half_built, a fresh batch after the failure")
+
+
+def scenario_half_built_windows(tmp, threads, slab):
+    """MI_HIP_STUB_HOSTMALLOC_FAIL=8388608:1 -- the SECOND read-back window cannot be pinned: the read that wanted the windows
+    fails with MI_ERR_NOMEM; the next read builds them from nothing and returns the file's bytes -- also to a reader that
+    streams, whose next range travels into the second window while it consumes the first"""
+    with M.Engine(n_streams=threads, staging_bytes=slab) as eng, eng.batch() as b:
+        data = os.urandom(1000000)
+        b.add_bytes(data)
+        b.add_bytes(data[::-1])
+        b.run()
+        try:
+            b.read_file(0, 0, len(data))
+        except M.MiError as e:
+            assert e.code == -4, str(e)
+        else:
+            raise SystemExit("the second window was pinned: is MI_HIP_STUB_HOSTMALLOC_FAIL=8388608:1 set?")
+        assert b.read_file(0, 0, len(data)) == data
+        for f, want in ((0, data), (1, data[::-1])):                            # piece by piece, in order: a streaming reader
+            got = b"".join(b.read_file(f, at, 100000) for at in range(0, len(want), 100000))
+            assert got == want, "file %d read in pieces" % f
+        assert b.read_file(1, 1000, 5000) == data[::-1][1000:6000]
+
+
 def main():
     tmp = sys.argv[1]
     threads = int(sys.argv[2]) if len(sys.argv) > 2 else 4
@@ -355,8 +467,9 @@ def main():
     only = sys.argv[4].split(",") if len(sys.argv) > 4 else None
     for name, fn in [("mix", scenario_mix), ("growth", scenario_growth_and_reuse), ("two", scenario_two_batches), ("interleaved", scenario_interleaved),
                      ("errors", scenario_errors), ("api", scenario_api), ("warm", scenario_warm), ("tree", scenario_tree_reserves_ahead),
-                     ("two_ctxs", scenario_two_ctxs), ("recycle", scenario_blocks_recycle), ("long_strings", scenario_long_strings)]:
-        if (name not in only) if only else name in ("recycle", "long_strings"):    # these run only when asked for
+                     ("two_ctxs", scenario_two_ctxs), ("recycle", scenario_blocks_recycle), ("long_strings", scenario_long_strings),
+                     ("owners", scenario_owners), ("half_built_ring", scenario_half_built_ring), ("half_built_windows", scenario_half_built_windows)]:
+        if (name not in only) if only else name in ("recycle", "long_strings", "owners", "half_built_ring", "half_built_windows"):    # these run only when asked for
             continue
         fn(tmp, threads, slab)
         print("OK", name, flush=True)

@@ -143,3 +143,31 @@ def test_strings_too_long_for_a_gpu_lane_are_hashed_by_host_streams(hip_double, 
     p = subprocess.run([sys.executable, os.path.join(STUB_DIR, "scenarios.py"), str(tmp_path), str(threads), str(slab), "long_strings"],
                        env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0 and "OK long_strings" in p.stdout, p.stdout[-800:] + p.stderr[-1500:]
+
+
+def _scenario(stub, tmp, name, threads=4, slab=65536, extra_env=None):
+    env = dict(os.environ, LD_PRELOAD=(os.environ.get("LD_PRELOAD", "") + " " + stub).strip())
+    env.update(extra_env or {})
+    p = subprocess.run([sys.executable, os.path.join(STUB_DIR, "scenarios.py"), str(tmp), str(threads), str(slab), name],
+                       env=env, capture_output=True, text=True, timeout=900)
+    assert p.returncode == 0 and "OK " + name in p.stdout, "exit %d\n" % p.returncode + p.stdout[-800:] + p.stderr[-1500:]
+
+
+@pytest.mark.parametrize("threads,slab", [(4, 65536), (2, 1 << 20)])
+def test_what_a_ctx_and_its_batches_made_is_gone_when_they_are(hip_double, tmp_path, threads, slab):
+    """pinned buffers, streams and events have owners (mi_internal.h), as device memory has: after a ctx went through every path
+    that creates one -- the inline window, the reader threads, the long strings' hashing, the read-back windows, reset, two batches
+    in flight, a batch freed while submitted -- and was destroyed, the double counts as many allocations, streams, events and
+    arena pieces alive as before mi_ctx_create"""
+    _scenario(hip_double, tmp_path, "owners", threads, slab)
+
+
+def test_an_inline_window_whose_second_slab_cannot_be_pinned_is_not_left_half_built(hip_double, tmp_path):
+    """the second 2 MiB slab fails: MI_ERR_NOMEM for that add, and the next small add finds NO window and builds one -- not
+    "slab 0 is there, so the window is" and a null slab 1 at the first flip"""
+    _scenario(hip_double, tmp_path, "half_built_ring", extra_env={"MI_HIP_STUB_HOSTMALLOC_FAIL": "2097152:1"})
+
+
+def test_read_back_windows_whose_second_cannot_be_pinned_are_not_left_half_built(hip_double, tmp_path):
+    """the second 8 MiB window fails: MI_ERR_NOMEM for that read, and the next read builds both and returns the file's bytes"""
+    _scenario(hip_double, tmp_path, "half_built_windows", extra_env={"MI_HIP_STUB_HOSTMALLOC_FAIL": "8388608:1"})
