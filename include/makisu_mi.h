@@ -117,6 +117,23 @@ enum {
                                       measurements).  About 0.06 ns per byte on each side -- beside a
                                       2.45 GB/s SHA-256 stream.  The heavier MI_FLAG_VERIFY_STAGING
                                       checks every staged span on the GPU itself: a diagnosis tool */
+#define MI_FLAG_CHUNK_BLAKE2S 0x40u /* chunk digests and chunk roots of this ctx are BLAKE2s-256 (RFC 7693:
+                                      unkeyed, no salt, no personalisation, sequential mode; Python's
+                                      hashlib.blake2s(b).digest(); the empty string is one all-zero block
+                                      with t = 0 and the final flag) instead of SHA-256.  Both are keys of
+                                      THIS engine -- dedup, the chunk index, "did this file's content
+                                      change" -- and nothing Docker sees; what Docker sees stays SHA-256:
+                                      MI_FLAG_FILE_SHA256, mi_sha256_many, the layer writer's TarDigest and
+                                      gzip digest, the cache entry codec.  The chunk root is the same tree
+                                      (mi_chunk_root_alg) with BLAKE2s-256 at every node.  Cut points, the
+                                      rows, the dedup keys (a digest's first 8 bytes), the exchange do not
+                                      change.  The algorithm BELONGS to whatever keeps digests or roots
+                                      between batches: a chunk index, a MemFS handle, the ranks of an
+                                      exchange, an exported index blob -- see each of them.  Fewer VALU
+                                      instructions per block than SHA-256              */
+/* a ctx's chunk digest algorithm (mi_ctx_chunk_digest, mi_chunk_root_alg) */
+#define MI_DIGEST_SHA256  0u
+#define MI_DIGEST_BLAKE2S 1u
 
 typedef struct mi_ctx mi_ctx;
 typedef struct mi_batch mi_batch;
@@ -218,8 +235,11 @@ MI_CORE int  mi_abi_version(void);
 /* Diagnostics: from now on every chunk-pass launch of this ctx runs the recording instantiation of the hashing kernel
  * and appends one record per wave to `path` (where it ran, when, how much it hashed: tools/sha_wave_stats.py reads it);
  * each such launch is followed by a stream synchronize -- never on a ctx whose time is measured.  NULL or "" turns it
- * off.  MI_SHA_WAVE_STATS=<file> in the environment of mi_ctx_create does the same for the new ctx.              */
+ * off.  MI_SHA_WAVE_STATS=<file> in the environment of mi_ctx_create does the same for the new ctx.  The record is the
+ * SHA-256 kernel's: on a ctx with MI_FLAG_CHUNK_BLAKE2S the call returns MI_ERR_INVALID (and the variable is ignored).   */
 MI_DIAG int  mi_debug_sha_wave_stats(mi_ctx* ctx, const char* path);
+/* MI_DIGEST_SHA256, or MI_DIGEST_BLAKE2S for a ctx created with MI_FLAG_CHUNK_BLAKE2S */
+MI_BLOCK int mi_ctx_chunk_digest(mi_ctx* ctx, uint32_t* alg);
 MI_CORE int  mi_config_default(mi_config* cfg);
 MI_CORE int  mi_ctx_create(const mi_config* cfg, mi_ctx** out);
 /* Batches and indexes hold a pointer to their ctx: free them first (mi_batch_free /
@@ -245,6 +265,8 @@ MI_DIAG int  mi_device_info(mi_ctx* ctx, int32_t* n_cu, int32_t* clock_mhz, uint
  * three launches.  0 = defaults (8 waves, 512 blocks: ~10 ms).  bench.py quotes the SHA pass against
  * this number from the same run (SURVEY.md 8d "second roof that actually binds SHA-256").          */
 MI_DIAG int  mi_sha_valu_roof(mi_ctx* ctx, uint32_t waves_per_simd, uint32_t blocks, double* bytes_per_second);
+/* The same for BLAKE2s-256: the ten-round compression of the MI_FLAG_CHUNK_BLAKE2S kernels alone (any ctx may ask). */
+MI_DIAG int  mi_blake2s_valu_roof(mi_ctx* ctx, uint32_t waves_per_simd, uint32_t blocks, double* bytes_per_second);
 
 /* ---- batch: a set of files scanned in one pass --------------------------------- *
  * Serves the per-entry loop of MemFS.commitLayer -> contentMemFile.commit ->
@@ -378,6 +400,9 @@ MI_BLOCK int mi_batch_add_synthetic_part(mi_batch* b, uint64_t file_size, uint64
  * over the concatenation when n <= 64, else the fan-out-64 tree the engine computes per file.  A
  * split file's root = mi_chunk_root over its parts' digests put end to end.                     */
 MI_BLOCK int mi_chunk_root(const uint8_t* digests, uint64_t n, uint8_t* root_out);
+/* The same tree with the hash of `alg` (MI_DIGEST_*) at every node: the chunk root of a ctx whose mi_ctx_chunk_digest
+ * is alg.  alg = MI_DIGEST_SHA256 is mi_chunk_root; an unknown alg is MI_ERR_INVALID.                                */
+MI_BLOCK int mi_chunk_root_alg(uint32_t alg, const uint8_t* digests, uint64_t n, uint8_t* root_out);
 /* Blocking: stages the batch and runs Gear marking + cut selection only.                         */
 MI_BLOCK int mi_batch_scan_cuts(mi_batch* b);
 MI_BLOCK int mi_batch_parts(mi_batch* b, mi_part_state* out, uint64_t cap, uint64_t* n_parts);
@@ -426,7 +451,10 @@ MI_BLOCK int mi_batch_device_dup_of(mi_batch* b, const void** d_dup_of, uint64_t
  * padded to the largest count), marks this rank's chunks against the gathered set
  * (mi_batch_mark_global) so the batch's dup_of holds GLOBAL row indices (rank-major), and
  * sums the ranks' first-occurrence counts into n_unique; collective: every rank must call
- * it.  Outputs are optional.                                                            */
+ * it.  Outputs are optional.
+ * Every rank's digests must be of one algorithm (all ctxs with MI_FLAG_CHUNK_BLAKE2S, or none):
+ * the _all forms check it (MI_ERR_INVALID); across processes it is the caller's to guarantee --
+ * no collective is spent on it, and ranks that disagree simply find no duplicates of each other. */
 #define MI_COMM_ID_BYTES 128
 MI_BLOCK int mi_comm_unique_id(void* id_out /* MI_COMM_ID_BYTES */);
 MI_BLOCK int mi_comm_init_rank(mi_ctx* ctx, int nranks, int rank, const void* id);
@@ -674,7 +702,9 @@ MI_CORE void mi_copy_layer_free(mi_copy_layer* layer);
  *                             per deleted subtree (if the child's src is really gone).  roots / root_stride: chunk roots
  *                             by file_index, kept in the tree -- for changed paths with their new node, for unchanged
  *                             files that had none as the root they have now -- so that the NEXT scan's isUpdated is
- *                             content-aware (NULL = the reference's metadata-only rule).  mi_memfs_commit_layer with
+ *                             content-aware (NULL = the reference's metadata-only rule).  The handle does not know which
+ *                             algorithm these roots were computed with: they must be of the one (mi_ctx_chunk_digest) that
+ *                             later commits on this handle use, or every file reads as changed.  mi_memfs_commit_layer with
  *                             a ctx does walk, GPU scan, this call and the layer tar in one.
  *   mi_memfs_add_layer_by_copy_ops   AddLayerByCopyOps (mem_fs.go:276-289): addToLayer per mi_copy_op against this tree.
  * Both return the layer in commit order as an mi_copy_layer (mi_copy_layer_entries: headers + the path each entry's
@@ -785,6 +815,13 @@ MI_BLOCK void mi_layer_free(mi_layer* layer);
  *   4. the layer writer frames the tar; file content comes from HBM (mi_layer_add_batch_file): the tar holds the bytes
  *      the stored root describes, even if the file was written to after it was staged;
  *   5. with an index set (mi_memfs_set_index) the batch's chunk digests are added to it (mi_index_add_batch).
+ * The roots a handle holds were computed with ONE chunk digest algorithm (mi_ctx_chunk_digest of the ctx that committed
+ * them).  A commit with a ctx of the other algorithm would compare roots of different hashes and call every file changed:
+ * it fails with MI_ERR_STATE before anything is walked or changed.  mi_memfs_commit_layer_n with ctxs that disagree among
+ * themselves is MI_ERR_INVALID.  A handle on which no commit with a ctx has begun its scan takes either; a commit that fails
+ * after that point may already have stored roots, so it fixes the algorithm as a successful one does.  mi_memfs_reset forgets
+ * the tree and with it the algorithm.  Roots handed in from outside (mi_memfs_add_layer_by_scan's `roots`) are not tracked:
+ * they must be of the algorithm that later commits on the handle use.
  * Steps 2-4 overlap: the scan runs on a thread of the library's own while the committing thread computes the layer and
  * frames the tar from the bytes that have landed; the diff waits for the scan only where a root DECIDES (a file the tree
  * holds with a root and an unchanged header).  A file that vanishes or shrinks between the walk and its staging therefore
@@ -929,7 +966,15 @@ MI_CORE int mi_sha256_many(mi_ctx* ctx, const void* data, const uint64_t* offset
  * digest was in the index BEFORE the call (an in-batch repeat of a new digest stays
  * 0 - dup_of already says so), then the new digests are added.  known may be NULL.
  * mi_index_export / mi_index_import move the set as a flat blob of 32-byte digests
- * (order unspecified) so the shim can keep it behind keyvalue.Store.Put/Get.      */
+ * (order unspecified) so the shim can keep it behind keyvalue.Store.Put/Get.
+ *
+ * An index holds digests of ONE algorithm, its ctx's (mi_ctx_chunk_digest): it takes
+ * batches of its own ctx only, and a commit whose ctxs hash with the other algorithm
+ * fails with MI_ERR_INVALID before it starts (mi_memfs_set_index).  The blob of
+ * mi_index_export is raw digests and says nothing about their algorithm: the caller
+ * keeps the algorithm with the blob and imports it into an index of the same kind --
+ * SHA-256 and BLAKE2s digests of the same chunk never compare equal, so a mixed-up
+ * index silently knows nothing.                                                    */
 MI_CORE int  mi_index_create(mi_ctx* ctx, uint64_t capacity_hint, mi_index** out);
 MI_CORE void mi_index_free(mi_index* index);
 MI_CORE int  mi_index_count(mi_index* index, uint64_t* n_digests);

@@ -16,6 +16,7 @@ from . import build as _build
 
 __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE", "CHUNK_DTYPE",
            "FLAG_FILE_SHA256", "FLAG_FILE_CRC32", "FLAG_NO_DEDUP", "FLAG_PREFETCH_ROWS", "FLAG_VERIFY_STAGING", "FLAG_FILE_SUMS",
+           "FLAG_CHUNK_BLAKE2S", "DIGEST_SHA256", "DIGEST_BLAKE2S", "chunk_root",
            "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex"]
 
 FLAG_FILE_SHA256 = 0x1
@@ -24,6 +25,8 @@ FLAG_NO_DEDUP = 0x4
 FLAG_PREFETCH_ROWS = 0x8
 FLAG_VERIFY_STAGING = 0x10
 FLAG_FILE_SUMS = 0x20
+FLAG_CHUNK_BLAKE2S = 0x40                # chunk digests and chunk roots are BLAKE2s-256 (hashlib.blake2s) instead of SHA-256
+DIGEST_SHA256, DIGEST_BLAKE2S = 0, 1     # Engine.chunk_digest, chunk_root(alg=)
 SHA_LOADS_AUTO, SHA_LOADS_LANE, SHA_LOADS_COOP = 0, 1, 2
 SHA_SCHED_FLAT = 1                       # mi_config.sha_sched: one range, every wave equal
 
@@ -209,6 +212,8 @@ def load_library(rebuild=False):
         "mi_device_info": ([vp, C.POINTER(C.c_int32), C.POINTER(C.c_int32), u64p, C.c_char_p,
                             C.c_size_t], C.c_int),
         "mi_sha_valu_roof": ([vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)], C.c_int),
+        "mi_blake2s_valu_roof": ([vp, C.c_uint32, C.c_uint32, C.POINTER(C.c_double)], C.c_int),
+        "mi_ctx_chunk_digest": ([vp, C.POINTER(C.c_uint32)], C.c_int),
         "mi_batch_begin": ([vp, u64, u64, C.POINTER(vp)], C.c_int),
         "mi_batch_add_bytes": ([vp, vp, u64, u64], C.c_int),
         "mi_batch_add_path": ([vp, C.c_char_p, u64, u64], C.c_int),
@@ -219,6 +224,7 @@ def load_library(rebuild=False):
         "mi_batch_add_path_part": ([vp, C.c_char_p, u64, u64, u64, u64], C.c_int),
         "mi_batch_add_synthetic_part": ([vp, u64, u64, u64, u64, u64], C.c_int),
         "mi_chunk_root": ([vp, u64, vp], C.c_int),
+        "mi_chunk_root_alg": ([C.c_uint32, vp, u64, vp], C.c_int),
         "mi_batch_scan_cuts": ([vp], C.c_int),
         "mi_batch_parts": ([vp, C.POINTER(PartState), u64, u64p], C.c_int),
         "mi_batch_set_part_entry": ([vp, u64, u64], C.c_int),
@@ -873,15 +879,16 @@ def layer_header_bytes(entry, mode_with_type=False):
     return bytes(buf[: n.value])
 
 
-def chunk_root(digests):
-    """mi_chunk_root: the file-level root of a list of chunk digests (bytes-like of n x 32, or an
-    (n, 32) uint8 array) -- what a split file's parts combine to."""
+def chunk_root(digests, alg=DIGEST_SHA256):
+    """mi_chunk_root_alg: the file-level root of a list of chunk digests (bytes-like of n x 32, or an
+    (n, 32) uint8 array) -- what a split file's parts combine to.  alg: the DIGEST_* of the ctx the
+    digests came from (Engine.chunk_digest)."""
     a = np.ascontiguousarray(np.frombuffer(digests, dtype=np.uint8) if not isinstance(digests, np.ndarray) else digests,
                              dtype=np.uint8).reshape(-1, 32)
     out = np.zeros(32, dtype=np.uint8)
-    rc = load_library().mi_chunk_root(a.ctypes.data if a.size else None, a.shape[0], out.ctypes.data)
+    rc = load_library().mi_chunk_root_alg(alg, a.ctypes.data if a.size else None, a.shape[0], out.ctypes.data)
     if rc:
-        raise MiError(rc, "mi_chunk_root")
+        raise MiError(rc, "mi_chunk_root_alg")
     return out.tobytes()
 
 
@@ -1042,6 +1049,19 @@ class Engine:
         """The SHA-256 VALU roof of this device right now, in bytes hashed per second (mi_sha_valu_roof)."""
         v = C.c_double()
         self._check(self._lib.mi_sha_valu_roof(self._h, waves_per_simd, blocks, C.byref(v)))
+        return v.value
+
+    def blake2s_valu_roof(self, waves_per_simd=0, blocks=0):
+        """The BLAKE2s-256 VALU roof of this device right now, in bytes hashed per second (mi_blake2s_valu_roof)."""
+        v = C.c_double()
+        self._check(self._lib.mi_blake2s_valu_roof(self._h, waves_per_simd, blocks, C.byref(v)))
+        return v.value
+
+    @property
+    def chunk_digest(self):
+        """DIGEST_SHA256, or DIGEST_BLAKE2S for an engine made with FLAG_CHUNK_BLAKE2S (mi_ctx_chunk_digest)."""
+        v = C.c_uint32()
+        self._check(self._lib.mi_ctx_chunk_digest(self._h, C.byref(v)))
         return v.value
 
     def debug_sha_wave_stats(self, path):

@@ -8,7 +8,7 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libmakisu_mi.so")
-SOURCES = ["mi_api.hip", "mi_readback.hip", "mi_group.hip", "gear_cdc.hip", "sha256.hip", "tables.hip", "crc32.hip", "mi_tree.hip", "mi_comm.hip",
+SOURCES = ["mi_api.hip", "mi_readback.hip", "mi_group.hip", "gear_cdc.hip", "sha256.hip", "blake2s.hip", "tables.hip", "crc32.hip", "mi_tree.hip", "mi_comm.hip",
            "mi_index.hip", "mi_alloc.hip", "mi_arena.hip", "mi_tar.hip", "mi_stage.hip", "mi_layer.hip", "mi_copyops.hip", "mi_memfs.hip", "mi_commit.hip"]
 # every header there is, listed from the directories: a new one cannot be forgotten
 INCLUDE = os.path.join(HERE, "..", "include")
@@ -19,7 +19,9 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-u
 # sha256.hip aggregates its dequeue atomic per wave by hand and consumes the result one
 # iteration later; LLVM's atomic optimizer would wrap it in its own reduction + an immediate
 # wait for the result, which stalls the wave for a memory round trip per dequeue.
-EXTRA = {"sha256.hip": ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]}
+# blake2s.hip: the same loop with the same dequeue.
+NO_ATOMIC_OPT = ["-mllvm", "-amdgpu-atomic-optimizer-strategy=None"]
+EXTRA = {"sha256.hip": NO_ATOMIC_OPT, "blake2s.hip": NO_ATOMIC_OPT}
 OBJ_DIR = os.path.join(HERE, "_obj")
 
 

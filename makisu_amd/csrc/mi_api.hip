@@ -493,7 +493,9 @@ int submit_pipeline_enqueue(mi_batch* b) {
     // of one batch are no longer filled by the other's hashing), which is what one batch at a time does too.
     if (c->serialize_sha && c->sha_done_set) HIPCHK(c, hipStreamWaitEvent(s, c->sha_done, 0));
     HIPCHK(c, hipEventRecord(b->ev[2], s));
-    launch_sha256_items(kShaChunks, b->arena.as<u8>(), b->q_off.as<u64>(), b->q_len.as<u64>(),
+    // the chunk digest and the root tree are the ctx's algorithm (MI_FLAG_CHUNK_BLAKE2S); whole-file digests stay SHA-256
+    const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
+    hash_items(kShaChunks, b->arena.as<u8>(), b->q_off.as<u64>(), b->q_len.as<u64>(),
                         b->q_id.as<u32>(), (u32)cap, d_n, heads(0), roles(0), false,
                         b->digests.as<u8>(), sha, ncu, b->arena_used, s);
     HIPCHK(c, hipEventRecord(b->ev[3], s));
@@ -528,19 +530,19 @@ int submit_pipeline_enqueue(mi_batch* b) {
                               b->rseg_first.as<u64>(), b->rseg_total.as<u64>(), b->scratch.as<u64>(),
                               b->root_level[r].as<u8>(), b->root_items_off.as<u64>(),
                               b->root_items_len.as<u64>(), s);
-            launch_sha256_items(kShaRoots, nullptr, b->root_items_off.as<u64>(),
-                                b->root_items_len.as<u64>(), nullptr, (u32)out_ub,
-                                b->rseg_total.as<u64>(), heads(3 + r), nullptr, false,
-                                b->root_level[r].as<u8>(), sha, ncu, 0, s);
+            hash_items(kShaRoots, nullptr, b->root_items_off.as<u64>(),
+                       b->root_items_len.as<u64>(), nullptr, (u32)out_ub,
+                       b->rseg_total.as<u64>(), heads(3 + r), nullptr, false,
+                       b->root_level[r].as<u8>(), sha, ncu, 0, s);
             nodes_ub = out_ub;
             std::swap(cur_addr, next_addr);
             std::swap(cur_cnt, next_cnt);
         }
         launch_root_final_items(cur_addr, cur_cnt, nf, b->item_off.as<u64>(), b->item_len.as<u64>(), s);
     }
-    launch_sha256_items(kShaRoots, nullptr, b->item_off.as<u64>(), b->item_len.as<u64>(), nullptr,
-                        (u32)nf, nullptr, heads(1), nullptr, false, b->roots.as<u8>(),
-                        sha, ncu, 0, s);
+    hash_items(kShaRoots, nullptr, b->item_off.as<u64>(), b->item_len.as<u64>(), nullptr,
+               (u32)nf, nullptr, heads(1), nullptr, false, b->roots.as<u8>(),
+               sha, ncu, 0, s);
     if (c->cfg.flags & MI_FLAG_FILE_SHA256)
         launch_sha256_items(kShaFiles, b->arena.as<u8>(), d_off, b->fsha_len.as<u64>(), nullptr, (u32)nf, nullptr,
                             heads(2), nullptr, false, b->file_sha.as<u8>(), sha, ncu, b->arena_used, s);   // files come in
@@ -677,6 +679,8 @@ int mi_abi_version(void) { return MI_ABI_VERSION; }
 
 int mi_debug_sha_wave_stats(mi_ctx* c, const char* path) {
     if (!c) return MI_ERR_INVALID;
+    if (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S)
+        return fail(c, MI_ERR_INVALID, "mi_debug_sha_wave_stats: the per-wave record is the SHA-256 chunk pass's; this ctx hashes chunks with BLAKE2s");
     c->sha_wave_stats = path ? path : "";
     c->sha.wave_stats_path = c->sha_wave_stats.empty() ? nullptr : c->sha_wave_stats.c_str();
     return MI_OK;
@@ -808,7 +812,8 @@ int mi_ctx_create(const mi_config* cfg, mi_ctx** out) {
     if (const char* e = getenv("MI_SHA_PIN_BLOCKS")) c->sha.pin_blocks_per_cu = atoi(e) != 0;
     if (const char* e = getenv("MI_SHA_ROLES")) c->sha.roles = atoi(e) != 0;
     if (const char* e = getenv("MI_SHA_PRIO")) c->sha.prio = atoi(e) != 0;
-    if (const char* e = getenv("MI_SHA_WAVE_STATS")) (void)mi_debug_sha_wave_stats(c, e);     // diagnostics, read per ctx here
+    if (const char* e = getenv("MI_SHA_WAVE_STATS"))                                          // diagnostics, read per ctx here
+        if (!(cfg->flags & MI_FLAG_CHUNK_BLAKE2S)) (void)mi_debug_sha_wave_stats(c, e);       // (SHA-256 only: ignored, not an error)
     if (const char* e = getenv("MI_SHA_LONG_SHIFT")) {
         const int v = atoi(e);
         if (v >= 0 && v <= 16) c->sha.long_shift = v;
@@ -884,6 +889,27 @@ int mi_sha_valu_roof(mi_ctx* c, uint32_t waves_per_simd, uint32_t blocks, double
                                               scratch.as<u32>(), c->stream, c->ev[0], c->ev[1]);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess || *bytes_per_second <= 0) return fail(c, MI_ERR_HIP, "mi_sha_valu_roof: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+int mi_blake2s_valu_roof(mi_ctx* c, uint32_t waves_per_simd, uint32_t blocks, double* bytes_per_second) {
+    if (!c || !bytes_per_second) return MI_ERR_INVALID;
+    HIPCHK(c, hipSetDevice(c->device));
+    if (waves_per_simd == 0) waves_per_simd = 8;
+    if (blocks == 0) blocks = 512;
+    if (waves_per_simd > 8 || blocks > (1u << 20)) return fail(c, MI_ERR_INVALID, "mi_blake2s_valu_roof: waves_per_simd <= 8, blocks <= 2^20");
+    DevBuf scratch;
+    HIPCHK(c, scratch.ensure((size_t)c->prop.multiProcessorCount * waves_per_simd * kShaWG * 4));
+    *bytes_per_second = measure_blake2s_valu_roof(c->prop.multiProcessorCount, (int)waves_per_simd, blocks,
+                                                  scratch.as<u32>(), c->stream, c->ev[0], c->ev[1]);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess || *bytes_per_second <= 0) return fail(c, MI_ERR_HIP, "mi_blake2s_valu_roof: %s", hipGetErrorString(e));
+    return MI_OK;
+}
+
+int mi_ctx_chunk_digest(mi_ctx* c, uint32_t* alg) {
+    if (!c || !alg) return MI_ERR_INVALID;
+    *alg = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? MI_DIGEST_BLAKE2S : MI_DIGEST_SHA256;
     return MI_OK;
 }
 

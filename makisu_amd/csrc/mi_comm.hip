@@ -681,6 +681,9 @@ int mi_dedup_allgather_all(mi_batch** batches, int n, uint64_t* n_total, uint64_
         if (!batches[i]->ran || batches[i]->in_flight)
             return fail(c, MI_ERR_STATE, "every batch must have run (and been waited for)");
     }
+    for (int i = 1; i < n; ++i)                // digests of two algorithms never match: an exchange of them finds nothing
+        if ((batches[i]->ctx->cfg.flags ^ batches[0]->ctx->cfg.flags) & MI_FLAG_CHUNK_BLAKE2S)
+            return fail(batches[i]->ctx, MI_ERR_INVALID, "batch %d hashes chunks with another algorithm than batch 0 (MI_FLAG_CHUNK_BLAKE2S)", i);
     mi_ctx* c0 = batches[0]->ctx;
     int rc = MI_OK;
     // every rank's row count is known to this process: no counts collective, no host sync before the slabs
@@ -774,6 +777,9 @@ int mi_dedup_alltoall_all(mi_batch** batches, int n, uint64_t* n_total, uint64_t
         if (!batches[i]->ran || batches[i]->in_flight)
             return fail(c, MI_ERR_STATE, "every batch must have run (and been waited for)");
     }
+    for (int i = 1; i < n; ++i)                // digests of two algorithms never match: an exchange of them finds nothing
+        if ((batches[i]->ctx->cfg.flags ^ batches[0]->ctx->cfg.flags) & MI_FLAG_CHUNK_BLAKE2S)
+            return fail(batches[i]->ctx, MI_ERR_INVALID, "batch %d hashes chunks with another algorithm than batch 0 (MI_FLAG_CHUNK_BLAKE2S)", i);
     mi_ctx* c0 = batches[0]->ctx;
     int rc = need_p2p(c0);
     if (rc) return rc;

@@ -492,8 +492,29 @@ static int memfs_commit(mi_memfs* m, mi_ctx* const* ctxs, uint32_t n_ctx, int mu
     if (layer_out) *layer_out = nullptr;
     memset(&m->last, 0, sizeof m->last);
     if (!must_scan && n_ops == 0) return MI_OK;                                   // "Nothing to do, return."
+    // ONE chunk digest algorithm per handle: the ctxs agree among themselves, with the roots the tree holds and with the index --
+    // roots of two hashes never compare equal, every file would read as changed.  Checked before anything is walked or changed.
+    uint32_t alg = MI_DIGEST_SHA256;
+    for (uint32_t k = 0; k < n_ctx; ++k) {
+        uint32_t a = 0;
+        if (mi_ctx_chunk_digest(ctxs[k], &a)) return MI_ERR_INVALID;
+        if (k == 0) alg = a;
+        else if (a != alg) { m->err = "failed to generate diff layer: the ctxs of one commit hash chunks with different algorithms (MI_FLAG_CHUNK_BLAKE2S)"; return MI_ERR_INVALID; }
+    }
+    if (n_ctx && m->root_alg >= 0 && (uint32_t)m->root_alg != alg) {
+        m->err = "failed to generate diff layer: this handle's roots were computed with the other chunk digest algorithm (MI_FLAG_CHUNK_BLAKE2S): mi_memfs_reset first";
+        return MI_ERR_STATE;
+    }
+    if (n_ctx && m->index) {
+        uint32_t a = 0;
+        if (mi_ctx_chunk_digest(mi_index_ctx(m->index), &a) || a != alg) {
+            m->err = "failed to generate diff layer: chunk index: the index holds digests of the other chunk digest algorithm (MI_FLAG_CHUNK_BLAKE2S)";
+            return MI_ERR_INVALID;
+        }
+    }
     Commit c(m, ctxs, n_ctx, must_scan != 0, ops, n_ops);
     int rc = c.open_batch();
+    if (!rc && n_ctx) m->root_alg = (int)alg;                                     // (from here on roots of this algorithm may land)
     if (!rc) rc = must_scan ? c.layer_by_scan() : c.layer_by_copy_ops();
     if (rc) return rc;                                                            // (no layer; ~Commit settles the scan)
     rc = c.write_layer(cfg, res);

@@ -134,6 +134,36 @@ struct ShaTune {
     const char* wave_stats_path = nullptr;   // diagnostics (mi_debug_sha_wave_stats): per-wave records of every chunk pass
                                              // of this ctx are appended to this file; the ctx owns the string
 };
+// The geometry of one hashing launch, the same rule for both algorithms' launchers (sha256.hip launch_sha256_items has the
+// measurements behind it): the load scheme by footprint, blocks_per_cu x n_cu persistent workgroups at the most, the grid
+// a multiple of the queue count so that every queue has the same number of pullers, and -- lane-owned loads only, up to
+// max_pinned workgroups per CU -- an LDS request of just over 160 KiB / (blocks_per_cu + 1) per workgroup, unused memory
+// that makes the intended placement the only possible one.  static_lds: what the lane-owned kernel declares itself.
+struct ShaGeometry {
+    bool coop;
+    bool pinned;       // lds_pad is set: the caller raises its kernels' dynamic LDS limit (96 KiB) before the launch
+    u32 grid;
+    size_t lds_pad;
+};
+inline ShaGeometry sha_items_geometry(ShaPass pass, u32 n, const ShaTune& tune, int n_cu, u64 footprint_bytes,
+                                      int max_pinned, size_t static_lds) {
+    ShaGeometry g{};
+    g.coop = pass != kShaRoots && footprint_bytes >= tune.coop_min_bytes;
+    int blocks_per_cu = tune.blocks_per_cu;
+    if (g.coop) blocks_per_cu = tune.coop_blocks_per_cu ? tune.coop_blocks_per_cu
+                              : footprint_bytes >= (24ull << 30) ? 3 : blocks_per_cu;   // enough work per lane for a third
+    g.pinned = tune.pin_blocks_per_cu && !g.coop && blocks_per_cu >= 1 && blocks_per_cu <= max_pinned;
+    if (g.pinned) {
+        const size_t per_wg = (160u * 1024u) / (size_t)(blocks_per_cu + 1) + 1024u;
+        g.lds_pad = per_wg > static_lds ? per_wg - static_lds : 0;
+    }
+    const u64 want = ((u64)n + kShaWG - 1) / kShaWG;
+    const u64 cap = (u64)blocks_per_cu * (u64)n_cu;
+    g.grid = (u32)(want < cap ? want : cap);
+    if (g.grid >= (u32)kShaQueues) g.grid -= g.grid % kShaQueues;
+    if (g.grid == 0) g.grid = 1;
+    return g;
+}
 // n = string count (or its upper bound when d_n, a device word holding the real count, is given)
 // d_heads and d_roles must be zero on entry unless zero_heads (then the launcher clears them first)
 void launch_sha256_items(ShaPass pass, const u8* d_base, const u64* d_off, const u64* d_len,
@@ -143,6 +173,13 @@ void launch_sha256_items(ShaPass pass, const u8* d_base, const u64* d_off, const
 // d_scratch: n_cu * waves_per_simd * kShaWG words
 double measure_sha_valu_roof(int n_cu, int waves_per_simd, u32 blocks, u32* d_scratch, hipStream_t s,
                              hipEvent_t e0, hipEvent_t e1);
+// blake2s.hip: the same two with BLAKE2s-256 (RFC 7693, unkeyed) in place of SHA-256 -- the chunk digest and the root tree
+// of a ctx with MI_FLAG_CHUNK_BLAKE2S.  Same queues, same buffers, same slack behind them.
+void launch_blake2s_items(ShaPass pass, const u8* d_base, const u64* d_off, const u64* d_len,
+                          const u32* d_ids, u32 n, const u64* d_n, u32* d_heads, u32* d_roles, bool zero_heads,
+                          u8* d_out, const ShaTune& tune, int n_cu, u64 footprint_bytes, hipStream_t s);
+double measure_blake2s_valu_roof(int n_cu, int waves_per_simd, u32 blocks, u32* d_scratch, hipStream_t s,
+                                 hipEvent_t e0, hipEvent_t e1);
 
 // tables.hip
 // unit0: the files' first byte is byte 16 * unit0 of their content stream (0 except for parts)

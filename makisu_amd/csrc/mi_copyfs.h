@@ -643,6 +643,8 @@ struct mi_memfs {
     std::vector<mi_ctx*> batch_ctxs;     // the ctxs it was made for: one, or several -- then one batch per ctx behind the one
                                          // handle (mi_memfs_commit_layer_n: a group)
     mi_index* index = nullptr;           // mi_memfs_set_index: every content-aware commit adds its batch's chunks
+    int root_alg = -1;                   // MI_DIGEST_* of the roots the tree holds; -1: no content-aware commit since the handle was
+                                         // made or reset (memfs_commit refuses a ctx of the other kind)
     mi_commit_stats last;                // of the last mi_memfs_commit_layer
     bool went_windowed = false;          // the scanned tree did not fit the device (the next full scan goes window by window at once)
     mi_memfs() { memset(&last, 0, sizeof last); }

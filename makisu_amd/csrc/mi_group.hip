@@ -298,7 +298,7 @@ int group_roots(mi_batch* h, u8* out, u64 cap) {
     if (rc) return rc;
     for (u64 g = 0; g < nf; ++g) {
         if (G.row_member[g] != kGroupSplit) { memcpy(out + 32 * g, mr[G.row_member[g]].data() + 32 * G.row_row[g], 32); continue; }
-        // a split file's root: mi_chunk_root over its parts' chunk digests put end to end (include/makisu_mi.h, "parts")
+        // a split file's root: mi_chunk_root_alg over its parts' chunk digests put end to end (include/makisu_mi.h, "parts")
         std::vector<u8> dg;
         for (const SplitPart& pt : G.splits[G.row_row[g]].parts) {
             const mi_file_result* fr = nullptr;
@@ -310,7 +310,9 @@ int group_roots(mi_batch* h, u8* out, u64 cap) {
             const mi_file_result& f = fr[pt.row];
             for (u64 j = 0; j < f.n_chunks; ++j) { const u8* d = cr[f.first_chunk + j].sha256; dg.insert(dg.end(), d, d + 32); }
         }
-        rc = mi_chunk_root(dg.data(), dg.size() / 32, out + 32 * g);
+        uint32_t alg = MI_DIGEST_SHA256;                              // (the members' ctxs agree: group_begin)
+        (void)mi_ctx_chunk_digest(h->ctx, &alg);
+        rc = mi_chunk_root_alg(alg, dg.data(), dg.size() / 32, out + 32 * g);
         if (rc) return fail(h->ctx, rc, "the root of a split file");
     }
     return MI_OK;
@@ -408,6 +410,9 @@ int mi_batch_group_begin(mi_ctx* const* ctxs, uint32_t n, mi_batch** out) {
         if (!ctxs[i]) return MI_ERR_INVALID;
         for (uint32_t j = 0; j < i; ++j) if (ctxs[j] == ctxs[i]) return fail(ctxs[0], MI_ERR_INVALID, "a batch group needs %u DIFFERENT ctxs", n);
     }
+    for (uint32_t i = 1; i < n; ++i)                                  // one root per file, whichever member hashed it
+        if ((ctxs[i]->cfg.flags ^ ctxs[0]->cfg.flags) & MI_FLAG_CHUNK_BLAKE2S)
+            return fail(ctxs[0], MI_ERR_INVALID, "the ctxs of a batch group hash chunks with different algorithms (MI_FLAG_CHUNK_BLAKE2S)");
     mi_batch* h = new mi_batch();
     h->ctx = ctxs[0];
     h->group.reset(new Group());

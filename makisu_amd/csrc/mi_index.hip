@@ -337,6 +337,7 @@ int mi_index_add_digests(mi_index* x, const void* digests, uint64_t n, uint8_t* 
 }
 
 int mi_index_same_ctx(mi_index* x, mi_batch* b) { return x && b && b->ctx == x->ctx ? 1 : 0; }
+mi_ctx* mi_index_ctx(mi_index* x) { return x ? x->ctx : nullptr; }
 
 int mi_index_export(mi_index* x, void* out, uint64_t cap_digests) {
     if (!x || (!out && cap_digests)) return MI_ERR_INVALID;

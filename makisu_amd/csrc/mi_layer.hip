@@ -30,6 +30,7 @@
 // the gzip digest is a faithful DigestPair member for THIS writer, not comparable across writers.
 #include "../../include/makisu_mi.h"
 #include "host_sha256.h"
+#include "host_blake2s.h"
 #include "mi_local.h"             // mi_batch_file_size, mi_last_error_of_batch
 #include "mi_filesum.h"           // the check of bytes that come back from HBM against the sums taken where they were read
 
@@ -996,11 +997,13 @@ int mi_cache_parse_entry_str(const char* entry, char* tar_digest, uint64_t tar_c
 }
 
 // chunk_root of a digest list on the host: the definition the kernels implement (tables.hip root
-// passes) -- SHA-256 over the concatenation when n <= 64, else a fan-out-64 tree.
+// passes) -- one hash over the concatenation when n <= 64, else a fan-out-64 tree; the
+// hash at every node is the ctx's chunk digest algorithm (MI_DIGEST_*).
 // For a file whose chunk rows come from several batches (parts): concatenate the parts' digests in
 // part order and call this; equals mi_file_result.chunk_root of the file scanned whole.
-int mi_chunk_root(const uint8_t* digests, uint64_t n, uint8_t* root_out) {
-    if ((!digests && n) || !root_out) return MI_ERR_INVALID;
+extern "C++" {
+template <class Hash>
+static void chunk_root_with(const uint8_t* digests, uint64_t n, uint8_t* root_out) {
     const uint64_t F = 64;
     std::vector<uint8_t> cur, next;
     const uint8_t* p = digests;
@@ -1009,7 +1012,7 @@ int mi_chunk_root(const uint8_t* digests, uint64_t n, uint8_t* root_out) {
         next.resize(m * 32);
         for (uint64_t g = 0; g < m; ++g) {
             const uint64_t cnt = n - g * F < F ? n - g * F : F;
-            mi_host::Sha256 h;
+            Hash h;
             h.update(p + g * F * 32, cnt * 32);
             h.final(&next[g * 32]);
         }
@@ -1017,10 +1020,19 @@ int mi_chunk_root(const uint8_t* digests, uint64_t n, uint8_t* root_out) {
         p = cur.data();
         n = m;
     }
-    mi_host::Sha256 h;
+    Hash h;
     h.update(p, n * 32);
     h.final(root_out);
+}
+}  // extern "C++"
+int mi_chunk_root_alg(uint32_t alg, const uint8_t* digests, uint64_t n, uint8_t* root_out) {
+    if ((!digests && n) || !root_out || alg > MI_DIGEST_BLAKE2S) return MI_ERR_INVALID;
+    if (alg == MI_DIGEST_BLAKE2S) chunk_root_with<mi_host::Blake2s>(digests, n, root_out);
+    else                          chunk_root_with<mi_host::Sha256>(digests, n, root_out);
     return MI_OK;
+}
+int mi_chunk_root(const uint8_t* digests, uint64_t n, uint8_t* root_out) {
+    return mi_chunk_root_alg(MI_DIGEST_SHA256, digests, n, root_out);
 }
 
 }  // extern "C"

@@ -56,6 +56,7 @@ MI_LOCAL int  mi_dedup_mark_range_enqueue(mi_ctx* c, const void* d_digests, uint
 // mi_index.hip: mi_index_add_batch for digests in host memory (a batch of another GPU than the index's)
 MI_LOCAL int  mi_index_add_digests(mi_index* index, const void* digests, uint64_t n, uint8_t* known_out, uint64_t* n_new, uint64_t* n_known);
 MI_LOCAL int  mi_index_same_ctx(mi_index* index, mi_batch* b);
+MI_LOCAL mi_ctx* mi_index_ctx(mi_index* index);   /* whose algorithm its digests are of (mi_ctx_chunk_digest) */
 // mi_tree.hip
 MI_LOCAL void mi_batch_tree_free(void* tree);
 }

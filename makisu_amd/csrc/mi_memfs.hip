@@ -167,6 +167,7 @@ extern "C" int mi_memfs_reset(mi_memfs* m) {                                    
     if (!m) return MI_ERR_INVALID;
     m->fs.t.root.children.clear();
     m->fs.t.shape_reset();
+    m->root_alg = -1;                                                             // (no roots left: a ctx of either algorithm may commit)
     return MI_OK;
 }
 

@@ -21,16 +21,13 @@
 // SIMD takes the longest quarter of the strings, the other(s) the rest (two ranges of
 // kShaQueues queues; whoever runs dry continues in the other range).
 #include "mi_common.h"
+#include "mi_item_loads.h"    // the load types and the quad-cooperative fetch (shared with blake2s.hip)
 
 #include <stdio.h>
 #include <stdlib.h>
 #include <vector>
 
 namespace mi {
-
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-typedef u32x4 u32x4_unaligned __attribute__((aligned(1)));
-typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 
 // kCoop: how a lane's next 64-byte block comes in.
 //   false  four byte-aligned 16-byte loads by the lane itself (64 lanes -> 64 pages per instruction,
@@ -45,11 +42,6 @@ typedef u32x4 u32x4_a4 __attribute__((aligned(4)));
 // and win 14 % on a 32 GB one (profiles/r02_sha_utcl1_and_load_alignment.txt), so the launcher
 // picks by the footprint of the strings.
 __device__ __forceinline__ u32 be_word(u32 hi, u32 lo, u32 sel) { return __builtin_amdgcn_perm(hi, lo, sel); }
-template <int kM>
-__device__ __forceinline__ u32 quad_bcast(u32 v) {            // value of lane (lane & ~3) + kM
-    return (u32)__builtin_amdgcn_update_dpp(0, (int)v, kM * 0x55, 0xF, 0xF, true);
-}
-constexpr int kXRow = 20;                                      // LDS row: 64 B of block + 16 B pad (dwords)
 
 __device__ __forceinline__ u32 rotr(u32 x, u32 n) { return __builtin_amdgcn_alignbit(x, x, n); }
 // gfx950 v_bitop3_b32: any 3-input boolean in ONE VALU op (truth table: a=0xF0, b=0xCC, c=0xAA)
@@ -147,21 +139,6 @@ __device__ __forceinline__ void block_words_coop(u32 (&w)[16], const u32x4& nx0,
     w[14] = be_word(nx3.z, nx3.y, sel); w[15] = be_word(nx3.w, nx3.z, sel);
     carry = nx3.w;
 }
-// every quad fetches the next blocks of its owners that want one (kAll: all four do), owner m's 64
-// bytes with ONE instruction; piece `sub` of owner qbase + m lands in g_m
-template <bool kAll>
-__device__ __forceinline__ void coop_fetch(u32x4& g0, u32x4& g1, u32x4& g2, u32x4& g3, const u8* ptr, bool want, int sub) {
-    const u32 wf = want ? 1u : 0u;
-    const u32 plo = (u32)(size_t)ptr, phi = (u32)((size_t)ptr >> 32);
-    const u32 l0 = quad_bcast<0>(plo), l1 = quad_bcast<1>(plo), l2 = quad_bcast<2>(plo), l3 = quad_bcast<3>(plo);
-    const u32 h0 = quad_bcast<0>(phi), h1 = quad_bcast<1>(phi), h2 = quad_bcast<2>(phi), h3 = quad_bcast<3>(phi);
-    const u64 mine = 16u * (u32)sub;                 // my 16-byte piece of every owner's block
-    if (kAll || quad_bcast<0>(wf)) g0 = *(const u32x4_a4*)(size_t)((((u64)h0 << 32) | l0) + mine);
-    if (kAll || quad_bcast<1>(wf)) g1 = *(const u32x4_a4*)(size_t)((((u64)h1 << 32) | l1) + mine);
-    if (kAll || quad_bcast<2>(wf)) g2 = *(const u32x4_a4*)(size_t)((((u64)h2 << 32) | l2) + mine);
-    if (kAll || quad_bcast<3>(wf)) g3 = *(const u32x4_a4*)(size_t)((((u64)h3 << 32) | l3) + mine);
-}
-
 // Lane pipeline (one iteration = one 64-byte compression per lane):
 //   cur  : the string being hashed: ptr/rem/total/slot, state st[8], and nx* = its NEXT
 //          64 bytes, loaded one iteration ahead so HBM latency hides under 64 rounds;
@@ -174,7 +151,6 @@ __device__ __forceinline__ void coop_fetch(u32x4& g0, u32x4& g1, u32x4& g2, u32x
 // string that does not start on a dword) -- never used; every buffer this is launched on carries
 // that slack (arena: 4 KiB; digest arrays and mi_sha256_many staging: DevBuf adds 256 bytes) and no
 // string starts unaligned at a buffer's first byte.
-constexpr u32 kLook = 5;
 
 // kPass only names the instantiation (chunk pass / root pass / ...) so profiles tell them apart.
 // kStats: the per-wave record of MI_SHA_WAVE_STATS (a second instantiation: its two counters cost two
@@ -507,21 +483,20 @@ void launch_sha256_items(ShaPass pass, const u8* d_base, const u64* d_off, const
         (void)hipMemsetAsync(d_heads, 0, sizeof(u32) * kShaHeadWords, s);
         if (d_roles) (void)hipMemsetAsync(d_roles, 0, sizeof(u32) * kShaRoleWords, s);
     }
-    const bool coop = pass != kShaRoots && footprint_bytes >= tune.coop_min_bytes;
-    int blocks_per_cu = tune.blocks_per_cu;
-    if (coop) blocks_per_cu = tune.coop_blocks_per_cu ? tune.coop_blocks_per_cu
-                            : footprint_bytes >= (24ull << 30) ? 3 : blocks_per_cu;   // enough work per lane for a third
     // The grid is blocks_per_cu x n_cu persistent workgroups -- but the dispatcher places by free
     // resources, and at 136 VGPRs a CU has room for THREE: some CUs take three workgroups and others one,
     // the waves of a crowded CU run at two thirds of the pace, and the launch ends with them (measured on
     // one box, same clocks: 4.13 ... 5.48 ms from launch to launch).  An LDS request of just over
     // 160 KiB / (blocks_per_cu + 1) per workgroup -- unused memory -- makes the intended placement the
-    // only possible one.
-    size_t lds_pad = 0;
+    // only possible one (sha_items_geometry, mi_common.h: shared with blake2s.hip).
     // (Only for the lane-owned scheme: the cooperative kernel's 161 VGPRs already cap a CU at three
     // workgroups, and pinned to two it ran SLOWER on a 6.5 GB arena -- 5.4 against 4.5 ms,
     // profiles/r03_sha_placement.txt -- so it is left to the dispatcher.)
-    if (tune.pin_blocks_per_cu && !coop && blocks_per_cu >= 1 && blocks_per_cu <= 3) {
+    const ShaGeometry geo = sha_items_geometry(pass, n, tune, n_cu, footprint_bytes, 3, 16);   // 16: the kernel's own static LDS
+    const bool coop = geo.coop;
+    const u32 grid = geo.grid;
+    const size_t lds_pad = geo.lds_pad;
+    if (geo.pinned) {
         static thread_local int attr_dev = -1;
         int dev = 0;
         (void)hipGetDevice(&dev);
@@ -533,16 +508,7 @@ void launch_sha256_items(ShaPass pass, const u8* d_base, const u64* d_off, const
 #undef MI_SHA_ATTR
             attr_dev = dev;
         }
-        const size_t per_wg = (160u * 1024u) / (size_t)(blocks_per_cu + 1) + 1024u;
-        const size_t fixed = coop ? (size_t)(kShaWG / 64) * 64 * kXRow * 4 : 16;     // the kernel's own static LDS
-        lds_pad = per_wg > fixed ? per_wg - fixed : 0;
     }
-    u64 want = ((u64)n + kShaWG - 1) / kShaWG;
-    u64 cap = (u64)blocks_per_cu * (u64)n_cu;
-    u32 grid = (u32)(want < cap ? want : cap);
-    // keep the grid a multiple of the queue count so every queue has the same number of pullers
-    if (grid >= (u32)kShaQueues) grid -= grid % kShaQueues;
-    if (grid == 0) grid = 1;
 #define MI_SHA_LAUNCH(P, C)                                                                   \
     hipLaunchKernelGGL((sha256_items_kernel<P, C>), dim3(grid), dim3(kShaWG), lds_pad, s, d_base, d_off, \
                        d_len, d_order, n, d_n, d_heads, d_roles, (u32)tune.long_shift | (tune.prio ? 0u : 0x100u), d_out, nullptr)
