@@ -17,6 +17,7 @@
 // What the two share without a branch -- the load types, the quad fetch, kLook -- is in mi_item_loads.h.
 #include "mi_common.h"
 #include "mi_item_loads.h"
+#include "mi_item_launch.h"
 
 namespace mi {
 
@@ -341,35 +342,23 @@ void blake2s_items_kernel(const u8* __restrict__ base, const u64* __restrict__ o
 void launch_blake2s_items(ShaPass pass, const u8* d_base, const u64* d_off, const u64* d_len,
                           const u32* d_order, u32 n, const u64* d_n, u32* d_heads, u32* d_roles, bool zero_heads,
                           u8* d_out, const ShaTune& tune, int n_cu, u64 footprint_bytes, hipStream_t s) {
-    if (n == 0) return;
-    if (!tune.roles) d_roles = nullptr;
-    if (zero_heads) {
-        (void)hipMemsetAsync(d_heads, 0, sizeof(u32) * kShaHeadWords, s);
-        if (d_roles) (void)hipMemsetAsync(d_roles, 0, sizeof(u32) * kShaRoleWords, s);
-    }
+    static thread_local int attr_dev = -1;
+    ShaGeometry geo;
+    u32 shift_flags;
     // up to FOUR workgroups per CU can be pinned: at 95 VGPRs five waves per SIMD fit; the lane-owned kernel has no static LDS
-    const ShaGeometry geo = sha_items_geometry(pass, n, tune, n_cu, footprint_bytes, 4, 0);
-    const bool coop = geo.coop;
-    const u32 grid = geo.grid;
-    const size_t lds_pad = geo.lds_pad;
-    if (geo.pinned) {
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (attr_dev != dev) {
-            (void)hipFuncSetAttribute((const void*)blake2s_items_kernel<kShaChunks, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            (void)hipFuncSetAttribute((const void*)blake2s_items_kernel<kShaRoots, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            attr_dev = dev;
-        }
-    }
-#define MI_B2S_LAUNCH(P, C)                                                                   \
-    hipLaunchKernelGGL((blake2s_items_kernel<P, C>), dim3(grid), dim3(kShaWG), lds_pad, s, d_base, d_off, \
-                       d_len, d_order, n, d_n, d_heads, d_roles, (u32)tune.long_shift | (tune.prio ? 0u : 0x100u), d_out)
+    if (!prepare_items_launch(geo, shift_flags, d_roles, pass, n, d_heads, zero_heads, tune, n_cu, footprint_bytes, 4, 0,
+                              {(const void*)blake2s_items_kernel<kShaChunks, false>, (const void*)blake2s_items_kernel<kShaRoots, false>},
+                              attr_dev, s))
+        return;
+#define MI_B2S_LAUNCH(P, C)                                                                              \
+    hipLaunchKernelGGL((blake2s_items_kernel<P, C>), dim3(geo.grid), dim3(kShaWG), geo.lds_pad, s, d_base, d_off, \
+                       d_len, d_order, n, d_n, d_heads, d_roles, shift_flags, d_out)
     if (pass == kShaRoots) MI_B2S_LAUNCH(kShaRoots, false);
-    else if (coop)         MI_B2S_LAUNCH(kShaChunks, true);
+    else if (geo.coop)     MI_B2S_LAUNCH(kShaChunks, true);
     else                   MI_B2S_LAUNCH(kShaChunks, false);
 #undef MI_B2S_LAUNCH
 }
+
 
 // ---- the VALU roof of this file's compression (mi_blake2s_valu_roof), as sha256_roof_kernel is SHA-256's ----------
 // ten rounds per lane and iteration over register data: no memory traffic, no queues, no tails
@@ -391,23 +380,9 @@ void blake2s_roof_kernel(u32* __restrict__ out, u32 blocks) {
     out[t] = r;
 }
 
-// bytes "hashed" per second by n_cu * waves_per_simd workgroups running `blocks` compressions per lane
 double measure_blake2s_valu_roof(int n_cu, int waves_per_simd, u32 blocks, u32* d_scratch, hipStream_t s,
                                  hipEvent_t e0, hipEvent_t e1) {
-    const u32 grid = (u32)(n_cu * waves_per_simd);                 // a workgroup = one wave on each of the CU's 4 SIMDs
-    hipLaunchKernelGGL(blake2s_roof_kernel, dim3(grid), dim3(kShaWG), 0, s, d_scratch, blocks / 8 + 1);   // clocks up
-    double best = 0;
-    for (int rep = 0; rep < 3; ++rep) {
-        (void)hipEventRecord(e0, s);
-        hipLaunchKernelGGL(blake2s_roof_kernel, dim3(grid), dim3(kShaWG), 0, s, d_scratch, blocks);
-        (void)hipEventRecord(e1, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return 0;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        const double rate = ms > 0 ? (double)grid * kShaWG * blocks * 64.0 / (ms * 1e-3) : 0;
-        best = rate > best ? rate : best;
-    }
-    return best;
+    return measure_valu_roof(blake2s_roof_kernel, n_cu, waves_per_simd, blocks, d_scratch, s, e0, e1);
 }
 
 }  // namespace mi

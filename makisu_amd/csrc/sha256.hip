@@ -22,6 +22,7 @@
 // kShaQueues queues; whoever runs dry continues in the other range).
 #include "mi_common.h"
 #include "mi_item_loads.h"    // the load types and the quad-cooperative fetch (shared with blake2s.hip)
+#include "mi_item_launch.h"   // what the two launchers and roof measurements share
 
 #include <stdio.h>
 #include <stdlib.h>
@@ -471,52 +472,37 @@ static void launch_sha256_chunks_recorded(bool coop, u32 grid, size_t lds_pad, c
     (void)hipFree(d_stats);
 }
 
-// With the TLB out of the way (cooperative loads) a third workgroup per CU pays (161 VGPRs: three
-// waves per SIMD fit): 26 GB arena 1.43 (byte loads, 2/CU) -> 1.57 (cooperative, 2/CU) -> 1.63 TB/s
-// (cooperative, 3/CU); on 6.5 GB three are slower with either scheme (coarser tail).
+// With the TLB out of the way (cooperative loads) a third workgroup per CU pays (161 VGPRs: three waves per SIMD fit):
+// 26 GB arena 1.43 (byte loads, 2/CU) -> 1.57 (cooperative, 2/CU) -> 1.63 TB/s (cooperative, 3/CU); on 6.5 GB three are
+// slower with either scheme (coarser tail).
 void launch_sha256_items(ShaPass pass, const u8* d_base, const u64* d_off, const u64* d_len,
                          const u32* d_order, u32 n, const u64* d_n, u32* d_heads, u32* d_roles, bool zero_heads,
                          u8* d_out, const ShaTune& tune, int n_cu, u64 footprint_bytes, hipStream_t s) {
-    if (n == 0) return;
-    if (!tune.roles) d_roles = nullptr;
-    if (zero_heads) {
-        (void)hipMemsetAsync(d_heads, 0, sizeof(u32) * kShaHeadWords, s);
-        if (d_roles) (void)hipMemsetAsync(d_roles, 0, sizeof(u32) * kShaRoleWords, s);
-    }
-    // The grid is blocks_per_cu x n_cu persistent workgroups -- but the dispatcher places by free
-    // resources, and at 136 VGPRs a CU has room for THREE: some CUs take three workgroups and others one,
-    // the waves of a crowded CU run at two thirds of the pace, and the launch ends with them (measured on
-    // one box, same clocks: 4.13 ... 5.48 ms from launch to launch).  An LDS request of just over
-    // 160 KiB / (blocks_per_cu + 1) per workgroup -- unused memory -- makes the intended placement the
-    // only possible one (sha_items_geometry, mi_common.h: shared with blake2s.hip).
-    // (Only for the lane-owned scheme: the cooperative kernel's 161 VGPRs already cap a CU at three
-    // workgroups, and pinned to two it ran SLOWER on a 6.5 GB arena -- 5.4 against 4.5 ms,
-    // profiles/r03_sha_placement.txt -- so it is left to the dispatcher.)
-    const ShaGeometry geo = sha_items_geometry(pass, n, tune, n_cu, footprint_bytes, 3, 16);   // 16: the kernel's own static LDS
+    // The grid is blocks_per_cu x n_cu persistent workgroups -- but the dispatcher places by free resources, and at 136
+    // VGPRs a CU has room for THREE: some CUs take three workgroups and others one, the waves of a crowded CU run at two
+    // thirds of the pace, and the launch ends with them (measured on one box, same clocks: 4.13 ... 5.48 ms from launch to
+    // launch).  Hence the LDS pad of sha_items_geometry (mi_common.h) -- only for the lane-owned scheme: the cooperative
+    // kernel's 161 VGPRs already cap a CU at three workgroups, and pinned to two it ran SLOWER on a 6.5 GB arena -- 5.4
+    // against 4.5 ms, profiles/r03_sha_placement.txt -- so it is left to the dispatcher.
+    static thread_local int attr_dev = -1;
+    ShaGeometry geo;
+    u32 shift_flags;
+#define MI_SHA_K(...) (const void*)sha256_items_kernel<__VA_ARGS__>
+    if (!prepare_items_launch(geo, shift_flags, d_roles, pass, n, d_heads, zero_heads, tune, n_cu, footprint_bytes, 3, 16,   // 16: the kernel's own static LDS
+                              {MI_SHA_K(kShaChunks, false), MI_SHA_K(kShaChunks, true), MI_SHA_K(kShaRoots, false),
+                               MI_SHA_K(kShaChunks, false, true), MI_SHA_K(kShaFiles, false), MI_SHA_K(kShaFiles, true),
+                               MI_SHA_K(kShaBlobs, false), MI_SHA_K(kShaBlobs, true)}, attr_dev, s))
+        return;
+#undef MI_SHA_K
     const bool coop = geo.coop;
-    const u32 grid = geo.grid;
-    const size_t lds_pad = geo.lds_pad;
-    if (geo.pinned) {
-        static thread_local int attr_dev = -1;
-        int dev = 0;
-        (void)hipGetDevice(&dev);
-        if (attr_dev != dev) {
-#define MI_SHA_ATTR(P, C) (void)hipFuncSetAttribute((const void*)sha256_items_kernel<P, C>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024)
-            MI_SHA_ATTR(kShaChunks, false); MI_SHA_ATTR(kShaChunks, true); MI_SHA_ATTR(kShaRoots, false);
-            (void)hipFuncSetAttribute((const void*)sha256_items_kernel<kShaChunks, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-            MI_SHA_ATTR(kShaFiles, false); MI_SHA_ATTR(kShaFiles, true); MI_SHA_ATTR(kShaBlobs, false); MI_SHA_ATTR(kShaBlobs, true);
-#undef MI_SHA_ATTR
-            attr_dev = dev;
-        }
-    }
-#define MI_SHA_LAUNCH(P, C)                                                                   \
-    hipLaunchKernelGGL((sha256_items_kernel<P, C>), dim3(grid), dim3(kShaWG), lds_pad, s, d_base, d_off, \
-                       d_len, d_order, n, d_n, d_heads, d_roles, (u32)tune.long_shift | (tune.prio ? 0u : 0x100u), d_out, nullptr)
+#define MI_SHA_LAUNCH(P, C)                                                                                 \
+    hipLaunchKernelGGL((sha256_items_kernel<P, C>), dim3(geo.grid), dim3(kShaWG), geo.lds_pad, s, d_base, d_off, \
+                       d_len, d_order, n, d_n, d_heads, d_roles, shift_flags, d_out, nullptr)
     switch (pass) {
         case kShaChunks:
             if (tune.wave_stats_path) {      // diagnostics, per ctx (mi_debug_sha_wave_stats): the recording instantiation
-                launch_sha256_chunks_recorded(coop, grid, lds_pad, d_base, d_off, d_len, d_order, n, d_n, d_heads, d_roles,
-                                              (u32)tune.long_shift | (tune.prio ? 0u : 0x100u), d_out, tune.wave_stats_path, s);
+                launch_sha256_chunks_recorded(coop, geo.grid, geo.lds_pad, d_base, d_off, d_len, d_order, n, d_n, d_heads, d_roles,
+                                              shift_flags, d_out, tune.wave_stats_path, s);
                 break;
             }
             if (coop) MI_SHA_LAUNCH(kShaChunks, true); else MI_SHA_LAUNCH(kShaChunks, false);
@@ -550,23 +536,9 @@ void sha256_roof_kernel(u32* __restrict__ out, u32 blocks) {
     out[t] = r;
 }
 
-// bytes "hashed" per second by n_cu * waves_per_simd workgroups running `blocks` compressions per lane
 double measure_sha_valu_roof(int n_cu, int waves_per_simd, u32 blocks, u32* d_scratch, hipStream_t s,
                              hipEvent_t e0, hipEvent_t e1) {
-    const u32 grid = (u32)(n_cu * waves_per_simd);                 // a workgroup = one wave on each of the CU's 4 SIMDs
-    hipLaunchKernelGGL(sha256_roof_kernel, dim3(grid), dim3(kShaWG), 0, s, d_scratch, blocks / 8 + 1);   // clocks up
-    double best = 0;
-    for (int rep = 0; rep < 3; ++rep) {
-        (void)hipEventRecord(e0, s);
-        hipLaunchKernelGGL(sha256_roof_kernel, dim3(grid), dim3(kShaWG), 0, s, d_scratch, blocks);
-        (void)hipEventRecord(e1, s);
-        if (hipStreamSynchronize(s) != hipSuccess) return 0;
-        float ms = 0;
-        (void)hipEventElapsedTime(&ms, e0, e1);
-        const double rate = ms > 0 ? (double)grid * kShaWG * blocks * 64.0 / (ms * 1e-3) : 0;
-        best = rate > best ? rate : best;
-    }
-    return best;
+    return measure_valu_roof(sha256_roof_kernel, n_cu, waves_per_simd, blocks, d_scratch, s, e0, e1);
 }
 
 }  // namespace mi

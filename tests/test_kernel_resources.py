@@ -70,6 +70,9 @@ def test_hot_kernels_keep_their_occupancy_step(usage):
         assert u["LDS Size [bytes/block]"] == (20480 if coop else 0), (name, u)
     lane = [u["VGPRs"] for n, u in usage.items() if re.match(r"mi::sha256_items_kernel<\d+, false, false>", n)]
     assert lane and max(lane) <= 144                              # the lane-owned form: where it has been since round 3 (135)
+    # the figures any fold of this loop with blake2s.hip's has to keep: not a register more in either form
+    coop = [u["VGPRs"] for n, u in usage.items() if re.match(r"mi::sha256_items_kernel<\d+, true, false>", n)]
+    assert max(lane) <= 135 and coop and max(coop) <= 161, (lane, coop)
     # Gear marking, bitmap-free kernels (4.1): 512-thread workgroups, two per CU = 4 waves per SIMD -> <= 128 VGPRs;
     # their 32 table copies are dynamic LDS (requested at launch), no static LDS
     for prefix in ("mi::gear_cdc_small_fast_kernel", "mi::gear_tile_mark_kernel"):
@@ -109,3 +112,10 @@ def test_sha256_instruction_count_is_at_its_floor(tmp_path):
     assert valu(roof) <= 1460, valu(roof)                         # 1 450: the compression + the benchmark's loop
     assert valu(chunk) <= 1760, valu(chunk)                       # 1 734: + loads, byte swaps, padding, the dequeue, the store
     assert chunk["v_mov_b32_e32"] <= 90                           # no copying of state or schedule words around the block loop
+    assert valu(chunk) <= 1734, valu(chunk)                       # ... nor an instruction
+    # s_waitcnt instructions that name vmcnt: three per non-recording item kernel, one of them the loop top's own -- one
+    # more is a wait on memory that hipcc has put somewhere in the iteration
+    items = {k: f for k, f in ((re.match(r"[0-9a-f]+ <(\S+)>:", f), f) for f in re.split(r"\n(?=[0-9a-f]+ <)", asm)) if k}
+    waits = {k.group(1): len(re.findall(r"s_waitcnt[^\n/]*vmcnt", f)) for k, f in items.items()
+             if re.search(r"sha256_items_kernelILi\dELb[01]ELb0E", k.group(1))}
+    assert len(waits) == 7 and set(waits.values()) == {3}, waits

@@ -38,6 +38,8 @@ def test_blake2s_kernels_keep_their_occupancy_step(usage):
         coop = name.endswith(", true>")
         assert u["VGPRs"] <= 128 and u["Occupancy [waves/SIMD]"] >= 4, (name, u)
         assert u["LDS Size [bytes/block]"] == (20480 if coop else 0), (name, u)
+        # the figures any fold of this loop with sha256.hip's has to keep: not a register more
+        assert u["VGPRs"] <= (122 if coop else 95), (name, u)
     assert usage["mi::blake2s_roof_kernel"]["Occupancy [waves/SIMD]"] == 8           # the roof is measured at up to 8 waves per SIMD
 
 
@@ -56,7 +58,7 @@ def _mixes(tmp_path):
             # what a wave can execute: up to the LAST s_endpgm (behind it the assembler pads the code object with s_nop)
             body, _, pad = f.rpartition("s_endpgm")
             mix[m.group(1)] = (collections.Counter(mm.group(1) for mm in re.finditer(r"^\s+([vs]_\w+)", body, re.M)),
-                               len(re.findall(r"\bs_nop\b", pad)))
+                               len(re.findall(r"\bs_nop\b", pad)), len(re.findall(r"s_waitcnt[^\n/]*vmcnt", body)))
     return mix
 
 
@@ -71,9 +73,9 @@ def test_blake2s_instruction_count_is_at_its_floor(tmp_path):
     pipeline, the dequeue and the store = 1 222 as compiled (the cooperative form: 1 286 with its 16 v_perm_b32 and the
     quad broadcasts)."""
     mix = _mixes(tmp_path)
-    roof, roof_pad = next(v for k, v in mix.items() if "blake2s_roof_kernel" in k)
-    chunk, _ = next(v for k, v in mix.items() if "blake2s_items_kernelILi0ELb0E" in k)
-    coop, _ = next(v for k, v in mix.items() if "blake2s_items_kernelILi0ELb1E" in k)
+    roof, roof_pad, _ = next(v for k, v in mix.items() if "blake2s_roof_kernel" in k)
+    chunk, _, _ = next(v for k, v in mix.items() if "blake2s_items_kernelILi0ELb0E" in k)
+    coop, _, _ = next(v for k, v in mix.items() if "blake2s_items_kernelILi0ELb1E" in k)
     valu = lambda c: sum(n for k, n in c.items() if k.startswith("v_"))                                   # noqa: E731
     for c in (roof, chunk, coop):
         assert c["v_alignbit_b32"] == 320 and c["v_add3_u32"] >= 160 and c["v_add3_u32"] <= 164, c
@@ -81,7 +83,12 @@ def test_blake2s_instruction_count_is_at_its_floor(tmp_path):
     assert valu(roof) <= 1040, valu(roof)                          # 1 035
     assert valu(chunk) <= 1235, valu(chunk)                        # 1 222
     assert valu(coop) <= 1300, valu(coop)                          # 1 286
+    assert valu(chunk) <= 1222 and valu(coop) <= 1286              # ... nor an instruction
     assert coop["v_perm_b32"] == 16 and chunk["v_perm_b32"] == 0   # the realignment; lane-owned loads ARE the message words
+    # s_waitcnt instructions that name vmcnt: three per item kernel, one of them the loop top's own -- one more is a wait on
+    # memory that hipcc has put somewhere in the iteration
+    waits = {k: v[2] for k, v in mix.items() if "blake2s_items_kernel" in k}
+    assert len(waits) == 3 and set(waits.values()) == {3}, waits
     # s_nop.  The 250-odd of a plain compile of the compression are NOT hazard pads: they stand behind s_endpgm, where the
     # assembler fills the code object up to its alignment, and no wave reaches them.  The compression itself has none ...
     assert roof["s_nop"] == 0 and roof_pad >= 1, (roof["s_nop"], roof_pad)
