@@ -900,6 +900,14 @@ MI_CORE int  mi_memfs_commit_stats(const mi_memfs* fs, mi_commit_stats* out);
  * whole tree; the layer, the roots and the DigestPair are the same unless the kernel's timestamps lie (a clock set back
  * between a write and the next one to the same file).  Scan commits only.                                               */
 #define MI_MEMFS_TRUST_CTIME 0x1u
+/* MI_MEMFS_CHUNK_PACK: a content-aware scan or copy commit on ONE ctx, with an index set, also packs exactly the rows whose
+ * bytes index_new_bytes counts (known[i] == 0 and dup_of < 0) -- mi_batch_pack_chunks with MI_PACK_VERIFY, after the index took
+ * the batch, while the handle's batch still holds the tree's bytes -- and keeps every layer file's ordered chunks (its recipe:
+ * mi_copy_layer_chunks).  mi_memfs_take_pack hands the pack over.  With the option and no index the commit fails with
+ * MI_ERR_STATE, with mi_memfs_commit_layer_n and n_ctx > 1 with MI_ERR_INVALID, both before anything is walked.  A commit in
+ * windows (n_windows > 0) succeeds as before and has no pack (take: MI_ERR_STATE); a pack that cannot be built (MI_ERR_NOMEM) does
+ * not fail the commit -- the layer is written -- and the take returns the error.  Without the option nothing changes.       */
+#define MI_MEMFS_CHUNK_PACK 0x2u
 MI_CORE int  mi_memfs_set_options(mi_memfs* fs, uint32_t options);
 /* From now on every content-aware commit of this handle adds its batch to `index` (NULL: stop).  The index must belong
  * to the ctx the commits run on and outlive them; the handle does not own it.                                          */
@@ -982,6 +990,63 @@ MI_BLOCK int  mi_index_add_batch(mi_index* index, mi_batch* b, uint8_t* known, u
                         uint64_t* n_new, uint64_t* n_known);
 MI_CORE int  mi_index_export(mi_index* index, void* out_digests, uint64_t cap_digests);
 MI_CORE int  mi_index_import(mi_index* index, const void* digests, uint64_t n, uint64_t* n_new);
+
+/* ---- chunk packs: a batch's selected chunks as ONE blob, gathered on the device ---------------------- *
+ * mi_index_add_batch says which chunks of a layer no earlier layer held, mi_commit_stats.index_new_bytes counts their
+ * bytes; a pack DELIVERS them: what a chunk-addressed store behind keyvalue.Store (lib/cache/keyvalue/store.go:22-26) takes
+ * in for a layer, next to the files' recipes (their ordered chunk digests: mi_batch_chunks).  The reference has no
+ * counterpart: its unit is the layer blob (lib/builder/step/common.go:88-91).
+ *   mi_batch_pack_chunks  select: n_select flags in host memory, n_select = the batch's chunk count; NULL = every row.  Rows
+ *                         with a non-zero flag go in, in ascending row order -- duplicates too if the caller selects them.
+ *                         Entry k begins at the sum of the lengths before it, each rounded up to 16; the pad bytes behind a
+ *                         chunk are zero: the blob is a pure function of the rows and their bytes.  The batch must have run
+ *                         and not be in flight (MI_ERR_STATE); a group head (mi_memfs_commit_layer_n's batch) and a wrong
+ *                         n_select are MI_ERR_INVALID; part rows are rows like any other; an empty selection is a valid pack
+ *                         of 0 entries.  The blob lives in device memory of its own: if it does not fit, MI_ERR_NOMEM naming
+ *                         both sizes, nothing else has changed, and the caller may pack in several calls with partial
+ *                         selections.  A pack points at its ctx (free it before mi_ctx_destroy, which refuses while one
+ *                         lives) but not at its batch: it survives mi_batch_reset and mi_batch_free.
+ *                         MI_PACK_VERIFY: the blob's entries are hashed again on the device (the ctx's algorithm) and held
+ *                         against the batch's digests; one differing row fails the call with MI_ERR_IO naming the row, its
+ *                         arena offset and its blob offset, and no pack is returned.
+ *   mi_pack_entries       the entries in blob order (cap = rows `out` has room for).
+ *   mi_pack_read          bytes [offset, offset + len) of the blob through two pinned windows of the pack's own (8 MiB each:
+ *                         a reader that streams finds the next window on its way); outside the blob: MI_ERR_INVALID.
+ *   mi_pack_device        the blob where it lies (valid until mi_pack_free); NULL for an empty pack.
+ *   mi_pack_check         host logic, no ctx, no GPU -- what the pulling side runs before it trusts a pack: the entries lie
+ *                         inside the blob on 16-byte offsets, ascending, without overlap; the pad bytes are zero; every chunk
+ *                         hashes to its digest under alg (MI_DIGEST_*).  MI_OK, or MI_ERR_INVALID with *first_bad = the
+ *                         first entry that fails (an unknown alg: MI_ERR_INVALID).                                    */
+#define MI_PACK_VERIFY 0x1u
+typedef struct mi_pack mi_pack;
+typedef struct {               /* 56 bytes */
+    uint8_t  digest[32];       /* the row's chunk digest (the ctx's algorithm) */
+    uint64_t offset;           /* where the chunk begins in the blob: a multiple of 16 */
+    uint64_t chunk_index;      /* the row in the batch's chunk table */
+    uint32_t length;           /* bytes */
+    uint32_t reserved;         /* 0 */
+} mi_pack_entry;
+typedef struct {
+    uint64_t n_entries, blob_bytes, chunk_bytes;   /* blob_bytes = sum of lengths rounded up to 16 */
+    uint32_t alg;              /* MI_DIGEST_* of the ctx that made it */
+    uint32_t verified;         /* 1: the blob was hashed again on the device and every digest agreed */
+    double   ms_gather, ms_verify;
+} mi_pack_info;
+MI_BLOCK int  mi_batch_pack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select, uint32_t flags, mi_pack** out);
+MI_BLOCK int  mi_pack_get_info(const mi_pack* p, mi_pack_info* out);
+MI_BLOCK int  mi_pack_entries(const mi_pack* p, mi_pack_entry* out, uint64_t cap);
+MI_BLOCK int  mi_pack_read(mi_pack* p, uint64_t offset, void* dst, uint64_t len);
+MI_BLOCK int  mi_pack_device(const mi_pack* p, const void** d_blob, uint64_t* blob_bytes);
+MI_BLOCK void mi_pack_free(mi_pack* p);
+MI_BLOCK int  mi_pack_check(const void* blob, uint64_t blob_bytes, const mi_pack_entry* entries, uint64_t n,
+                   uint32_t alg, uint64_t* first_bad);
+/* the pack of the handle's last commit (MI_MEMFS_CHUNK_PACK); the caller owns it (mi_pack_free).  MI_ERR_STATE with no commit
+ * since the last take, and after a commit in windows; the pack's own error if it could not be built (mi_memfs_error says why) */
+MI_BLOCK int mi_memfs_take_pack(mi_memfs* fs, mi_pack** out);
+/* the ordered chunks of layer entry `entry` (mi_copy_layer_entries' order): digests n x 32 bytes, lengths n x u32;
+   cap 0 sizes; regular files of a commit made with the option, *n = 0 for everything else */
+MI_BLOCK int mi_copy_layer_chunks(const mi_copy_layer* layer, uint64_t entry, uint8_t* digests, uint32_t* lengths,
+                                  uint64_t cap, uint64_t* n);
 
 #ifdef __cplusplus
 }

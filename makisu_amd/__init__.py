@@ -17,7 +17,8 @@ from . import build as _build
 __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE", "CHUNK_DTYPE",
            "FLAG_FILE_SHA256", "FLAG_FILE_CRC32", "FLAG_NO_DEDUP", "FLAG_PREFETCH_ROWS", "FLAG_VERIFY_STAGING", "FLAG_FILE_SUMS",
            "FLAG_CHUNK_BLAKE2S", "DIGEST_SHA256", "DIGEST_BLAKE2S", "chunk_root",
-           "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex"]
+           "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex",
+           "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -104,6 +105,23 @@ class LayerConfig(C.Structure):
 
 LAYER_MODE_WITH_TYPE = 0x1
 MEMFS_TRUST_CTIME = 0x1
+MEMFS_CHUNK_PACK = 0x2                   # a commit also packs the chunks its index did not know (MemFS.take_pack) and keeps the recipes
+PACK_VERIFY = 0x1                        # mi_batch_pack_chunks: hash the blob again on the device
+
+
+class PackEntry(C.Structure):
+    """mi_pack_entry: one chunk of a pack."""
+    _fields_ = [("digest", C.c_uint8 * 32), ("offset", C.c_uint64), ("chunk_index", C.c_uint64),
+                ("length", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class PackInfo(C.Structure):
+    """mi_pack_info."""
+    _fields_ = [("n_entries", C.c_uint64), ("blob_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64),
+                ("alg", C.c_uint32), ("verified", C.c_uint32), ("ms_gather", C.c_double), ("ms_verify", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
 
 
 class LayerResult(C.Structure):
@@ -183,6 +201,7 @@ def _np_dtype(struct):
 
 FILE_DTYPE = _np_dtype(_FileResult)
 CHUNK_DTYPE = _np_dtype(_ChunkResult)
+PACK_ENTRY_DTYPE = _np_dtype(PackEntry)
 
 _lib = None
 
@@ -330,6 +349,15 @@ def load_library(rebuild=False):
         "mi_index_add_batch": ([vp, vp, vp, u64, u64p, u64p], C.c_int),
         "mi_index_export": ([vp, vp, u64], C.c_int),
         "mi_index_import": ([vp, vp, u64, u64p], C.c_int),
+        "mi_batch_pack_chunks": ([vp, vp, u64, C.c_uint32, C.POINTER(vp)], C.c_int),
+        "mi_pack_get_info": ([vp, C.POINTER(PackInfo)], C.c_int),
+        "mi_pack_entries": ([vp, vp, u64], C.c_int),
+        "mi_pack_read": ([vp, u64, vp, u64], C.c_int),
+        "mi_pack_device": ([vp, C.POINTER(vp), u64p], C.c_int),
+        "mi_pack_free": ([vp], None),
+        "mi_pack_check": ([vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
+        "mi_memfs_take_pack": ([vp, C.POINTER(vp)], C.c_int),
+        "mi_copy_layer_chunks": ([vp, u64, vp, vp, u64, u64p], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -582,9 +610,10 @@ def _copy_op_array(ops, keep):
     return cops
 
 
-def _take_copy_layer(L, h, n):
+def _take_copy_layer(L, h, n, chunks=False):
     """mi_copy_layer -> list of entry dicts (commit order) with an extra "src" key and, for regular files of a
-    content-aware commit, "root" (32 bytes); frees the handle."""
+    content-aware commit, "root" (32 bytes); chunks: the layer of a handle with MEMFS_CHUNK_PACK, whose regular files also
+    get "chunks", their recipes (asked for only then: two more calls per entry); frees the handle."""
     try:
         out = (TreeEntry * max(n, 1))()
         srcp = (C.c_char_p * max(n, 1))()
@@ -602,6 +631,18 @@ def _take_copy_layer(L, h, n):
             d["src"] = os.fsdecode(srcp[i]) if srcp[i] is not None else ""
             if has[i]:
                 d["root"] = roots[i].tobytes()
+            nc = C.c_uint64()
+            if chunks:
+                rc = L.mi_copy_layer_chunks(h, i, None, None, 0, C.byref(nc))
+                if rc:
+                    raise MiError(rc, "mi_copy_layer_chunks")
+            if nc.value:                                      # the file's recipe
+                dg = np.zeros((nc.value, 32), dtype=np.uint8)
+                ln = np.zeros(nc.value, dtype=np.uint32)
+                rc = L.mi_copy_layer_chunks(h, i, dg.ctypes.data, ln.ctypes.data, nc.value, C.byref(nc))
+                if rc:
+                    raise MiError(rc, "mi_copy_layer_chunks")
+                d["chunks"] = [(dg[k].tobytes(), int(ln[k])) for k in range(nc.value)]
             res.append(d)
         return res
     finally:
@@ -647,6 +688,8 @@ class MemFS:
         if rc:
             raise MiError(rc, "mi_memfs_create: unable to stat root dir: %s" % root)
         self.root, self.blacklist = root, list(blacklist)
+        self._chunk_pack = False                              # set_options(chunk_pack=True)
+        self._pack_engine = None                              # the Engine of the last commit that could make a pack: take_pack's Pack is its child
 
     def _check(self, rc, what):
         if rc:
@@ -735,6 +778,8 @@ class MemFS:
                                                           C.byref(res), hp, C.byref(done)), "mi_memfs_commit_layer_n")
         else:
             ctx = engine._h if engine is not None else None
+            if engine is not None and self._chunk_pack:
+                self._pack_engine = engine                    # only such a commit makes (or drops) the handle's pack
             if engine is not None:
                 engine._children.add(self)                    # the handle keeps a batch of that ctx: given back before it dies
             self._check(self._lib.mi_memfs_commit_layer(self._h, ctx, int(must_scan), cops, len(ops), C.byref(cfg), C.byref(res),
@@ -743,7 +788,7 @@ class MemFS:
             return None
         return {"tar_digest": Digest.from_raw(res.tar_sha256), "gzip_digest": Digest.from_raw(res.gzip_sha256),
                 "tar_bytes": res.tar_bytes, "gzip_bytes": res.gzip_bytes, "n_entries": res.n_entries,
-                "layer": _take_copy_layer(self._lib, h, int(res.n_entries)) if want_layer else None, "stats": self.commit_stats()}
+                "layer": _take_copy_layer(self._lib, h, int(res.n_entries), self._chunk_pack) if want_layer else None, "stats": self.commit_stats()}
 
     def commit_stats(self):
         st = CommitStats()
@@ -760,9 +805,19 @@ class MemFS:
         engine._children.add(self)
         self._check(self._lib.mi_memfs_reserve_device(self._h, engine._h, files, nbytes), "mi_memfs_reserve_device")
 
-    def set_options(self, trust_ctime=False):
-        """MI_MEMFS_TRUST_CTIME: scan commits do not read files again whose inode is what it was when they were hashed"""
-        self._check(self._lib.mi_memfs_set_options(self._h, MEMFS_TRUST_CTIME if trust_ctime else 0), "mi_memfs_set_options")
+    def set_options(self, trust_ctime=False, chunk_pack=False):
+        """MI_MEMFS_TRUST_CTIME: scan commits do not read files again whose inode is what it was when they were hashed.
+        MI_MEMFS_CHUNK_PACK: a commit (one Engine, an index set) also packs the chunks the index did not know -- take_pack() --
+        and its layer's regular files carry "chunks": [(digest, length), ...], their recipes"""
+        self._check(self._lib.mi_memfs_set_options(self._h, (MEMFS_TRUST_CTIME if trust_ctime else 0) | (MEMFS_CHUNK_PACK if chunk_pack else 0)),
+                    "mi_memfs_set_options")
+        self._chunk_pack = bool(chunk_pack)
+
+    def take_pack(self):
+        """mi_memfs_take_pack: the Pack of the last commit made with chunk_pack, a child of the Engine that commit ran on"""
+        h = C.c_void_p()
+        self._check(self._lib.mi_memfs_take_pack(self._h, C.byref(h)), "mi_memfs_take_pack")
+        return Pack(self._pack_engine, h)
 
     def release_device(self):
         if self._h:
@@ -985,6 +1040,75 @@ class ChunkIndex:
 
     def __exit__(self, *exc):
         self.close()
+
+
+class Pack:
+    """mi_pack_*: selected chunks of a batch as one blob in device memory (Batch.pack, MemFS.take_pack).  A child of its
+    Engine, independent of the batch it came from."""
+
+    def __init__(self, engine, handle):
+        self._eng = engine
+        self._lib = engine._lib
+        self._h = handle
+        engine._children.add(self)
+
+    @property
+    def info(self):
+        out = PackInfo()
+        self._eng._check(self._lib.mi_pack_get_info(self._h, C.byref(out)))
+        return out
+
+    def __len__(self):
+        return self.info.n_entries
+
+    def entries(self):
+        """the entries in blob order: a numpy array of PACK_ENTRY_DTYPE"""
+        n = self.info.n_entries
+        out = np.zeros(max(n, 1), dtype=PACK_ENTRY_DTYPE)
+        self._eng._check(self._lib.mi_pack_entries(self._h, out.ctypes.data, n))
+        return out[:n]
+
+    def read(self, offset, length):
+        out = np.zeros(max(length, 1), dtype=np.uint8)
+        self._eng._check(self._lib.mi_pack_read(self._h, offset, out.ctypes.data, length))
+        return out[:length].tobytes()
+
+    def bytes(self):
+        """the whole blob"""
+        return self.read(0, self.info.blob_bytes)
+
+    def device(self):
+        p, n = C.c_void_p(), C.c_uint64()
+        self._eng._check(self._lib.mi_pack_device(self._h, C.byref(p), C.byref(n)))
+        return p.value, n.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mi_pack_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+def pack_check(blob, entries, alg=DIGEST_SHA256):
+    """mi_pack_check (host logic, no GPU): None if the pack is sound, else the index of the first entry that is not -- off the
+    16-byte grid, overlapping, past the end, a non-zero pad byte, a chunk that does not hash to its digest; an unknown alg
+    raises."""
+    if alg not in (DIGEST_SHA256, DIGEST_BLAKE2S):
+        raise MiError(-1, "mi_pack_check: unknown digest algorithm %r" % (alg,))
+    b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+    e = np.ascontiguousarray(entries, dtype=PACK_ENTRY_DTYPE)
+    bad = C.c_uint64()
+    rc = load_library().mi_pack_check(b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size, alg,
+                                      C.byref(bad))
+    return None if rc == 0 else bad.value
 
 
 def default_config(**overrides):
@@ -1322,6 +1446,18 @@ class Batch:
         p, n = C.c_void_p(), C.c_uint64()
         self._check(self._lib.mi_batch_device_digests(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
+
+    def pack(self, select=None, verify=False):
+        """mi_batch_pack_chunks: the rows with a non-zero flag in `select` (one per chunk row; None = every row) gathered
+        into one blob on the device -> Pack"""
+        h = C.c_void_p()
+        ptr, n = None, 0
+        if select is not None:
+            sel = np.zeros(max(len(select), 1), dtype=np.uint8)      # (never NULL: NULL means every row)
+            sel[:len(select)] = np.asarray(select) != 0
+            ptr, n = sel.ctypes.data, len(select)
+        self._check(self._lib.mi_batch_pack_chunks(self._h, ptr, n, PACK_VERIFY if verify else 0, C.byref(h)))
+        return Pack(self.engine, h)
 
     def add_tree(self, root, rel_base=None, blacklist=(), mode=TREE_CONTEXT):
         """Walk `root` the way the reference does (filepath.Walk order) and add its regular

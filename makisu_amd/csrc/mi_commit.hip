@@ -30,7 +30,15 @@ static uint64_t commit_window_bytes(bool* given) {
 
 // ---- the handle's batch: ONE record of the ctxs it was made for, these two functions its only writers ------------------
 // the commit's batch (its arena holds the last scanned tree's bytes) is given back; the next content-aware commit begins anew
+// MI_MEMFS_CHUNK_PACK: a pack nobody took goes; until the next commit's pack a take says `why` with `rc`
+static void memfs_pack_drop(mi_memfs* m, int rc, const std::string& why) {
+    if (m->pack) mi_pack_free(m->pack);
+    m->pack = nullptr;
+    m->pack_rc = rc;
+    m->pack_err = why;
+}
 static int memfs_batch_drop(mi_memfs* m) {
+    memfs_pack_drop(m, MI_ERR_STATE, "no commit since the device was released");      // (a pack is a child of the ctx, as the batch is)
     int rc = MI_OK;
     if (m->batch) rc = mi_batch_free(m->batch);
     m->batch = nullptr;
@@ -448,10 +456,46 @@ struct Commit {
                     for (uint64_t i = 0; i < nc; ++i)
                         if (!known[i] && rows[i].dup_of < 0) m->last.index_new_bytes += rows[i].length;
                 }
+                if (!rc && m->chunk_pack && !windowed) pack_and_recipes(mb, rows, nc, known.data());     // (one ctx: one member)
             }
             if (rc) m->err = std::string("failed to generate diff layer: chunk index: ") + mi_last_error(ctx);
+        } else if (b && m->chunk_pack && !windowed) {                             // nothing was scanned: a pack of nothing
+            mi_pack* p = nullptr;
+            const int prc = mi_pack_empty(ctx, &p);
+            memfs_pack_drop(m, prc, prc ? "the empty pack of a commit that scanned nothing" : "");
+            m->pack = p;
+            cl->chunk_first.assign(cl->nodes.size() + 1, 0);
         }
+        if (b && m->chunk_pack && windowed)
+            memfs_pack_drop(m, MI_ERR_STATE, "the last commit's tree did not fit the device and was scanned in " + std::to_string(m->last.n_windows) +
+                                             " windows: no batch holds its bytes, there is no pack (packs window by window are not built)");
         return rc;
+    }
+    // MI_MEMFS_CHUNK_PACK: the rows whose bytes index_new_bytes counts as ONE blob (mi_batch_pack_chunks with MI_PACK_VERIFY: the
+    // batch still holds the tree's bytes), and every layer file's ordered chunks.  A pack that cannot be built does not fail the
+    // commit -- the layer is written: mi_memfs_take_pack returns the error and the message.
+    void pack_and_recipes(mi_batch* mb, const mi_chunk_result* rows, uint64_t nc, const uint8_t* known) {
+        std::vector<uint8_t> select(nc ? nc : 1);
+        for (uint64_t i = 0; i < nc; ++i) select[i] = !known[i] && rows[i].dup_of < 0;
+        mi_pack* p = nullptr;
+        const int prc = mi_batch_pack_chunks(mb, select.data(), nc, MI_PACK_VERIFY, &p);
+        memfs_pack_drop(m, prc, prc ? std::string("chunk pack: ") + mi_last_error(ctx) : std::string());
+        m->pack = p;
+        const mi_file_result* files = nullptr;
+        uint64_t nf = 0;
+        cl->chunk_first.assign(cl->nodes.size() + 1, 0);
+        if (mi_batch_files_view(mb, &files, &nf)) return;
+        for (size_t i = 0; i < cl->nodes.size(); ++i) {
+            const mi_copy::Node& nd = cl->nodes[i];
+            if (nd.batch_file >= 0 && nd.batch_gen == fs.commit_gen && (uint64_t)nd.batch_file < nf) {
+                const mi_file_result& f = files[nd.batch_file];
+                for (uint64_t k = f.first_chunk; k < f.first_chunk + f.n_chunks && k < nc; ++k) {
+                    cl->chunk_digests.insert(cl->chunk_digests.end(), rows[k].sha256, rows[k].sha256 + 32);
+                    cl->chunk_lengths.push_back(rows[k].length);
+                }
+            }
+            cl->chunk_first[i + 1] = cl->chunk_lengths.size();
+        }
     }
     void stats() {
         m->last.files_opened += mi_io::content_opens.load() - opens0;
@@ -512,6 +556,11 @@ static int memfs_commit(mi_memfs* m, mi_ctx* const* ctxs, uint32_t n_ctx, int mu
             return MI_ERR_INVALID;
         }
     }
+    if (n_ctx && m->chunk_pack) {                                                 // MI_MEMFS_CHUNK_PACK: before anything is walked
+        if (!m->index) { m->err = "failed to generate diff layer: chunk pack: MI_MEMFS_CHUNK_PACK packs the chunks the index did not know: set one first (mi_memfs_set_index)"; return MI_ERR_STATE; }
+        if (n_ctx > 1) { m->err = "failed to generate diff layer: chunk pack: a pack over several GPUs' arenas is not built (MI_MEMFS_CHUNK_PACK with n_ctx > 1)"; return MI_ERR_INVALID; }
+        memfs_pack_drop(m, MI_ERR_STATE, "the last commit made no pack");         // (an earlier commit's pack nobody took goes)
+    }
     Commit c(m, ctxs, n_ctx, must_scan != 0, ops, n_ops);
     int rc = c.open_batch();
     if (!rc && n_ctx) m->root_alg = (int)alg;                                     // (from here on roots of this algorithm may land)
@@ -552,8 +601,22 @@ extern "C" int mi_memfs_commit_stats(const mi_memfs* m, mi_commit_stats* out) {
     return MI_OK;
 }
 extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
-    if (!m || (options & ~MI_MEMFS_TRUST_CTIME)) return MI_ERR_INVALID;
+    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK))) return MI_ERR_INVALID;
     m->fs.trust_ctime = (options & MI_MEMFS_TRUST_CTIME) != 0;
+    m->chunk_pack = (options & MI_MEMFS_CHUNK_PACK) != 0;
+    return MI_OK;
+}
+extern "C" int mi_memfs_take_pack(mi_memfs* m, mi_pack** out) {
+    if (!m || !out) return MI_ERR_INVALID;
+    *out = nullptr;
+    if (!m->pack) {
+        m->err = "mi_memfs_take_pack: " + m->pack_err;
+        return m->pack_rc ? m->pack_rc : MI_ERR_STATE;
+    }
+    *out = m->pack;
+    m->pack = nullptr;
+    m->pack_rc = MI_ERR_STATE;
+    m->pack_err = "no commit since the last mi_memfs_take_pack";
     return MI_OK;
 }
 extern "C" int mi_memfs_set_index(mi_memfs* m, mi_index* index) {

@@ -625,6 +625,11 @@ inline bool eval_symlinks(const std::string& p, const std::string& root, std::st
 
 struct mi_copy_layer {
     std::vector<mi_copy::Node> nodes;                       // commit order
+    // MI_MEMFS_CHUNK_PACK: the recipes -- entry i's ordered chunks are rows [chunk_first[i], chunk_first[i + 1]) of the two
+    // arrays (32 bytes / one length per row); chunk_first is empty for a layer of a commit without the option
+    std::vector<uint64_t> chunk_first;
+    std::vector<uint8_t>  chunk_digests;
+    std::vector<uint32_t> chunk_lengths;
 };
 
 // ---- MemFS as a handle: the reference's type (lib/snapshot/mem_fs.go:59-125) behind the ABI ---------------------------
@@ -647,8 +652,14 @@ struct mi_memfs {
                                          // made or reset (memfs_commit refuses a ctx of the other kind)
     mi_commit_stats last;                // of the last mi_memfs_commit_layer
     bool went_windowed = false;          // the scanned tree did not fit the device (the next full scan goes window by window at once)
+    // MI_MEMFS_CHUNK_PACK: the pack of the last commit until mi_memfs_take_pack hands it over (mi_commit.hip: memfs_pack_drop /
+    // Commit::pack_and_recipes are its only writers); pack_rc: what a take returns while there is none, pack_err: why
+    bool chunk_pack = false;
+    mi_pack* pack = nullptr;
+    int pack_rc = MI_ERR_STATE;
+    std::string pack_err = "no commit since the last mi_memfs_take_pack";
     mi_memfs() { memset(&last, 0, sizeof last); }
-    ~mi_memfs() { if (batch) mi_batch_free(batch); }
+    ~mi_memfs() { if (pack) mi_pack_free(pack); if (batch) mi_batch_free(batch); }
 };
 
 // MI_MEMFS_TIMING=1: one line per merge / scan on stderr

@@ -59,4 +59,6 @@ MI_LOCAL int  mi_index_same_ctx(mi_index* index, mi_batch* b);
 MI_LOCAL mi_ctx* mi_index_ctx(mi_index* index);   /* whose algorithm its digests are of (mi_ctx_chunk_digest) */
 // mi_tree.hip
 MI_LOCAL void mi_batch_tree_free(void* tree);
+// mi_pack.hip: a valid pack of nothing (a commit with the pack option that scanned no file has no batch that ran)
+MI_LOCAL int  mi_pack_empty(mi_ctx* ctx, mi_pack** out);
 }

@@ -404,6 +404,21 @@ extern "C" int mi_copy_layer_roots(const mi_copy_layer* l, uint8_t* roots, uint8
     return MI_OK;
 }
 
+// the ordered chunks of layer entry `entry`: the recipe a chunk store rebuilds the file from (MI_MEMFS_CHUNK_PACK)
+extern "C" int mi_copy_layer_chunks(const mi_copy_layer* l, uint64_t entry, uint8_t* digests, uint32_t* lengths, uint64_t cap, uint64_t* n) {
+    if (!l || !n || entry >= l->nodes.size() || (cap && (!digests || !lengths))) return MI_ERR_INVALID;
+    const uint64_t first = l->chunk_first.empty() ? 0 : l->chunk_first[entry];
+    const uint64_t cnt = l->chunk_first.empty() ? 0 : l->chunk_first[entry + 1] - first;
+    *n = cnt;
+    if (cap == 0) return MI_OK;                                                   // sizing
+    if (cap < cnt) return MI_ERR_CAPACITY;
+    if (cnt) {
+        memcpy(digests, l->chunk_digests.data() + 32 * first, 32 * cnt);
+        memcpy(lengths, l->chunk_lengths.data() + first, 4 * cnt);
+    }
+    return MI_OK;
+}
+
 // the tree, sorted by path (directories made up by addAncestors included: they are nodes like any other)
 extern "C" int mi_memfs_entries(const mi_memfs* m, mi_tree_entry* out, const char** src_paths, uint64_t cap, uint64_t* n_out) {
     if (!m || !n_out || (cap && !out)) return MI_ERR_INVALID;
