@@ -1048,6 +1048,67 @@ MI_BLOCK int mi_memfs_take_pack(mi_memfs* fs, mi_pack** out);
 MI_BLOCK int mi_copy_layer_chunks(const mi_copy_layer* layer, uint64_t entry, uint8_t* digests, uint32_t* lengths,
                                   uint64_t cap, uint64_t* n);
 
+/* ---- the consuming side: files of a batch rebuilt on the device from packs and recipes ---------------------- *
+ * A host that pulled packs (blob + entries) and recipes (mi_copy_layer_chunks' digests and lengths) from its chunk store puts
+ * the layer's bytes back into a batch without the files ever existing on its disk: the batch is then an ordinary batch --
+ * mi_batch_run gives the recipes' own rows and roots (same CDC parameters), mi_batch_read_file and mi_layer_add_batch_file
+ * give the bytes and the layer tar with its TarDigest, mi_batch_pack_chunks packs again.
+ *   mi_packset_create     a PACK SET: packs resident on the ctx's device, addressed by digest through a device hash table
+ *                         (open addressing, the tag a digest's first 8 bytes; entries_hint sizes it, 0 is fine: it is
+ *                         rebuilt at twice the size when it passes half full).  A child of its ctx: free it before
+ *                         mi_ctx_destroy, which refuses while one lives.
+ *   mi_packset_add_blob   a pack from host memory.  ALWAYS, on the host, before a byte is uploaded: the entries lie inside
+ *                         the blob on 16-byte offsets, ascending, without overlap (offset + length rounded up to 16 <=
+ *                         blob_bytes, without 64-bit wrap), n < 2^32 -- the structural half of mi_pack_check; a violation is
+ *                         MI_ERR_INVALID with *first_bad = the entry (first_bad may be NULL), the set unchanged.  The blob goes
+ *                         up through two pinned windows of the set's own into device memory of its own (does not fit:
+ *                         MI_ERR_NOMEM naming both sizes, the set unchanged).  MI_PACKSET_VERIFY: the other half -- the pad
+ *                         bytes are zero and every entry hashes to its digest under the ctx's algorithm, hashed on the device
+ *                         by the ctx's own hashing kernel; MI_ERR_INVALID with *first_bad = the entry mi_pack_check names for
+ *                         the same input, the set unchanged.  A digest the set holds already is kept once (the same pack
+ *                         twice, another pack, several entries of one pack).  The same digest with ANOTHER LENGTH -- only
+ *                         unverified input can hold one -- fails the add with MI_ERR_INVALID and the set is unusable from
+ *                         then on: every later call with it is MI_ERR_STATE with that first message (sticky, like a staging
+ *                         failure; mi_packset_free is what remains).
+ *   mi_packset_add_pack   the same for a pack of the SAME ctx where it lies (mi_batch_pack_chunks, mi_memfs_take_pack): a
+ *                         device-to-device copy; the pack stays the caller's.
+ *   mi_batch_add_recipes  n_files files from their recipes: file i has n_chunks[i] rows, `digests` (32 bytes a row) and
+ *                         `lengths` hold all files' rows end to end, a file's size is the sum of its lengths, 0 rows are an
+ *                         empty file; user_tags may be NULL (tags 0).  The files are placed as mi_batch_add_synthetic places
+ *                         them and may be mixed with host-fed files in any order.  BLOCKING: every row is looked up in the
+ *                         set's table, the files are assembled in the arena by one destination-driven kernel, and the call
+ *                         returns when the bytes lie there -- the set may be freed at once, the batch keeps no pointer to it.
+ *                         MI_ERR_INVALID: a digest the set does not hold (the message names the file, the row within it and
+ *                         the digest), a digest held with another length than the row states, a row of length 0, more than
+ *                         2^32 - 1 rows, a set of another ctx, a group head; the smallest bad row is the one named.
+ *                         MI_ERR_STATE: a batch that was staged already.  MI_RECIPE_VERIFY: the assembled ranges are hashed
+ *                         where they lie (the ctx's hashing kernel) and held against the recipes' digests -- the end-to-end
+ *                         check, whatever the set believed about its packs; a row that differs is MI_ERR_IO naming file, row,
+ *                         arena offset and source address.  ANY failure leaves the batch as it was before the call.  Restored
+ *                         rows carry no source sums (like synthetic rows): MI_RECIPE_VERIFY is their check.                */
+#define MI_PACKSET_VERIFY 0x1u
+#define MI_RECIPE_VERIFY  0x1u
+typedef struct mi_packset mi_packset;
+typedef struct {
+    uint64_t n_packs, n_entries, n_digests /* distinct */, blob_bytes;
+    uint32_t alg /* MI_DIGEST_* of the ctx */, reserved;
+    double   ms_upload, ms_verify, ms_insert;      /* of the last add */
+} mi_packset_info;
+typedef struct {
+    uint64_t n_files, n_rows, bytes;
+    uint64_t n_joined_units;     /* 16-byte destination units assembled from more than one row (counted by the kernel) */
+    double   ms_resolve, ms_assemble, ms_verify;
+} mi_recipe_stats;
+MI_BLOCK int  mi_packset_create(mi_ctx* ctx, uint64_t entries_hint, mi_packset** out);
+MI_BLOCK int  mi_packset_add_blob(mi_packset* s, const void* blob, uint64_t blob_bytes, const mi_pack_entry* entries,
+                                  uint64_t n, uint32_t flags, uint64_t* first_bad);
+MI_BLOCK int  mi_packset_add_pack(mi_packset* s, const mi_pack* p, uint32_t flags);
+MI_BLOCK int  mi_packset_get_info(const mi_packset* s, mi_packset_info* out);
+MI_BLOCK void mi_packset_free(mi_packset* s);
+MI_BLOCK int  mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t n_files, const uint64_t* n_chunks,
+                                   const uint8_t* digests, const uint32_t* lengths, const uint64_t* user_tags,
+                                   uint32_t flags, mi_recipe_stats* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

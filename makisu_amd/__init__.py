@@ -18,7 +18,8 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "FLAG_FILE_SHA256", "FLAG_FILE_CRC32", "FLAG_NO_DEDUP", "FLAG_PREFETCH_ROWS", "FLAG_VERIFY_STAGING", "FLAG_FILE_SUMS",
            "FLAG_CHUNK_BLAKE2S", "DIGEST_SHA256", "DIGEST_BLAKE2S", "chunk_root",
            "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex",
-           "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check"]
+           "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
+           "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -119,6 +120,29 @@ class PackInfo(C.Structure):
     """mi_pack_info."""
     _fields_ = [("n_entries", C.c_uint64), ("blob_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64),
                 ("alg", C.c_uint32), ("verified", C.c_uint32), ("ms_gather", C.c_double), ("ms_verify", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+PACKSET_VERIFY = 0x1                     # mi_packset_add_*: pad bytes and digests checked on the device before the set takes the pack
+RECIPE_VERIFY = 0x1                      # mi_batch_add_recipes: the assembled rows hashed where they lie, held against the recipes
+
+
+class PackSetInfo(C.Structure):
+    """mi_packset_info."""
+    _fields_ = [("n_packs", C.c_uint64), ("n_entries", C.c_uint64), ("n_digests", C.c_uint64), ("blob_bytes", C.c_uint64),
+                ("alg", C.c_uint32), ("reserved", C.c_uint32), ("ms_upload", C.c_double), ("ms_verify", C.c_double),
+                ("ms_insert", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RecipeStats(C.Structure):
+    """mi_recipe_stats."""
+    _fields_ = [("n_files", C.c_uint64), ("n_rows", C.c_uint64), ("bytes", C.c_uint64), ("n_joined_units", C.c_uint64),
+                ("ms_resolve", C.c_double), ("ms_assemble", C.c_double), ("ms_verify", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -358,6 +382,12 @@ def load_library(rebuild=False):
         "mi_pack_check": ([vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
         "mi_memfs_take_pack": ([vp, C.POINTER(vp)], C.c_int),
         "mi_copy_layer_chunks": ([vp, u64, vp, vp, u64, u64p], C.c_int),
+        "mi_packset_create": ([vp, u64, C.POINTER(vp)], C.c_int),
+        "mi_packset_add_blob": ([vp, vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
+        "mi_packset_add_pack": ([vp, vp, C.c_uint32], C.c_int),
+        "mi_packset_get_info": ([vp, C.POINTER(PackSetInfo)], C.c_int),
+        "mi_packset_free": ([vp], None),
+        "mi_batch_add_recipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1097,6 +1127,56 @@ class Pack:
         self.close()
 
 
+class PackSet:
+    """mi_packset_*: packs resident on the engine's device, addressed by digest (Engine.packset): what Batch.add_recipes
+    assembles files from.  A child of its Engine."""
+
+    def __init__(self, engine, entries_hint=0):
+        self._eng = engine
+        self._lib = engine._lib
+        h = C.c_void_p()
+        engine._check(self._lib.mi_packset_create(engine._h, entries_hint, C.byref(h)))
+        self._h = h
+        engine._children.add(self)
+
+    def add_blob(self, blob, entries, verify=False):
+        """mi_packset_add_blob: a pack from host memory (blob: bytes-like; entries: PACK_ENTRY_DTYPE rows).  A failure raises
+        MiError with .first_bad = the entry the call names."""
+        b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+        e = np.ascontiguousarray(entries, dtype=PACK_ENTRY_DTYPE)
+        bad = C.c_uint64()
+        rc = self._lib.mi_packset_add_blob(self._h, b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size,
+                                           PACKSET_VERIFY if verify else 0, C.byref(bad))
+        if rc:
+            err = MiError(rc, self._lib.mi_last_error(self._eng._h).decode())
+            err.first_bad = bad.value
+            raise err
+
+    def add_pack(self, pack, verify=False):
+        """mi_packset_add_pack: a Pack of the same Engine, copied where it lies; the pack stays the caller's"""
+        self._eng._check(self._lib.mi_packset_add_pack(self._h, pack._h, PACKSET_VERIFY if verify else 0))
+
+    @property
+    def info(self):
+        out = PackSetInfo()
+        self._eng._check(self._lib.mi_packset_get_info(self._h, C.byref(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mi_packset_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def pack_check(blob, entries, alg=DIGEST_SHA256):
     """mi_pack_check (host logic, no GPU): None if the pack is sound, else the index of the first entry that is not -- off the
     16-byte grid, overlapping, past the end, a non-zero pad byte, a chunk that does not hash to its digest; an unknown alg
@@ -1217,6 +1297,10 @@ class Engine:
     def index(self, capacity_hint=0):
         """A chunk-digest set that outlives batches (dedup across layers)."""
         return ChunkIndex(self, capacity_hint)
+
+    def packset(self, entries_hint=0):
+        """mi_packset_create: packs on this device, addressed by digest (the source of Batch.add_recipes)"""
+        return PackSet(self, entries_hint)
 
     # ---- native RCCL exchange (what a Go host would use; bench.py drives torch instead) ----
     @staticmethod
@@ -1458,6 +1542,36 @@ class Batch:
             ptr, n = sel.ctypes.data, len(select)
         self._check(self._lib.mi_batch_pack_chunks(self._h, ptr, n, PACK_VERIFY if verify else 0, C.byref(h)))
         return Pack(self.engine, h)
+
+    def add_recipes(self, packset, recipes, tags=None, verify=False):
+        """mi_batch_add_recipes: one file per recipe, assembled on the device from the pack set.  recipes: a list of (digests:
+        (n, 32) uint8, lengths: n uint32) pairs, or of lists of (digest bytes, length) rows as a MEMFS_CHUNK_PACK commit's layer
+        gives them under "chunks".  -> RecipeStats"""
+        dig, lens, counts = [], [], []
+        for rec in recipes:
+            if isinstance(rec, tuple) and len(rec) == 2 and not isinstance(rec[0], (bytes, bytearray)):
+                d = np.ascontiguousarray(rec[0], dtype=np.uint8).reshape(-1, 32)
+                n = np.ascontiguousarray(rec[1], dtype=np.uint32).reshape(-1)
+            else:
+                d = np.frombuffer(b"".join(bytes(x[0]) for x in rec), dtype=np.uint8).reshape(-1, 32)
+                n = np.array([int(x[1]) for x in rec], dtype=np.uint32)
+            if len(d) != len(n):
+                raise ValueError("a recipe of %d digests and %d lengths" % (len(d), len(n)))
+            dig.append(d)
+            lens.append(n)
+            counts.append(len(n))
+        d = np.ascontiguousarray(np.concatenate(dig)) if dig else np.zeros((0, 32), np.uint8)
+        n = np.ascontiguousarray(np.concatenate(lens)) if lens else np.zeros(0, np.uint32)
+        cnt = np.array(counts, dtype=np.uint64)
+        tg = np.ascontiguousarray(tags, dtype=np.uint64) if tags is not None else None
+        if tg is not None and tg.size != cnt.size:
+            raise ValueError("%d tags for %d recipes" % (tg.size, cnt.size))
+        out = RecipeStats()
+        self._check(self._lib.mi_batch_add_recipes(self._h, packset._h, cnt.size, cnt.ctypes.data if cnt.size else None,
+                                                   d.ctypes.data if d.size else None, n.ctypes.data if n.size else None,
+                                                   tg.ctypes.data if tg is not None and tg.size else None, RECIPE_VERIFY if verify else 0,
+                                                   C.byref(out)))
+        return out
 
     def add_tree(self, root, rel_base=None, blacklist=(), mode=TREE_CONTEXT):
         """Walk `root` the way the reference does (filepath.Walk order) and add its regular

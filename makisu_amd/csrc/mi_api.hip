@@ -1172,6 +1172,9 @@ int mi_batch_add_synthetic(mi_batch* b, uint64_t n_files, const uint64_t* sizes,
     return MI_OK;
 }
 
+// (hidden: mi_local.h) the reservation of the call above, for the files mi_batch_add_recipes places (mi_restore.hip)
+extern "C" int mi_batch_arena_reserve(mi_batch* b, uint64_t end) { return arena_reserve(b, end); }
+
 // Stages everything that was added (flush of the pinned ring, file tables, synthetic
 // generation).  Done once per batch, before its first submit.
 static int stage_batch(mi_batch* b);

@@ -61,4 +61,9 @@ MI_LOCAL mi_ctx* mi_index_ctx(mi_index* index);   /* whose algorithm its digests
 MI_LOCAL void mi_batch_tree_free(void* tree);
 // mi_pack.hip: a valid pack of nothing (a commit with the pack option that scanned no file has no batch that ran)
 MI_LOCAL int  mi_pack_empty(mi_ctx* ctx, mi_pack** out);
+// ... and the ctx a pack points at (mi_restore.hip: a set takes packs of its own ctx only)
+MI_LOCAL mi_ctx* mi_pack_ctx(const mi_pack* p);
+// mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
+// it: what the arena holds stays, whichever kind it is)
+MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);
 }

@@ -515,6 +515,8 @@ int mi_pack_empty(mi_ctx* c, mi_pack** out) {           // (hidden: mi_local.h)
     return MI_OK;
 }
 
+mi_ctx* mi_pack_ctx(const mi_pack* p) { return p ? p->ctx : nullptr; }     // (hidden: mi_local.h)
+
 int mi_pack_get_info(const mi_pack* p, mi_pack_info* out) {
     if (!p || !out) return MI_ERR_INVALID;
     *out = p->info;
