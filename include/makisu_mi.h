@@ -1109,6 +1109,53 @@ MI_BLOCK int  mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t 
                                    const uint8_t* digests, const uint32_t* lengths, const uint64_t* user_tags,
                                    uint32_t flags, mi_recipe_stats* stats_out);
 
+/* ---- fetch only what is missing: a pack set asked by digest, and cut by digest into a new pack ------------------- *
+ * What connects the two sides at chunk granularity.  The puller asks its own set which chunks of a layer's recipes it lacks
+ * (the want list), the server cuts exactly those out of whatever packs hold them (one mi_pack), the puller adds that pack
+ * (mi_packset_add_blob with MI_PACKSET_VERIFY) and assembles the layer (mi_batch_add_recipes) as before.  mi_packset_pack over a
+ * store's live digests is also its compaction: live digests -> a pack -> a new set -> free the old one.  Both calls block on
+ * the ctx stream, leave the set unchanged, take fewer than 2^32 rows (more: MI_ERR_INVALID) and answer MI_ERR_STATE with the
+ * first message for a set in its sticky failed state.
+ *   mi_packset_missing    digests: n x 32 bytes of host memory (a layer's recipes end to end); lengths: n x u32 or NULL.
+ *                         held (optional, n bytes): 1 where the set holds the row's digest.  want_rows (cap = the rows it has
+ *                         room for): the rows at which a digest the set lacks occurs for the FIRST time, ascending -- every
+ *                         distinct missing digest once; the caller has digest and length at each row.  cap < n_want: nothing
+ *                         is written to want_rows and the call is MI_ERR_CAPACITY with held and *info filled; cap = 0 with
+ *                         want_rows = NULL is the sizing call and MI_OK.  With lengths: a row of length 0 is MI_ERR_INVALID;
+ *                         a digest the set holds with another length than the row states is MI_ERR_INVALID naming the
+ *                         smallest such row, its digest and both lengths (mi_batch_add_recipes' words); repeats of a MISSING
+ *                         digest are not compared with each other -- nothing is known about it yet.  n = 0: MI_OK, *info zero.
+ *   mi_packset_pack       an ordinary mi_pack of every distinct requested digest once, in order of first occurrence: entry k
+ *                         = {digest, offset, chunk_index = the request row of the first occurrence, length = the SET'S,
+ *                         reserved 0}, the blob laid out as mi_batch_pack_chunks lays it out -- entry k at the sum of the
+ *                         lengths before it, each rounded up to 16, the pad bytes ZERO whatever the source blob held behind
+ *                         the chunk (a set built without MI_PACKSET_VERIFY may hold non-zero pads): a pure function of the
+ *                         request and the chunks' bytes, whichever pack held a chunk.  Everything that takes a pack takes
+ *                         this one (mi_pack_get_info with alg = the ctx's, _entries, _read, _device, mi_packset_add_pack,
+ *                         _free; mi_pack_check on the host).  The pack owns a COPY: it survives mi_packset_free; it is a
+ *                         child of the set's ctx (mi_ctx_destroy refuses while it lives).  MI_ERR_INVALID: a digest the
+ *                         set does not hold (or holds with 0 bytes: a pack has no entry for that), and with lengths a
+ *                         stated length of 0 or another one than the set's -- *first_bad (may be NULL) = the smallest such
+ *                         row, the message gives row and digest.  A blob that does not fit: MI_ERR_NOMEM naming both sizes,
+ *                         nothing has changed, the caller splits the request.  n = 0: the empty pack.
+ *                         MI_SUBPACK_VERIFY: the new blob's entries are hashed on the device (the ctx's algorithm) and held
+ *                         against the REQUESTED digests; an entry that differs is MI_ERR_IO naming the request row (also in
+ *                         *first_bad), the source address and the blob offset, and no pack is returned -- what catches a set
+ *                         fed from an unverified, damaged blob.  mi_pack_info.verified, ms_gather and ms_verify as for a
+ *                         batch's pack.                                                                                  */
+#define MI_SUBPACK_VERIFY 0x1u
+typedef struct {               /* 56 bytes */
+    uint64_t n_rows, n_distinct;   /* request rows; distinct digests among them */
+    uint64_t n_held, n_want;       /* distinct digests the set holds / lacks: n_held + n_want == n_distinct */
+    uint64_t held_bytes;           /* sum of the SET's lengths over the held distinct digests */
+    uint64_t want_bytes;           /* sum of the request's stated lengths over the want rows (0 when lengths == NULL) */
+    double   ms_resolve;           /* device time of the call, HIP events on the ctx stream */
+} mi_want_info;
+MI_BLOCK int  mi_packset_missing(const mi_packset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                                 uint8_t* held, uint64_t* want_rows, uint64_t cap, mi_want_info* info);
+MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                              uint32_t flags, mi_pack** out, uint64_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

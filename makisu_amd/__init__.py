@@ -19,7 +19,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "FLAG_CHUNK_BLAKE2S", "DIGEST_SHA256", "DIGEST_BLAKE2S", "chunk_root",
            "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
-           "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY"]
+           "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -143,6 +143,18 @@ class RecipeStats(C.Structure):
     """mi_recipe_stats."""
     _fields_ = [("n_files", C.c_uint64), ("n_rows", C.c_uint64), ("bytes", C.c_uint64), ("n_joined_units", C.c_uint64),
                 ("ms_resolve", C.c_double), ("ms_assemble", C.c_double), ("ms_verify", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+SUBPACK_VERIFY = 0x1                     # mi_packset_pack: the new blob hashed on the device, held against the requested digests
+
+
+class WantInfo(C.Structure):
+    """mi_want_info."""
+    _fields_ = [("n_rows", C.c_uint64), ("n_distinct", C.c_uint64), ("n_held", C.c_uint64), ("n_want", C.c_uint64),
+                ("held_bytes", C.c_uint64), ("want_bytes", C.c_uint64), ("ms_resolve", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -388,6 +400,8 @@ def load_library(rebuild=False):
         "mi_packset_get_info": ([vp, C.POINTER(PackSetInfo)], C.c_int),
         "mi_packset_free": ([vp], None),
         "mi_batch_add_recipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
+        "mi_packset_missing": ([vp, vp, vp, u64, vp, vp, u64, C.POINTER(WantInfo)], C.c_int),
+        "mi_packset_pack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1155,6 +1169,51 @@ class PackSet:
     def add_pack(self, pack, verify=False):
         """mi_packset_add_pack: a Pack of the same Engine, copied where it lies; the pack stays the caller's"""
         self._eng._check(self._lib.mi_packset_add_pack(self._h, pack._h, PACKSET_VERIFY if verify else 0))
+
+    @staticmethod
+    def _request(digests, lengths):
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        ln = None if lengths is None else np.ascontiguousarray(lengths, dtype=np.uint32).reshape(-1)
+        if ln is not None and len(ln) != len(d):
+            raise ValueError("%d lengths for %d digests" % (len(ln), len(d)))
+        return d, ln
+
+    def _raise(self, rc, first_bad=None):
+        err = MiError(rc, self._lib.mi_last_error(self._eng._h).decode())
+        if first_bad is not None:
+            err.first_bad = first_bad
+        raise err
+
+    def missing(self, digests, lengths=None):
+        """mi_packset_missing: which of the request's digests (n x 32 bytes; lengths: n or None) the set lacks.
+        -> (held: uint8[n], want_rows: uint64[n_want] -- the rows of first occurrence of every missing digest, ascending --,
+        WantInfo)"""
+        d, ln = self._request(digests, lengths)
+        n = len(d)
+        args = (self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n)
+        held = np.zeros(max(n, 1), dtype=np.uint8)
+        info = WantInfo()
+        rc = self._lib.mi_packset_missing(*args, held.ctypes.data, None, 0, C.byref(info))       # the sizing call
+        if rc:
+            self._raise(rc)
+        want = np.zeros(max(info.n_want, 1), dtype=np.uint64)
+        if info.n_want:
+            rc = self._lib.mi_packset_missing(*args, held.ctypes.data, want.ctypes.data, info.n_want, C.byref(info))
+            if rc:
+                self._raise(rc)
+        return held[:n], want[:info.n_want], info
+
+    def pack(self, digests, lengths=None, verify=False):
+        """mi_packset_pack: a Pack of every distinct requested digest once, in order of first occurrence, from whatever packs
+        of the set hold them.  A failure raises MiError with .first_bad = the request row the call names."""
+        d, ln = self._request(digests, lengths)
+        n = len(d)
+        h, bad = C.c_void_p(), C.c_uint64()
+        rc = self._lib.mi_packset_pack(self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n,
+                                       SUBPACK_VERIFY if verify else 0, C.byref(h), C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+        return Pack(self._eng, h)
 
     @property
     def info(self):

@@ -63,6 +63,18 @@ MI_LOCAL void mi_batch_tree_free(void* tree);
 MI_LOCAL int  mi_pack_empty(mi_ctx* ctx, mi_pack** out);
 // ... and the ctx a pack points at (mi_restore.hip: a set takes packs of its own ctx only)
 MI_LOCAL mi_ctx* mi_pack_ctx(const mi_pack* p);
+// mi_pack.hip, for mi_fetch.hip: a pack of n_entries (> 0) rows and a blob of blob_bytes whose contents the CALLER writes on the ctx
+// stream -- *d_blob is device memory of the pack's own (exactly blob_bytes + the slack; does not fit: MI_ERR_NOMEM naming both
+// sizes under `who`, no pack), *h_rows the n_entries rows mi_pack_entries hands out; mi_pack_free on any later failure.  Then what the
+// caller found out about it (mi_pack_info's other fields)
+MI_LOCAL int  mi_pack_alloc(mi_ctx* ctx, const char* who, uint64_t n_entries, uint64_t blob_bytes, uint64_t chunk_bytes, mi_pack** out,
+                            void** d_blob, mi_pack_entry** h_rows);
+MI_LOCAL void mi_pack_set_result(mi_pack* p, uint32_t verified, double ms_gather, double ms_verify);
+// mi_restore.hip, for mi_fetch.hip: the set's ctx and its table as it is now (cap slots, a power of two; tags 8 bytes a slot, slots
+// six words: digest 4 | the chunk's device address | its length).  MI_ERR_STATE under `who` with the first message for a set
+// in its sticky failed state, MI_ERR_INVALID for NULL
+MI_LOCAL int  mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ctx, const uint64_t** tags, const uint64_t** slots,
+                               uint64_t* cap);
 // mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
 // it: what the arena holds stays, whichever kind it is)
 MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);

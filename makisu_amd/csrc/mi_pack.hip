@@ -517,6 +517,42 @@ int mi_pack_empty(mi_ctx* c, mi_pack** out) {           // (hidden: mi_local.h)
 
 mi_ctx* mi_pack_ctx(const mi_pack* p) { return p ? p->ctx : nullptr; }     // (hidden: mi_local.h)
 
+// (hidden: mi_local.h) a pack whose blob and rows mi_fetch.hip writes: mi_packset_pack
+int mi_pack_alloc(mi_ctx* c, const char* who, uint64_t n_entries, uint64_t blob_bytes, uint64_t chunk_bytes, mi_pack** out, void** d_blob,
+                  mi_pack_entry** h_rows) {
+    if (!c || !out || !d_blob || !h_rows || !n_entries) return MI_ERR_INVALID;
+    *out = nullptr;
+    mi_pack* p = new mi_pack();
+    p->ctx = c;
+    ++c->live_children;                                    // mi_pack_free undoes it
+    p->info.alg = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? MI_DIGEST_BLAKE2S : MI_DIGEST_SHA256;
+    p->info.n_entries = n_entries;
+    p->info.blob_bytes = blob_bytes;
+    p->info.chunk_bytes = chunk_bytes;
+    const hipError_t e = alloc_exact(&p->blob, blob_bytes);
+    if (e != hipSuccess) {
+        size_t free_b = 0, total_b = 0;
+        (void)hipMemGetInfo(&free_b, &total_b);
+        (void)hipGetLastError();
+        const int rc = fail(c, e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "%s: a blob of %llu bytes (%llu chunks) does not fit: the "
+                            "device has %llu bytes free (%s); split the request", who, (unsigned long long)blob_bytes,
+                            (unsigned long long)n_entries, (unsigned long long)free_b, hipGetErrorString(e));
+        pack_delete(p);
+        return rc;
+    }
+    p->h_rows.resize(n_entries);
+    *d_blob = p->blob.p;
+    *h_rows = p->h_rows.data();
+    *out = p;
+    return MI_OK;
+}
+
+void mi_pack_set_result(mi_pack* p, uint32_t verified, double ms_gather, double ms_verify) {
+    p->info.verified = verified;
+    p->info.ms_gather = ms_gather;
+    p->info.ms_verify = ms_verify;
+}
+
 int mi_pack_get_info(const mi_pack* p, mi_pack_info* out) {
     if (!p || !out) return MI_ERR_INVALID;
     *out = p->info;

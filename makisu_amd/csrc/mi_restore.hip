@@ -689,6 +689,18 @@ int mi_packset_get_info(const mi_packset* s, mi_packset_info* out) {
     return MI_OK;
 }
 
+// (hidden: mi_local.h) what mi_fetch.hip's lookup walks: mi_packset_missing, mi_packset_pack
+int mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ctx, const uint64_t** tags, const uint64_t** slots, uint64_t* cap) {
+    if (!s || !ctx || !tags || !slots || !cap) return MI_ERR_INVALID;
+    *ctx = s->ctx;
+    const int rc = set_state(s, who);
+    if (rc) return rc;
+    *tags = s->tags.as<u64>();
+    *slots = s->slots.as<u64>();
+    *cap = s->cap;
+    return MI_OK;
+}
+
 void mi_packset_free(mi_packset* s) {
     if (!s) return;
     mi_ctx* c = s->ctx;
