@@ -65,6 +65,21 @@ def test_a_three_level_root(oracle):
         assert files["n_chunks"][0] > 4096
 
 
+def test_root_tree_exact_chunk_counts(oracle):
+    """test_gpu_parity.py's test_chunk_root_tree_exact_chunk_counts with BLAKE2s at every node: files of exactly N chunks
+    (mask_bits 0, min_size = max_size = 64) at the tree's edges up to 262 145 chunks (three reduction passes), then a batch
+    whose one planned reduction pass has no file to reduce"""
+    import makisu_amd
+    from table_models import ROOT_EDGE_CHUNKS
+    with makisu_amd.Engine(flags=makisu_amd.FLAG_CHUNK_BLAKE2S, mask_bits=0, min_size=64, max_size=64) as e:
+        counts = ROOT_EDGE_CHUNKS[:5] + [0] + ROOT_EDGE_CHUNKS[5:]
+        files, _ = check_batch(oracle, e, [oracle.synth_fill(SEED, 7000 + i, 0, 64 * n).tobytes() for i, n in enumerate(counts)])
+        assert files["n_chunks"].tolist() == counts and max(counts) == 262145
+        counts = [63, 1, 0, 62, 63]
+        files, _ = check_batch(oracle, e, [oracle.synth_fill(SEED, 7100 + i, 0, 64 * n).tobytes() for i, n in enumerate(counts)])
+        assert files["n_chunks"].tolist() == counts
+
+
 @pytest.mark.parametrize("mask_bits,min_size,max_size", [(0, 64, 64), (4, 128, 3000), (9, 512, 10000), (16, 4096, 262144),
                                                          (13, 2048, 1 << 20)])
 def test_param_sets_of_the_large_file_suite(oracle, mask_bits, min_size, max_size):

@@ -547,6 +547,61 @@ def test_file_crc32_large_files_fold_in_parallel(oracle):
         assert int(row["crc32"]) == zlib.crc32(oracle.synth_fill(SEED, c, 0, n).tobytes()), n
 
 
+def _crc32_of(blobs):
+    """the GPU's crc32 column for these files, and zlib's"""
+    import zlib
+    import makisu_amd
+    with makisu_amd.Engine(flags=makisu_amd.FLAG_FILE_CRC32) as e, e.batch(len(blobs), sum(len(x) for x in blobs)) as b:
+        for blob in blobs:
+            b.add_bytes(blob)
+        b.run()
+        got = b.files()["crc32"].astype(np.int64)
+    return got, np.array([zlib.crc32(blob) for blob in blobs], dtype=np.int64)
+
+
+def test_file_crc32_every_size_around_a_lane_run_and_a_tile():
+    """Every size 0..1160 and 65 536 - 1160 .. 65 536 + 1160: every residue of a lane's 128-byte and 4-byte loops, a last
+    run of 1..1024 bytes, files of 63, 64 and 65 runs, with and without a second tile of 1..1160 bytes -- against zlib."""
+    pool = np.random.default_rng(32).integers(0, 256, 1 << 20, dtype=np.uint8).tobytes()
+    sizes = list(range(0, 1161)) + list(range(65536 - 1160, 65536 + 1160 + 1))
+    blobs = [pool[(i * 4099) % 900000:][:n] for i, n in enumerate(sizes)]
+    assert [len(x) for x in blobs] == sizes
+    got, want = _crc32_of(blobs)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "sizes %s" % [sizes[i] for i in bad[:10]]
+
+
+def test_file_crc32_of_zeros_is_the_length_term():
+    """A file of zeros has the CRC of its length alone (0xFFFFFFFF * x^(8 size), complemented): whatever the lanes read
+    cancels, what is left is crc32_files_kernel's use of both power tables and the fold's x^(8 * bytes behind a tile).
+    Sizes 65 536 k + r around 64 and 128 tiles."""
+    sizes = [65536 * k + r for k in (1, 2, 3, 63, 64, 65, 127, 128, 129) for r in (0, 1, 1023, 1024, 1025, 65535)]
+    got, want = _crc32_of([bytes(n) for n in sizes])
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "sizes %s" % [sizes[i] for i in bad[:10]]
+    assert len(set(want.tolist())) == len(sizes)
+
+
+def test_file_crc32_one_byte_set_per_tile_position():
+    """Zeros but for one 0x80 byte -- at the first, middle and last byte of the first, a middle and the last tile, the last
+    tile whole (64 tiles) or 1000 bytes (130 tiles): against the all-zero file of the same size only that tile's term of
+    crc32_fold_kernel, x^(8 * bytes behind it), differs."""
+    blobs, where = [], []
+    for size in (64 * 65536, 129 * 65536 + 1000):
+        tiles = (size + 65535) // 65536
+        for t in (0, tiles // 2, tiles - 1):
+            lo, hi = t * 65536, min((t + 1) * 65536, size)
+            for pos in (lo, (lo + hi) // 2, hi - 1):
+                blob = bytearray(size)
+                blob[pos] = 0x80
+                blobs.append(bytes(blob))
+                where.append((size, t, pos - lo))
+    got, want = _crc32_of(blobs)
+    bad = np.nonzero(got != want)[0]
+    assert bad.size == 0, "(size, tile, byte in tile) %s" % [where[i] for i in bad[:10]]
+    assert len(set(want.tolist())) == len(blobs)
+
+
 def _walk_order(entries):
     """filepath.Walk order over a set of relative paths: lexical per directory, a directory
     before its children (Go path/filepath: Walk sorts names in each directory)."""
@@ -832,6 +887,23 @@ def test_chunk_root_tree_three_levels(oracle):
     import makisu_amd
     with makisu_amd.Engine(mask_bits=6, min_size=64, max_size=256) as e:
         _compare_synth(oracle, e, [160 * 1024 * 1024, 400000, 700, 0], [40, 41, 42, 43])
+
+
+def test_chunk_root_tree_exact_chunk_counts(oracle):
+    """mask_bits 0 and min_size = max_size = 64: a file of 64 N bytes has exactly N chunks, so the tree's edges are met
+    on purpose instead of where random content puts them -- exactly the fan-out (carried, not reduced), one more (a last
+    node with one child), the same one level up (4096, 4097, 4160 = 65 nodes), and 262 145 chunks: three reduction passes
+    (4097, 65 and 2 nodes) and the final one.  The second batch's largest file has 63 chunks: mi_batch_run plans one
+    reduction pass from the upper bound size / min_size + 2 = 65, and no file contributes to it."""
+    import makisu_amd
+    from table_models import ROOT_EDGE_CHUNKS
+    with makisu_amd.Engine(mask_bits=0, min_size=64, max_size=64) as e:
+        counts = ROOT_EDGE_CHUNKS[:5] + [0] + ROOT_EDGE_CHUNKS[5:]
+        files, _ = _compare_synth(oracle, e, [64 * n for n in counts], list(range(7000, 7000 + len(counts))))
+        assert files["n_chunks"].tolist() == counts and max(counts) == 262145
+        counts = [63, 1, 0, 62, 63]
+        files, _ = _compare_synth(oracle, e, [64 * n for n in counts], list(range(7100, 7100 + len(counts))))
+        assert files["n_chunks"].tolist() == counts
 
 
 @pytest.mark.skipif(False, reason="")
