@@ -1156,6 +1156,70 @@ MI_BLOCK int  mi_packset_missing(const mi_packset* s, const uint8_t* digests, co
 MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
                               uint32_t flags, mi_pack** out, uint64_t* first_bad);
 
+/* ---- compressed packs ("zpacks"): every chunk coded on its own as one LZ4 block, on the device ------------------- *
+ * What a chunk store keeps at rest and sends over the wire instead of plain bytes: take_pack -> mi_pack_compress -> store; the
+ * puller hands blob and entries to mi_packset_add_zblob and goes on as before -- a set holds PLAIN chunks, whatever fed it.
+ * FORMAT.  mi_zpack_entry is mi_pack_entry with `stored` where `reserved` was.  offset is a multiple of 16, entry k begins
+ * at the sum of the stored sizes before it, each rounded up to 16, the pad bytes are zero, length is never 0.  stored ==
+ * length: the chunk's bytes as they are.  stored < length: ONE STANDARD LZ4 BLOCK (token, literal-length extension bytes,
+ * literals, a 2-byte little-endian offset in 1..65535, match-length extension bytes; the last sequence is literals only, the
+ * last 5 bytes are literals, no match starts within the last 12 bytes) that any LZ4 library expands.  The coder keeps the block
+ * only when it is smaller than length - (length >> 4); chunks under 13 bytes are always raw.  Blob and entries are a pure
+ * function of the input pack: no timing, no hardware write order, no device shows in them.
+ *   mi_pack_compress      any pack (mi_batch_pack_chunks, mi_memfs_take_pack, mi_packset_pack), which stays the caller's and is
+ *                         not changed.  Blocking, on the ctx stream.  The zpack is a child of the pack's ctx (mi_ctx_destroy
+ *                         refuses while one lives).  0 entries: a zpack of 0 entries.  The coder's scratch (worst-case spans)
+ *                         or the blob does not fit: MI_ERR_NOMEM naming both sizes, nothing has changed.  MI_ZPACK_VERIFY: the
+ *                         new blob is decoded again on the device, hashed by the ctx's own hashing kernel and held against
+ *                         the entries' digests; an entry that differs is MI_ERR_IO naming the entry, its offset and its
+ *                         digest, and no zpack is returned.
+ *   mi_zpack_entries, _read, _free   as their mi_pack_* namesakes (mi_zpack_read: two pinned windows of the zpack's own).
+ *   mi_packset_add_zblob  a zpack from host memory into an ordinary set.  ALWAYS, on the host, before a byte is uploaded:
+ *                         offsets on the 16-byte grid, ascending, without overlap, offset + stored rounded up to 16 <=
+ *                         blob_bytes (no 64-bit wrap), 0 < stored <= length, n < 2^32; a violation is MI_ERR_INVALID with
+ *                         *first_bad (may be NULL) = the entry, the set unchanged.  The blob goes up through the set's
+ *                         windows and is decoded on the device into a plain blob laid out as a pack's.  The decoder trusts
+ *                         nothing: an offset of 0 or beyond the bytes produced so far, a literal run or a length extension
+ *                         that leaves the stored span, output that passes or falls short of `length`, stored bytes left over,
+ *                         a non-zero pad byte each fail the entry; the smallest failing entry is named (MI_ERR_INVALID,
+ *                         *first_bad, the message says which rule), the set unchanged.  Then as mi_packset_add_blob behind its
+ *                         upload: MI_PACKSET_VERIFY hashes the PLAIN entries -- whatever the stream claimed, an entry that does
+ *                         not hash to its digest never enters a verified set.
+ *   mi_packset_add_zpack  the same for a zpack of the SAME ctx, decoded where it lies; the zpack stays the caller's.
+ *   mi_zpack_check        host logic, no ctx, no GPU -- what a puller runs before it trusts a zpack: the structure as above,
+ *                         zero pads, and every entry decodes under the device's rules to `length` bytes that hash to its
+ *                         digest under alg.  MI_OK, or MI_ERR_INVALID with *first_bad = the entry the device path names for
+ *                         the same input (structure first, then the first entry that does not decode, then the first that
+ *                         does not hash).                                                                                */
+#define MI_ZPACK_VERIFY 0x1u
+typedef struct mi_zpack mi_zpack;
+typedef struct {               /* 56 bytes: mi_pack_entry's layout */
+    uint8_t  digest[32];       /* of the chunk's PLAIN bytes (the ctx's algorithm) */
+    uint64_t offset;           /* where the stored form begins in the blob: a multiple of 16 */
+    uint64_t chunk_index;      /* as in the pack the zpack was made from */
+    uint32_t length;           /* the chunk's bytes, never 0 */
+    uint32_t stored;           /* bytes in the blob: == length raw, < length one LZ4 block */
+} mi_zpack_entry;
+typedef struct {               /* 80 bytes */
+    uint64_t n_entries, blob_bytes, chunk_bytes;   /* blob_bytes = sum of stored sizes rounded up to 16 */
+    uint64_t stored_bytes;     /* sum of the stored sizes */
+    uint64_t n_raw;            /* entries stored as they are */
+    uint32_t alg;              /* MI_DIGEST_* of the ctx that made it */
+    uint32_t verified;         /* 1: decoded again on the device and every digest agreed */
+    double   ms_encode, ms_compact, ms_verify;     /* HIP events on the ctx stream */
+    double   ms_decode;        /* the part of ms_verify that is the decode kernel over the whole blob */
+} mi_zpack_info;
+MI_BLOCK int  mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out);
+MI_BLOCK int  mi_zpack_get_info(const mi_zpack* z, mi_zpack_info* out);
+MI_BLOCK int  mi_zpack_entries(const mi_zpack* z, mi_zpack_entry* out, uint64_t cap);
+MI_BLOCK int  mi_zpack_read(mi_zpack* z, uint64_t offset, void* dst, uint64_t len);
+MI_BLOCK void mi_zpack_free(mi_zpack* z);
+MI_BLOCK int  mi_packset_add_zblob(mi_packset* s, const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries,
+                                   uint64_t n, uint32_t flags, uint64_t* first_bad);
+MI_BLOCK int  mi_packset_add_zpack(mi_packset* s, const mi_zpack* z, uint32_t flags);
+MI_BLOCK int  mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n,
+                             uint32_t alg, uint64_t* first_bad);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,8 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "FLAG_CHUNK_BLAKE2S", "DIGEST_SHA256", "DIGEST_BLAKE2S", "chunk_root",
            "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
-           "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY"]
+           "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
+           "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -160,6 +161,25 @@ class WantInfo(C.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+ZPACK_VERIFY = 0x1                       # mi_pack_compress: the new blob decoded and hashed again on the device
+
+
+class ZPackEntry(C.Structure):
+    """mi_zpack_entry: one chunk of a compressed pack (stored == length: raw; stored < length: one LZ4 block)."""
+    _fields_ = [("digest", C.c_uint8 * 32), ("offset", C.c_uint64), ("chunk_index", C.c_uint64),
+                ("length", C.c_uint32), ("stored", C.c_uint32)]
+
+
+class ZPackInfo(C.Structure):
+    """mi_zpack_info."""
+    _fields_ = [("n_entries", C.c_uint64), ("blob_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64), ("stored_bytes", C.c_uint64),
+                ("n_raw", C.c_uint64), ("alg", C.c_uint32), ("verified", C.c_uint32), ("ms_encode", C.c_double),
+                ("ms_compact", C.c_double), ("ms_verify", C.c_double), ("ms_decode", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
 class LayerResult(C.Structure):
     """mi_layer_result: the numbers of step.commitLayer's DigestPair."""
     _fields_ = [("tar_sha256", C.c_uint8 * 32), ("gzip_sha256", C.c_uint8 * 32), ("tar_bytes", C.c_uint64),
@@ -238,6 +258,7 @@ def _np_dtype(struct):
 FILE_DTYPE = _np_dtype(_FileResult)
 CHUNK_DTYPE = _np_dtype(_ChunkResult)
 PACK_ENTRY_DTYPE = _np_dtype(PackEntry)
+ZPACK_ENTRY_DTYPE = _np_dtype(ZPackEntry)
 
 _lib = None
 
@@ -402,6 +423,14 @@ def load_library(rebuild=False):
         "mi_batch_add_recipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
         "mi_packset_missing": ([vp, vp, vp, u64, vp, vp, u64, C.POINTER(WantInfo)], C.c_int),
         "mi_packset_pack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
+        "mi_pack_compress": ([vp, C.c_uint32, C.POINTER(vp)], C.c_int),
+        "mi_zpack_get_info": ([vp, C.POINTER(ZPackInfo)], C.c_int),
+        "mi_zpack_entries": ([vp, vp, u64], C.c_int),
+        "mi_zpack_read": ([vp, u64, vp, u64], C.c_int),
+        "mi_zpack_free": ([vp], None),
+        "mi_packset_add_zblob": ([vp, vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
+        "mi_packset_add_zpack": ([vp, vp, C.c_uint32], C.c_int),
+        "mi_zpack_check": ([vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1126,9 +1155,65 @@ class Pack:
         self._eng._check(self._lib.mi_pack_device(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
+    def compress(self, verify=False):
+        """mi_pack_compress: every chunk coded on its own as one LZ4 block (or kept raw) on the device -> ZPack; this pack
+        is not changed"""
+        h = C.c_void_p()
+        self._eng._check(self._lib.mi_pack_compress(self._h, ZPACK_VERIFY if verify else 0, C.byref(h)))
+        return ZPack(self._eng, h)
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.mi_pack_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
+class ZPack:
+    """mi_zpack_*: a compressed pack in device memory (Pack.compress).  A child of its Engine, independent of the pack it
+    came from."""
+
+    def __init__(self, engine, handle):
+        self._eng = engine
+        self._lib = engine._lib
+        self._h = handle
+        engine._children.add(self)
+
+    @property
+    def info(self):
+        out = ZPackInfo()
+        self._eng._check(self._lib.mi_zpack_get_info(self._h, C.byref(out)))
+        return out
+
+    def __len__(self):
+        return self.info.n_entries
+
+    def entries(self):
+        """the entries in blob order: a numpy array of ZPACK_ENTRY_DTYPE"""
+        n = self.info.n_entries
+        out = np.zeros(max(n, 1), dtype=ZPACK_ENTRY_DTYPE)
+        self._eng._check(self._lib.mi_zpack_entries(self._h, out.ctypes.data, n))
+        return out[:n]
+
+    def read(self, offset=0, length=None):
+        """bytes [offset, offset + length) of the compressed blob; read() is the whole blob"""
+        if length is None:
+            length = self.info.blob_bytes - offset
+        out = np.zeros(max(length, 1), dtype=np.uint8)
+        self._eng._check(self._lib.mi_zpack_read(self._h, offset, out.ctypes.data, length))
+        return out[:length].tobytes()
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mi_zpack_free(self._h)
             self._h = None
 
     free = close
@@ -1169,6 +1254,21 @@ class PackSet:
     def add_pack(self, pack, verify=False):
         """mi_packset_add_pack: a Pack of the same Engine, copied where it lies; the pack stays the caller's"""
         self._eng._check(self._lib.mi_packset_add_pack(self._h, pack._h, PACKSET_VERIFY if verify else 0))
+
+    def add_zblob(self, blob, entries, verify=False):
+        """mi_packset_add_zblob: a compressed pack from host memory (entries: ZPACK_ENTRY_DTYPE rows), decoded on the device;
+        the set holds plain chunks as ever.  A failure raises MiError with .first_bad = the entry the call names."""
+        b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+        e = np.ascontiguousarray(entries, dtype=ZPACK_ENTRY_DTYPE)
+        bad = C.c_uint64()
+        rc = self._lib.mi_packset_add_zblob(self._h, b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size,
+                                            PACKSET_VERIFY if verify else 0, C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+
+    def add_zpack(self, zpack, verify=False):
+        """mi_packset_add_zpack: a ZPack of the same Engine, decoded where it lies; the zpack stays the caller's"""
+        self._eng._check(self._lib.mi_packset_add_zpack(self._h, zpack._h, PACKSET_VERIFY if verify else 0))
 
     @staticmethod
     def _request(digests, lengths):
@@ -1247,6 +1347,20 @@ def pack_check(blob, entries, alg=DIGEST_SHA256):
     bad = C.c_uint64()
     rc = load_library().mi_pack_check(b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size, alg,
                                       C.byref(bad))
+    return None if rc == 0 else bad.value
+
+
+def zpack_check(blob, entries, alg=DIGEST_SHA256):
+    """mi_zpack_check (host logic, no GPU): None if the compressed pack is sound, else the index of the first entry that is
+    not -- its structure, an LZ4 block the decoder refuses, a non-zero pad byte, bytes that do not hash to the digest; an
+    unknown alg raises."""
+    if alg not in (DIGEST_SHA256, DIGEST_BLAKE2S):
+        raise MiError(-1, "mi_zpack_check: unknown digest algorithm %r" % (alg,))
+    b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+    e = np.ascontiguousarray(entries, dtype=ZPACK_ENTRY_DTYPE)
+    bad = C.c_uint64()
+    rc = load_library().mi_zpack_check(b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size, alg,
+                                       C.byref(bad))
     return None if rc == 0 else bad.value
 
 

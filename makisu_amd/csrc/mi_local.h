@@ -75,6 +75,13 @@ MI_LOCAL void mi_pack_set_result(mi_pack* p, uint32_t verified, double ms_gather
 // in its sticky failed state, MI_ERR_INVALID for NULL
 MI_LOCAL int  mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ctx, const uint64_t** tags, const uint64_t** slots,
                                uint64_t* cap);
+// mi_restore.hip, for mi_zpack.hip: `bytes` of host memory up to d_dst through the set's two pinned windows (blocking; *ms: how
+// long it took); and a PLAIN blob that lies on the device already -- blob: a mi::DevBuf of exactly blob_bytes + the slack, which
+// the set takes over (NULL with n = 0); entries: on the host, structurally sound -- added as mi_packset_add_blob adds one behind
+// its upload: MI_PACKSET_VERIFY, the table, the counters; until the insert begins every failure leaves the set as it was
+MI_LOCAL int  mi_packset_upload(mi_packset* s, void* d_dst, const void* src, uint64_t bytes, double* ms);
+MI_LOCAL int  mi_packset_adopt(mi_packset* s, const char* who, void* blob, uint64_t blob_bytes, const mi_pack_entry* entries, uint64_t n,
+                               uint32_t flags, double ms_upload, uint64_t* first_bad);
 // mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
 // it: what the arena holds stays, whichever kind it is)
 MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);

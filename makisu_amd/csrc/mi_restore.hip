@@ -701,6 +701,26 @@ int mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ctx, const u
     return MI_OK;
 }
 
+// (hidden: mi_local.h) for mi_zpack.hip: bytes up through the set's two windows, blocking; and a PLAIN blob that lies on the
+// device already (blob: a mi::DevBuf the set takes over, NULL with n = 0) added as mi_packset_add_blob adds one behind its upload
+int mi_packset_upload(mi_packset* s, void* d_dst, const void* src, uint64_t bytes, double* ms) {
+    if (!s || (bytes && (!d_dst || !src))) return MI_ERR_INVALID;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int rc = s->up.upload(s->ctx, (u8*)d_dst, src, bytes);
+    if (ms) *ms = ms_since(t0);
+    return rc;
+}
+
+int mi_packset_adopt(mi_packset* s, const char* who, void* blob, uint64_t blob_bytes, const mi_pack_entry* entries, uint64_t n, uint32_t flags,
+                     double ms_upload, uint64_t* first_bad) {
+    if (!s || !who || (n && (!blob || !entries))) return MI_ERR_INVALID;
+    const int rc = set_state(s, who);
+    if (rc) return rc;
+    s->info.ms_upload = ms_upload;
+    DevBuf none;
+    return set_add(s, who, std::move(blob ? *(DevBuf*)blob : none), n ? blob_bytes : 0, entries, n, flags, first_bad);
+}
+
 void mi_packset_free(mi_packset* s) {
     if (!s) return;
     mi_ctx* c = s->ctx;

@@ -1,0 +1,944 @@
+// mi_zpack.hip -- compressed chunk packs ("zpacks"): every chunk of a pack coded ON ITS OWN as one standard LZ4 block, on the
+// device (mi_pack_compress and the mi_zpack_* calls of include/makisu_mi.h), and such a pack decoded on the device into the
+// plain blob an ordinary pack set holds (mi_packset_add_zblob, mi_packset_add_zpack); mi_zpack_check is the host's opinion
+// (csrc/host_lz4.h).  What a chunk store keeps at rest and sends over the wire instead of plain bytes.
+//
+//   encode    one wave a chunk, a hash table of 4 096 32-bit positions in LDS (16 KiB, cleared per chunk; the workgroup IS the
+//             wave).  The wave advances in STEPS of 64 consecutive positions [p, p + 64), capped at n - 12: lane i reads its 4
+//             bytes and the slot (u32 * 2654435761) >> 20 AS THE TABLE WAS BEFORE THE STEP.  A candidate c counts if c < pos,
+//             pos - c <= 65535 and the 4 bytes are equal (a table of zeros needs no "empty" mark).  No candidate: all 64
+//             positions go into the table, the bytes stay pending literals.  Otherwise the LOWEST lane with a candidate wins (one
+//             ballot), the match is extended 64 bytes a round up to n - 5, the sequence is written (lane 0: token and offset;
+//             the wave: extension bytes and literals), p becomes the match's end and the step's positions BELOW the new p go
+//             into the table.  Two lanes of a step in one slot: the greater position wins (atomicMax: the order the hardware
+//             writes LDS in does not show).  The block is kept if it is smaller than n - (n >> 4); chunks under 13 bytes are raw;
+//   layout    the wave writes into scratch at the chunk's WORST-CASE span (n + n / 255 + 16, rounded up to 16; the prefix sums
+//             are taken on the host, which has the pack's entries); the stored sizes are known only then: mi_pack.hip's three
+//             launches (block sums over 2 048 rows, one block over the sums, the placing pass) over round16(stored), and a
+//             destination-driven gather of 16 KiB tiles (mi_fetch.hip's, from absolute addresses: a raw chunk is gathered
+//             from the INPUT pack, a coded one from scratch) into a blob of exactly its size;
+//   decode    one wave an entry.  A raw entry is a copy in 16-byte units.  An LZ entry's sequences are taken in order: token and
+//             offset are read by every lane alike, extension bytes 64 at a time with a ballot for the first below 255, the wave
+//             copies literals and match bytes.  A match is PERIODIC with its offset: byte i is the byte (i mod offset) behind
+//             op - offset, so every lane reads in front of the match, whatever the overlap.  The pad behind the chunk is zero;
+//   verify    MI_ZPACK_VERIFY: the new blob decoded again into the scratch spans, the result through the ctx's own hashing
+//             launcher (pass kShaBlobs), held against the entries' digests.
+//
+// BOUNDS.  The decoder is what parses bytes from elsewhere.  WRITES: a literal run or a match is copied only after
+// len <= length - op was checked, the pad is [length, round16(length)): nothing outside [dst, dst + round16(length)), the
+// entry's own span of the plain layout.  READS of the stored form: every index is compared with `stored` before the load
+// (token, extension bytes, the two offset bytes, the literal run as a whole); the pad check reads [stored, round16(stored)),
+// which the structural check on the host (offset + round16(stored) <= blob_bytes, always, before any upload) keeps inside the
+// blob.  READS of the output: op - offset + (i mod offset) with 0 < offset <= op: inside [dst, dst + op).  A raw entry is read
+// in aligned 16-byte units inside [src, src + round16(stored)).  The encoder reads src[pos .. pos + 3] with pos <= n - 12 and
+// match bytes below n - 5: inside the chunk; it writes below the worst-case span (checked per sequence: a block that would pass
+// it -- none does -- is stored raw).  The gather reads aligned units inside [src, src + round16(stored)) of the input pack or of
+// a scratch span.  The hashing of the verify pass reads up to 67 bytes behind the last scratch span: DevBuf's 256 bytes.
+#include "mi_internal.h"
+#include "mi_item_loads.h"
+#include "host_blake2s.h"
+#include "host_lz4.h"
+#include "host_sha256.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+using namespace mi;
+
+namespace mi {
+
+constexpr u64 kZNone = ~0ull;
+__host__ __device__ static inline u64 z_round16(u64 v) { return (v + 15) & ~15ull; }
+// what one chunk of n bytes takes in scratch: the LZ4 bound for a block of literals, on the 16-byte grid
+__host__ __device__ static inline u64 z_worst_span(u64 n) { return z_round16(n + n / 255 + 16); }
+
+constexpr int kZEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
+static_assert(sizeof(mi_zpack_entry) == 56 && kZEntryWords == 7 && sizeof(mi_pack_entry) == 56, "mi_zpack_entry is seven 8-byte words");
+
+typedef u32 u32_unaligned __attribute__((aligned(1)));
+
+// ---- encode ---------------------------------------------------------------------------------------------------------------------
+constexpr int kZHashBits = 12;
+constexpr int kZTable = 1 << kZHashBits;                      // 32-bit positions: 16 KiB a wave
+constexpr u32 kZMinChunk = 13;                                // below: raw
+constexpr u32 kZMaxOffset = 65535;
+
+static __device__ __forceinline__ int z_first(u64 mask) { return __ffsll((unsigned long long)mask) - 1; }
+
+// `count` extension bytes for the value e behind a nibble of 15 (count = e / 255 + 1), by the wave
+static __device__ __forceinline__ void z_put_extension(u8* out, u32 e, int lane) {
+    const u32 count = e / 255 + 1;
+    for (u32 j = lane; j < count; j += 64) out[j] = j + 1 < count ? (u8)255 : (u8)(e % 255);
+}
+
+// rows[k]: digest | the chunk's offset in the pack's blob | chunk_index | length (the high half is written here: stored)
+__global__ __launch_bounds__(64)
+void zpack_encode_kernel(const u8* __restrict__ blob, u64* __restrict__ rows, const u64* __restrict__ w_off, u8* __restrict__ scratch, u64 n) {
+    __shared__ u32 table[kZTable];
+    const int lane = threadIdx.x;
+    for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
+        const u64* r = rows + kZEntryWords * k;
+        const u8* src = blob + r[4];
+        const u32 len = (u32)r[6];
+        u8* out = scratch + w_off[k];
+        const u64 cap = z_worst_span(len);
+        u32 stored = len;
+        if (len >= kZMinChunk) {
+            for (int i = lane; i < kZTable; i += 64) table[i] = 0;
+            __syncthreads();
+            const u32 last = len - 12, limit = len - 5;      // a match starts at or before `last` and ends at or before `limit`
+            u32 p = 0, anchor = 0;
+            u64 op = 0;
+            bool fits = true;
+            while (p <= last) {
+                const u32 cnt = last + 1 - p < 64u ? last + 1 - p : 64u;
+                const u32 pos = p + lane;
+                const bool active = (u32)lane < cnt;
+                u32 v = 0, h = 0, c = 0;
+                bool ok = false;
+                if (active) {
+                    v = *(const u32_unaligned*)(src + pos);
+                    h = (v * 2654435761u) >> (32 - kZHashBits);
+                    c = table[h];
+                    ok = c < pos && pos - c <= kZMaxOffset && *(const u32_unaligned*)(src + c) == v;
+                }
+                const u64 m = __ballot(ok);
+                __syncthreads();                              // every lane has read the table as it was before the step
+                if (m == 0) {
+                    if (active) atomicMax(&table[h], pos);
+                    p += cnt;
+                    __syncthreads();
+                    continue;
+                }
+                const int f = z_first(m);
+                const u32 mpos = p + f, mc = __shfl(c, f);
+                u32 mlen = 4;
+                for (;;) {                                    // 64 bytes a round; mpos + 4 < limit, so the first round has a lane inside
+                    const u32 i = mpos + mlen + lane;
+                    const bool differs = i >= limit || src[i] != src[mc + mlen + lane];
+                    const u64 d = __ballot(differs);
+                    if (d == 0) { mlen += 64; continue; }
+                    mlen += z_first(d);
+                    break;
+                }
+                const u32 lit = mpos - anchor, ml = mlen - 4;
+                const u64 need = 1 + (lit >= 15 ? (lit - 15) / 255 + 1 : 0) + lit + 2 + (ml >= 15 ? (ml - 15) / 255 + 1 : 0);
+                if (op + need > cap) { fits = false; break; }
+                if (lane == 0) out[op] = (u8)(((lit < 15 ? lit : 15u) << 4) | (ml < 15 ? ml : 15u));
+                op += 1;
+                if (lit >= 15) { z_put_extension(out + op, lit - 15, lane); op += (lit - 15) / 255 + 1; }
+                for (u32 j = lane; j < lit; j += 64) out[op + j] = src[anchor + j];
+                op += lit;
+                if (lane == 0) { out[op] = (u8)((mpos - mc) & 255); out[op + 1] = (u8)((mpos - mc) >> 8); }
+                op += 2;
+                if (ml >= 15) { z_put_extension(out + op, ml - 15, lane); op += (ml - 15) / 255 + 1; }
+                const u32 next = mpos + mlen;
+                if (active && pos < next) atomicMax(&table[h], pos);
+                p = anchor = next;
+                __syncthreads();
+            }
+            const u32 lit = len - anchor;                     // the last sequence: literals only (at least 5)
+            const u64 need = 1 + (lit >= 15 ? (lit - 15) / 255 + 1 : 0) + lit;
+            if (fits && op + need <= cap) {
+                if (lane == 0) out[op] = (u8)((lit < 15 ? lit : 15u) << 4);
+                op += 1;
+                if (lit >= 15) { z_put_extension(out + op, lit - 15, lane); op += (lit - 15) / 255 + 1; }
+                for (u32 j = lane; j < lit; j += 64) out[op + j] = src[anchor + j];
+                op += lit;
+                if (op < (u64)(len - (len >> 4))) stored = (u32)op;
+            }
+            __syncthreads();                                  // the next chunk clears the table
+        }
+        if (lane == 0) rows[kZEntryWords * k + 6] = (u64)len | ((u64)stored << 32);
+    }
+}
+
+// ---- layout: mi_pack.hip's scan over round16(stored) ---------------------------------------------------------------------------
+constexpr int kZBlock = 256;
+constexpr int kZPer   = 8;                            // rows per thread
+constexpr int kZTile  = kZBlock * kZPer;              // 2048 rows per block
+enum : int { kZTotBlob = 0, kZTotStored = 1, kZTotRaw = 2, kZTotChunk = 3, kZTotBad = 4 };
+
+static __device__ __forceinline__ u64 z_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    u64 x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
+        const u64 y = ((u64)hi << 32) | lo;
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    u64 wave_off = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < kZBlock / 64; ++w) {
+        const u64 s = lds[w];
+        if (w < wave) wave_off += s;
+        tot += s;
+    }
+    __syncthreads();
+    *total = tot;
+    return wave_off + x - v;
+}
+
+static __device__ __forceinline__ u64 z_wave_sum(u64 v) {
+#pragma unroll
+    for (int d = 32; d; d >>= 1) {
+        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
+        v += ((u64)hi << 32) | lo;
+    }
+    return v;
+}
+
+// per block of kZTile rows: the rounded-up stored bytes; into the totals: stored bytes, raw entries, chunk bytes
+__global__ __launch_bounds__(kZBlock)
+void zpack_block_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restrict__ block_bytes, u64* __restrict__ totals) {
+    __shared__ u64 lds[4][kZBlock / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 base = (u64)blockIdx.x * kZTile + (u64)threadIdx.x * kZPer;
+    u64 v[4] = {0, 0, 0, 0};                          // rounded-up stored bytes, stored bytes, raw entries, chunk bytes
+#pragma unroll
+    for (int k = 0; k < kZPer; ++k) {
+        if (base + k >= n) continue;
+        const u64 w = rows[kZEntryWords * (base + k) + 6];
+        const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
+        v[0] += z_round16(stored);
+        v[1] += stored;
+        v[2] += stored == len ? 1 : 0;
+        v[3] += len;
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        v[q] = z_wave_sum(v[q]);
+        if (lane == 0) lds[q][wave] = v[q];
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        u64 t[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            t[q] = 0;
+#pragma unroll
+            for (int w = 0; w < kZBlock / 64; ++w) t[q] += lds[q][w];
+        }
+        block_bytes[blockIdx.x] = t[0];
+        if (t[1]) atomicAdd((unsigned long long*)&totals[kZTotStored], (unsigned long long)t[1]);
+        if (t[2]) atomicAdd((unsigned long long*)&totals[kZTotRaw], (unsigned long long)t[2]);
+        if (t[3]) atomicAdd((unsigned long long*)&totals[kZTotChunk], (unsigned long long)t[3]);
+    }
+}
+
+// single block: exclusive scan of the block array in place; totals[kZTotBlob] = the blob's bytes
+__global__ __launch_bounds__(kZBlock)
+void zpack_block_offsets_kernel(u64* __restrict__ block_bytes, u64 n_blocks, u64* __restrict__ totals) {
+    __shared__ u64 lds[4];
+    u64 carry = 0;
+    for (u64 b0 = 0; b0 < n_blocks; b0 += kZBlock) {
+        const u64 i = b0 + threadIdx.x;
+        const u64 v = i < n_blocks ? block_bytes[i] : 0;
+        u64 t;
+        const u64 e = z_exclusive_scan(v, &t, lds);
+        if (i < n_blocks) block_bytes[i] = carry + e;
+        carry += t;
+    }
+    if (threadIdx.x == 0) totals[kZTotBlob] = carry;
+}
+
+// every entry's place in the new blob, where its stored form lies now (a raw chunk: in the input pack; a coded one: in its
+// scratch span) and the row's offset word: from here on the rows are the zpack's entries
+__global__ __launch_bounds__(kZBlock)
+void zpack_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, u64 n, const u64* __restrict__ block_bytes, u64 pack_base,
+                        u64 scratch_base, u64* __restrict__ e_src, u64* __restrict__ e_len, u64* __restrict__ e_dst) {
+    __shared__ u64 lds[4];
+    const u64 base = (u64)blockIdx.x * kZTile + (u64)threadIdx.x * kZPer;
+    u64 stored[kZPer], len[kZPer];
+    u64 bytes = 0;
+#pragma unroll
+    for (int k = 0; k < kZPer; ++k) {
+        const u64 w = base + k < n ? rows[kZEntryWords * (base + k) + 6] : 0;
+        len[k] = w & 0xFFFFFFFFull;
+        stored[k] = w >> 32;
+        bytes += z_round16(stored[k]);
+    }
+    u64 t;
+    u64 dst = z_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < kZPer; ++k) {
+        const u64 row = base + k;
+        if (row >= n) continue;
+        u64* r = rows + kZEntryWords * row;
+        e_src[row] = stored[k] == len[k] ? pack_base + r[4] : scratch_base + w_off[row];
+        e_len[row] = stored[k];
+        e_dst[row] = dst;
+        r[4] = dst;
+        dst += z_round16(stored[k]);
+    }
+}
+
+// ---- gather: mi_fetch.hip's, restated -----------------------------------------------------------------------------------------
+constexpr int kZWG = 256;
+constexpr u32 kZGatherTile = 16384;                   // bytes of the blob a workgroup writes
+constexpr u32 kZUnits = kZGatherTile / 16;            // ... in 16-byte units: an entry takes at least one, so at most as many entries
+constexpr int kZUnitsPer = kZUnits / kZWG;            // units per lane
+
+// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
+static __device__ __forceinline__ u64 z_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
+    u64 lo = 0, hi = n;
+    while (hi - lo > 1) {
+        const u64 step = (hi - lo + 63) >> 6;
+        const u64 p = lo + (u64)lane * step;
+        const bool ok = p < hi && a[p] <= x;
+        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
+        hi = lo + c * step < hi ? lo + c * step : hi;
+        lo = lo + (c - 1) * step;
+    }
+    return lo;
+}
+
+// an ALIGNED 16-byte load from an absolute device address (the address space is said here: a generic pointer would make it flat)
+static __device__ __forceinline__ u32x4 z_load16(u64 addr) {
+    typedef const u32x4 __attribute__((address_space(1))) * global_ptr;
+    return *(global_ptr)addr;
+}
+
+// the first `valid` (< 16) bytes of a unit, the rest zero
+static __device__ __forceinline__ u32x4 z_keep(u32x4 v, u32 valid) {
+    u32 w[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const u32 have = valid > 4u * q ? valid - 4u * q : 0u;
+        w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
+    }
+    return u32x4{w[0], w[1], w[2], w[3]};
+}
+
+__global__ __launch_bounds__(kZWG)
+void zpack_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
+                         u64 blob_bytes, u8* __restrict__ blob) {
+    __shared__ u64 s_src[kZUnits];
+    __shared__ u32 s_rel[kZUnits];                   // where the entry begins in the tile
+    __shared__ u32 s_len[kZUnits];
+    __shared__ u64 s_k[2];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const u64 tile0 = (u64)blockIdx.x * kZGatherTile;
+    const u64 tile1 = tile0 + kZGatherTile < blob_bytes ? tile0 + kZGatherTile : blob_bytes;
+    if (wave < 2) {
+        const u64 k = z_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
+        if (lane == 0) s_k[wave] = k;
+    }
+    __syncthreads();
+    const u64 k0 = s_k[0];
+    const u64 reach = s_k[1] - k0 + 1;
+    const u32 cnt = reach < kZUnits ? (u32)reach : kZUnits;
+    for (u32 i = threadIdx.x; i < cnt; i += kZWG) {
+        u64 src = e_src[k0 + i], len = e_len[k0 + i];
+        const u64 dst = e_dst[k0 + i];
+        u32 rel = (u32)(dst - tile0);
+        if (dst < tile0) {                           // the first entry may begin in front of the tile: the tile sees what is left
+            const u64 skip = tile0 - dst;            // of it -- skip is a multiple of 16 below its length
+            src += skip;
+            len -= skip;
+            rel = 0;
+        }
+        s_src[i] = src;
+        s_len[i] = (u32)len;
+        s_rel[i] = rel;
+    }
+    __syncthreads();
+    u64 src[kZUnitsPer];
+    u32 valid[kZUnitsPer];
+#pragma unroll
+    for (int j = 0; j < kZUnitsPer; ++j) {
+        const u32 r = ((u32)threadIdx.x + (u32)j * kZWG) * 16;
+        src[j] = s_src[0];                            // a unit behind the blob's end (the last tile) loads the tile's first unit and
+        valid[j] = 0;                                 // drops it: a lane's four loads are in flight together
+        if (tile0 + r >= tile1) continue;
+        u32 lo = 0, hi = cnt;                         // the entry this unit lies in: the last that begins at or before it
+        while (hi - lo > 1) {
+            const u32 mid = (lo + hi) >> 1;
+            if (s_rel[mid] <= r) lo = mid; else hi = mid;
+        }
+        const u32 o = r - s_rel[lo], len = s_len[lo];
+        if (o < len) {                                // (always, for entries of at least one byte)
+            src[j] = s_src[lo] + o;                   // a multiple of 16 behind an aligned address
+            valid[j] = len - o;
+        }
+    }
+    u32x4 v[kZUnitsPer];
+#pragma unroll
+    for (int j = 0; j < kZUnitsPer; ++j) v[j] = z_load16(src[j]);
+#pragma unroll
+    for (int j = 0; j < kZUnitsPer; ++j) {
+        const u32 r = ((u32)threadIdx.x + (u32)j * kZWG) * 16;
+        if (tile0 + r >= tile1) continue;
+        if (valid[j] < 16) v[j] = z_keep(v[j], valid[j]);   // the entry's last unit: zero at and beyond its stored bytes
+        *(u32x4*)(blob + tile0 + r) = v[j];
+    }
+}
+
+// ---- decode ---------------------------------------------------------------------------------------------------------------------
+// the extension bytes behind a nibble of 15, 64 at a time; false: the span ended first (host_lz4.h lz4_extension)
+static __device__ __forceinline__ bool z_get_extension(const u8* __restrict__ src, u64 stored, u64* ip, u64* len, int lane) {
+    for (;;) {
+        const u64 idx = *ip + lane;
+        const bool in = idx < stored;
+        const u32 b = in ? src[idx] : 0u;
+        const u64 m = __ballot(!in || b != 255u);
+        if (m == 0) { *len += 255ull * 64; *ip += 64; continue; }
+        const int f = z_first(m);
+        if (*ip + f >= stored) { *len += 255ull * f; *ip += f; return false; }
+        *len += 255ull * f + __shfl(b, f);
+        *ip += f + 1;
+        return true;
+    }
+}
+
+// one LZ4 block src[0, stored) -> dst[0, n), by one wave, under host_lz4.h's rules: 0 or the rule that refuses it
+static __device__ __forceinline__ u32 z_decode_block(const u8* __restrict__ src, u64 stored, u8* dst, u64 n, int lane) {
+    u64 ip = 0, op = 0, seen = 0;                     // seen: the output below it is visible to every lane's loads
+    for (;;) {
+        if (ip >= stored) return mi_host::kLz4OutputShort;
+        const u32 token = src[ip++];
+        u64 lit = token >> 4;
+        if (lit == 15 && !z_get_extension(src, stored, &ip, &lit, lane)) return mi_host::kLz4ExtensionCut;
+        if (lit > stored - ip) return mi_host::kLz4LiteralsLeave;
+        if (lit > n - op) return mi_host::kLz4OutputPasses;
+        for (u64 i = lane; i < lit; i += 64) dst[op + i] = src[ip + i];
+        ip += lit;
+        op += lit;
+        if (ip == stored) return op == n ? mi_host::kLz4Ok : mi_host::kLz4OutputShort;
+        if (stored - ip < 2) return mi_host::kLz4ExtensionCut;
+        const u64 off = (u64)src[ip] | ((u64)src[ip + 1] << 8);
+        ip += 2;
+        if (off == 0) return mi_host::kLz4OffsetZero;
+        if (off > op) return mi_host::kLz4OffsetBeyond;
+        u64 len = token & 15u;
+        if (len == 15 && !z_get_extension(src, stored, &ip, &len, lane)) return mi_host::kLz4ExtensionCut;
+        len += 4;
+        if (len > n - op) return mi_host::kLz4OutputPasses;
+        // the match repeats the `off` bytes in front of op: every byte comes from [op - off, op), written before this match
+        if (op - off + (len < off ? len : off) > seen) {
+            __syncthreads();                          // the wave's earlier stores have landed
+            seen = op;
+        }
+        const u8* from = dst + (op - off);
+        for (u64 i = lane; i < len; i += 64) dst[op + i] = from[i < off ? i : (u32)i % (u32)off];
+        op += len;
+    }
+}
+
+// rows: the zpack's entries (offset into zblob | chunk_index | length, stored); p_off: where the plain chunk goes in `out`
+__global__ __launch_bounds__(64)
+void zpack_decode_kernel(const u8* __restrict__ zblob, const u64* __restrict__ rows, const u64* __restrict__ p_off, u64 n, u8* out,
+                         u32* __restrict__ rule_out, u64* __restrict__ first_bad) {
+    const int lane = threadIdx.x;
+    for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
+        const u64* r = rows + kZEntryWords * k;
+        const u8* src = zblob + r[4];
+        const u64 len = r[6] & 0xFFFFFFFFull, stored = r[6] >> 32;
+        u8* dst = out + p_off[k];
+        u32 rule = 0;
+        if (stored == len) {                          // raw: aligned units, the bytes at and beyond the length zeroed in registers
+            for (u64 u = (u64)lane * 16; u < len; u += 64 * 16) {
+                u32x4 v = *(const u32x4*)(src + u);
+                if (len - u < 16) v = z_keep(v, (u32)(len - u));
+                *(u32x4*)(dst + u) = v;
+            }
+        } else {
+            rule = z_decode_block(src, stored, dst, len, lane);
+            if (len + lane < z_round16(len)) dst[len + lane] = 0;
+        }
+        const bool pad_set = stored + lane < z_round16(stored) && src[stored + lane] != 0;
+        if (__ballot(pad_set) != 0 && rule == 0) rule = mi_host::kLz4PadNotZero;
+        if (lane == 0) {
+            rule_out[k] = rule;
+            if (rule) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+        }
+        __syncthreads();
+    }
+}
+
+// MI_ZPACK_VERIFY: the digests of the decoded chunks against the rows'
+__global__ __launch_bounds__(256)
+void zpack_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ rows, u64 n, u64* __restrict__ first_bad) {
+    const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
+    if (k >= n) return;
+    const u64* g = (const u64*)(got + 32 * k);
+    const u64* w = rows + kZEntryWords * k;
+    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+}
+
+// ---- mi_zpack_read: mi_pack.hip's PackReader, restated -- the blob through two pinned windows, the copy of one overlapping the
+// consumption of the other ---------------------------------------------------------------------------------------------------
+constexpr u64 kZWinBytes = 8ull << 20;
+struct MI_LOCAL ZpackReader {
+    Stream stream;
+    struct Win { PinBuf buf; u64 start = 0, len = 0; bool pending = false; Event ev; };
+    Win win[2];
+    int cur = 0;
+    ZpackReader() = default;
+    ZpackReader(ZpackReader&&) = default;
+    ZpackReader& operator=(ZpackReader&&) = default;
+    ~ZpackReader() { if (stream) (void)hipStreamSynchronize(stream); }    // no copy into a window is under way when the windows go
+    int prepare(mi_ctx* c) {
+        if (win[0].buf.p) return MI_OK;
+        ZpackReader r;                                // whole or not at all
+        HIPCHK(c, r.stream.create());
+        for (auto& w : r.win) {
+            HIPCHK(c, w.buf.ensure(kZWinBytes));
+            HIPCHK(c, w.ev.create(hipEventDisableTiming));
+        }
+        *this = std::move(r);
+        return MI_OK;
+    }
+    int read(mi_ctx* c, const u8* base, u64 total, u64 at, void* dst, u64 len) {
+        if (!len) return MI_OK;
+        const int rc = prepare(c);
+        if (rc) return rc;
+        auto prefetch = [&](Win& w, u64 from) -> int {
+            w.len = 0;
+            if (from >= total) return MI_OK;
+            const u64 want = std::min(kZWinBytes, total - from);
+            HIPCHK(c, hipMemcpyAsync(w.buf.p, base + from, want, hipMemcpyDeviceToHost, stream));
+            HIPCHK(c, hipEventRecord(w.ev, stream));
+            w.start = from;
+            w.len = want;
+            w.pending = true;
+            return MI_OK;
+        };
+        u8* d = (u8*)dst;
+        while (len) {
+            Win* w = &win[cur];
+            if (!(w->len && at >= w->start && at < w->start + w->len)) {
+                Win* nx = &win[cur ^ 1];
+                const bool follows = w->len && at == w->start + w->len;          // the reader streams
+                if (nx->len && at >= nx->start && at < nx->start + nx->len) {
+                    if (nx->pending) { HIPCHK(c, hipEventSynchronize(nx->ev)); nx->pending = false; }
+                    cur ^= 1;
+                    const int prc = prefetch(*w, nx->start + nx->len);           // the window just left takes what follows the new one
+                    if (prc) return prc;
+                    continue;
+                }
+                if (nx->pending) { HIPCHK(c, hipEventSynchronize(nx->ev)); nx->pending = false; }
+                nx->len = 0;
+                const u64 want = std::min(kZWinBytes, total - at);
+                w->len = 0;
+                HIPCHK(c, hipMemcpyAsync(w->buf.p, base + at, want, hipMemcpyDeviceToHost, stream));
+                HIPCHK(c, hipStreamSynchronize(stream));
+                w->start = at;
+                w->len = want;
+                w->pending = false;
+                if (follows || want < len) {
+                    const int prc = prefetch(*nx, at + want);
+                    if (prc) return prc;
+                }
+            }
+            const u64 take = std::min(len, w->start + w->len - at);
+            memcpy(d, (const u8*)w->buf.p + (at - w->start), take);
+            d += take;
+            at += take;
+            len -= take;
+        }
+        return MI_OK;
+    }
+};
+
+}  // namespace mi
+
+struct mi_zpack {
+    mi_ctx* ctx = nullptr;
+    mi_zpack_info info = {};
+    DevBuf blob;                                 // info.blob_bytes + the slack every blob has
+    std::vector<mi_zpack_entry> h_rows;          // on the host before mi_pack_compress returns and never written again
+    ZpackReader reader;
+};
+
+namespace {
+
+std::string hex32(const uint8_t* d) {
+    static const char* dig = "0123456789abcdef";
+    std::string out(64, '0');
+    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
+    return out;
+}
+
+// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_pack.hip's scheme: a blob does not grow)
+hipError_t alloc_exact(DevBuf* b, u64 want) {
+    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
+    void* p = nullptr;
+    const hipError_t e = dev_alloc(&p, alloc);
+    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
+    return e;
+}
+
+int does_not_fit(mi_ctx* c, const char* who, const char* what, hipError_t e, u64 bytes, u64 n) {
+    size_t free_b = 0, total_b = 0;
+    (void)hipMemGetInfo(&free_b, &total_b);
+    (void)hipGetLastError();
+    return fail(c, e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "%s: %s of %llu bytes (%llu entries) does not fit: the device has "
+                "%llu bytes free (%s); split the pack", who, what, (unsigned long long)bytes, (unsigned long long)n, (unsigned long long)free_b,
+                hipGetErrorString(e));
+}
+
+void zpack_delete(mi_zpack* z) {
+    mi_ctx* c = z->ctx;
+    (void)hipSetDevice(c->device);
+    (void)hipStreamSynchronize(c->stream);
+    --c->live_children;
+    delete z;
+}
+
+mi_zpack* zpack_new(mi_ctx* c) {
+    mi_zpack* z = new mi_zpack();
+    z->ctx = c;
+    ++c->live_children;                                    // mi_zpack_free undoes it
+    z->info.alg = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? MI_DIGEST_BLAKE2S : MI_DIGEST_SHA256;
+    return z;
+}
+
+u32 wave_grid(u64 n) { return (u32)std::min<u64>(n, 1u << 20); }     // one wave an entry; more entries: the waves go round
+
+// The structure of a zpack, on the host, before anything else looks at it: offsets on the 16-byte grid, ascending, without
+// overlap, inside the blob (no 64-bit wrap), 0 < stored <= length.  false: *first_bad = the first entry that is not
+bool structure_ok(u64 blob_bytes, const mi_zpack_entry* entries, u64 n, u64* first_bad) {
+    u64 end = 0;                                       // where the previous entry's unit(s) end
+    for (u64 k = 0; k < n; ++k) {
+        const mi_zpack_entry& en = entries[k];
+        const u64 span = z_round16(en.stored);
+        if (en.stored != 0 && en.stored <= en.length && en.offset % 16 == 0 && en.offset >= end && en.offset <= blob_bytes &&
+            span <= blob_bytes - en.offset) {
+            end = en.offset + span;
+            continue;
+        }
+        *first_bad = k;
+        return false;
+    }
+    return true;
+}
+
+int refuse_structure(mi_ctx* c, const char* who, u64 blob_bytes, const mi_zpack_entry& en, u64 k) {
+    return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) is off the 16-byte grid, overlaps the entry before it, "
+                "leaves the blob of %llu bytes or states a stored size of 0 or above its length", who, (unsigned long long)k,
+                (unsigned long long)en.offset, en.stored, en.length, (unsigned long long)blob_bytes);
+}
+
+// The entries lie on the host, the compressed blob on the device (a copy into it may still be queued on the ctx stream): the
+// plain layout, the plain blob, the decode -- and the set takes it as it takes any plain blob (mi_packset_adopt)
+int add_compressed(mi_packset* s, mi_ctx* c, const char* who, const u8* d_zblob, const mi_zpack_entry* entries, u64 n, uint32_t flags,
+                   double ms_upload, u64* first_bad) {
+    hipStream_t st = c->stream;
+    std::vector<mi_pack_entry> plain(n);
+    std::vector<u64> p_off(n);
+    u64 plain_bytes = 0;
+    for (u64 k = 0; k < n; ++k) {
+        memcpy(plain[k].digest, entries[k].digest, 32);
+        plain[k].offset = p_off[k] = plain_bytes;
+        plain[k].chunk_index = entries[k].chunk_index;
+        plain[k].length = entries[k].length;
+        plain[k].reserved = 0;
+        plain_bytes += z_round16(entries[k].length);
+    }
+    DevBuf d_plain, d_rows, d_poff, d_rule, d_bad;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    const hipError_t e = alloc_exact(&d_plain, plain_bytes);
+    if (e != hipSuccess) return does_not_fit(c, who, "the plain blob", e, plain_bytes, n);
+    HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
+    HIPCHK(c, d_poff.ensure(n * 8));
+    HIPCHK(c, d_rule.ensure(n * 4));
+    HIPCHK(c, d_bad.ensure(8));
+    HIPCHK(c, hipMemcpyAsync(d_rows.p, entries, n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_poff.p, p_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(d_bad.p, 0xFF, 8, st));
+    hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, st, d_zblob, d_rows.as<u64>(), d_poff.as<u64>(), n, d_plain.as<u8>(),
+                       d_rule.as<u32>(), d_bad.as<u64>());
+    u64* h = c->h_word.as<u64>();
+    HIPCHK(c, hipMemcpyAsync(h, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    const u64 bad = h[0];
+    if (bad != kZNone) {                               // the plain blob goes with this frame: the set's table was not touched
+        u32 rule = 0;
+        if (bad < n) HIPCHK(c, hipMemcpy(&rule, d_rule.as<u32>() + bad, 4, hipMemcpyDeviceToHost));
+        if (first_bad) *first_bad = bad;
+        const mi_zpack_entry en = bad < n ? entries[bad] : mi_zpack_entry{};
+        return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) does not decode: %s", who, (unsigned long long)bad,
+                    (unsigned long long)en.offset, en.stored, en.length, mi_host::lz4_rule_name(rule));
+    }
+    return mi_packset_adopt(s, who, &d_plain, plain_bytes, plain.data(), n, flags, ms_upload, first_bad);
+}
+
+}  // namespace
+
+extern "C" {
+
+int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
+    if (out) *out = nullptr;
+    if (!p || !out) return MI_ERR_INVALID;
+    static const char* who = "mi_pack_compress";
+    mi_ctx* c = mi_pack_ctx(p);
+    if (flags & ~(uint32_t)MI_ZPACK_VERIFY) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    mi_pack_info pi;
+    const void* d_pack = nullptr;
+    u64 pack_bytes = 0;
+    int rc;
+    if ((rc = mi_pack_get_info(p, &pi)) || (rc = mi_pack_device(p, &d_pack, &pack_bytes))) return rc;
+    const u64 n = pi.n_entries;
+    HIPCHK(c, hipSetDevice(c->device));
+    struct Owned { mi_zpack* z = nullptr; ~Owned() { if (z) zpack_delete(z); } } mine;     // (drains the ctx stream before the blob goes)
+    mine.z = zpack_new(c);
+    if (n == 0) {                                          // a valid zpack of nothing
+        mine.z->info.verified = (flags & MI_ZPACK_VERIFY) ? 1 : 0;
+        *out = mine.z;
+        mine.z = nullptr;
+        return MI_OK;
+    }
+    if (n >> 32) return fail(c, MI_ERR_INVALID, "%s: %llu entries, a pack holds fewer than 2^32", who, (unsigned long long)n);
+    // the input's entries are on the host: the scratch spans' prefix sums are taken here
+    std::vector<mi_zpack_entry>& rows = mine.z->h_rows;
+    rows.resize(n);
+    static_assert(sizeof(mi_zpack_entry) == sizeof(mi_pack_entry), "one layout");
+    if ((rc = mi_pack_entries(p, (mi_pack_entry*)rows.data(), n))) return rc;
+    std::vector<u64> w_off(n);
+    u64 scratch_bytes = 0;
+    for (u64 k = 0; k < n; ++k) {
+        const u64 len = rows[k].length;
+        if (len == 0 || rows[k].offset % 16 || rows[k].offset > pack_bytes || z_round16(len) > pack_bytes - rows[k].offset)
+            return fail(c, MI_ERR_INVALID, "%s: entry %llu of the pack (offset %llu, %u bytes) has no bytes or leaves its blob of %llu bytes", who,
+                        (unsigned long long)k, (unsigned long long)rows[k].offset, rows[k].length, (unsigned long long)pack_bytes);
+        w_off[k] = scratch_bytes;
+        scratch_bytes += z_worst_span(len);
+    }
+    hipStream_t s = c->stream;
+    const u64 nb = (n + kZTile - 1) / kZTile;
+    DevBuf d_rows, d_woff, d_scratch, d_scan, e_src, e_len, e_dst, d_rule, d_got;
+    Event ev[7];
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    for (auto& e : ev) HIPCHK(c, e.create());
+    hipError_t e = alloc_exact(&d_scratch, scratch_bytes);
+    if (e != hipSuccess) return does_not_fit(c, who, "the coder's scratch", e, scratch_bytes, n);
+    HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
+    HIPCHK(c, d_woff.ensure(n * 8));
+    HIPCHK(c, d_scan.ensure((nb + 8) * 8));
+    u64* block_bytes = d_scan.as<u64>();
+    u64* totals = block_bytes + nb;                        // kZTot*
+    HIPCHK(c, hipMemcpyAsync(d_rows.p, rows.data(), n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemcpyAsync(d_woff.p, w_off.data(), n * 8, hipMemcpyHostToDevice, s));
+    HIPCHK(c, hipMemsetAsync(totals, 0, 4 * 8, s));
+    HIPCHK(c, hipMemsetAsync(totals + kZTotBad, 0xFF, 8, s));
+    HIPCHK(c, hipEventRecord(ev[0], s));
+    hipLaunchKernelGGL(zpack_encode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, (const u8*)d_pack, d_rows.as<u64>(), d_woff.as<u64>(),
+                       d_scratch.as<u8>(), n);
+    HIPCHK(c, hipEventRecord(ev[1], s));
+    hipLaunchKernelGGL(zpack_block_sums_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), n, block_bytes, totals);
+    hipLaunchKernelGGL(zpack_block_offsets_kernel, dim3(1), dim3(kZBlock), 0, s, block_bytes, nb, totals);
+    HIPCHK(c, hipEventRecord(ev[2], s));
+    u64* h = c->h_word.as<u64>();
+    HIPCHK(c, hipMemcpyAsync(h, totals, 4 * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    mi_zpack_info& zi = mine.z->info;
+    zi.n_entries = n;
+    zi.blob_bytes = h[kZTotBlob];
+    zi.stored_bytes = h[kZTotStored];
+    zi.n_raw = h[kZTotRaw];
+    zi.chunk_bytes = h[kZTotChunk];
+    const u64 blob_bytes = zi.blob_bytes;
+    if (blob_bytes < 16 * n || zi.stored_bytes > zi.chunk_bytes || zi.chunk_bytes != pi.chunk_bytes)
+        return fail(c, MI_ERR_HIP, "%s: the plan counted %llu stored bytes in a blob of %llu for %llu chunk bytes (the pack states %llu)", who,
+                    (unsigned long long)zi.stored_bytes, (unsigned long long)blob_bytes, (unsigned long long)zi.chunk_bytes,
+                    (unsigned long long)pi.chunk_bytes);
+    const u64 n_tiles = (blob_bytes + kZGatherTile - 1) / kZGatherTile;
+    if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
+    if ((e = alloc_exact(&mine.z->blob, blob_bytes)) != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
+    HIPCHK(c, e_src.ensure(n * 8));
+    HIPCHK(c, e_len.ensure(n * 8));
+    HIPCHK(c, e_dst.ensure(n * 8));
+    if (flags & MI_ZPACK_VERIFY) {
+        HIPCHK(c, d_rule.ensure(n * 4));
+        HIPCHK(c, d_got.ensure(n * 32));
+    }
+    HIPCHK(c, hipEventRecord(ev[3], s));
+    hipLaunchKernelGGL(zpack_place_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n, block_bytes,
+                       (u64)(size_t)d_pack, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
+    hipLaunchKernelGGL(zpack_gather_kernel, dim3((u32)n_tiles), dim3(kZWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n, blob_bytes,
+                       mine.z->blob.as<u8>());
+    HIPCHK(c, hipEventRecord(ev[4], s));
+    if (flags & MI_ZPACK_VERIFY) {
+        // the new blob decoded into the scratch spans (the gather has read them: same stream), hashed there.  The chunks' lengths
+        // for the launcher: e_len is free again
+        std::vector<u64> lens(n);
+        for (u64 k = 0; k < n; ++k) lens[k] = rows[k].length;
+        HIPCHK(c, hipMemcpyAsync(e_len.p, lens.data(), n * 8, hipMemcpyHostToDevice, s));
+        hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, mine.z->blob.as<u8>(), d_rows.as<u64>(), d_woff.as<u64>(), n,
+                           d_scratch.as<u8>(), d_rule.as<u32>(), totals + kZTotBad);
+        HIPCHK(c, hipEventRecord(ev[6], s));
+        const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
+        hash_items(kShaBlobs, d_scratch.as<u8>(), d_woff.as<u64>(), e_len.as<u64>(), nullptr, (u32)n, nullptr, c->heads.as<u32>(), nullptr, true,
+                   d_got.as<u8>(), c->sha, c->prop.multiProcessorCount, scratch_bytes, s);
+        hipLaunchKernelGGL(zpack_compare_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s, d_got.as<u8>(), d_rows.as<u64>(), n,
+                           totals + kZTotBad);
+        HIPCHK(c, hipMemcpyAsync(h, totals + kZTotBad, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIPCHK(c, hipEventRecord(ev[5], s));
+    // the entries to the host with the same synchronisation: mi_zpack_entries only reads from then on
+    HIPCHK(c, hipMemcpyAsync(rows.data(), d_rows.p, n * sizeof(mi_zpack_entry), hipMemcpyDeviceToHost, s));
+    HIPCHK(c, hipStreamSynchronize(s));
+    HIPCHK(c, hipGetLastError());
+    float ms = 0, ms2 = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    zi.ms_encode = ms;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev[1], ev[2]));
+    HIPCHK(c, hipEventElapsedTime(&ms2, ev[3], ev[4]));
+    zi.ms_compact = (double)ms + ms2;
+    if (flags & MI_ZPACK_VERIFY) {
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[4], ev[5]));
+        zi.ms_verify = ms;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[4], ev[6]));
+        zi.ms_decode = ms;
+        const u64 bad = h[0];
+        if (bad != kZNone) {
+            const mi_zpack_entry row = bad < n ? rows[bad] : mi_zpack_entry{};
+            return fail(c, MI_ERR_IO, "%s: entry %llu -- chunk row %llu, %u bytes stored for %u at blob offset %llu, digest %s -- does not decode on the "
+                        "device to bytes that hash to its digest", who, (unsigned long long)bad, (unsigned long long)row.chunk_index, row.stored,
+                        row.length, (unsigned long long)row.offset, hex32(row.digest).c_str());
+        }
+        zi.verified = 1;
+    }
+    *out = mine.z;
+    mine.z = nullptr;
+    return MI_OK;
+}
+
+int mi_zpack_get_info(const mi_zpack* z, mi_zpack_info* out) {
+    if (!z || !out) return MI_ERR_INVALID;
+    *out = z->info;
+    return MI_OK;
+}
+
+int mi_zpack_entries(const mi_zpack* z, mi_zpack_entry* out, uint64_t cap) {
+    if (!z || (!out && cap)) return MI_ERR_INVALID;
+    const u64 n = z->info.n_entries;
+    if (cap < n) return fail(z->ctx, MI_ERR_CAPACITY, "zpack entry buffer holds %llu rows, need %llu", (unsigned long long)cap, (unsigned long long)n);
+    if (n) memcpy(out, z->h_rows.data(), n * sizeof(mi_zpack_entry));
+    return MI_OK;
+}
+
+int mi_zpack_read(mi_zpack* z, uint64_t offset, void* dst, uint64_t len) {
+    if (!z || (!dst && len)) return MI_ERR_INVALID;
+    mi_ctx* c = z->ctx;
+    if (offset > z->info.blob_bytes || len > z->info.blob_bytes - offset)
+        return fail(c, MI_ERR_INVALID, "mi_zpack_read: [%llu, +%llu) is outside the blob of %llu bytes", (unsigned long long)offset,
+                    (unsigned long long)len, (unsigned long long)z->info.blob_bytes);
+    if (!len) return MI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    return z->reader.read(c, z->blob.as<u8>(), z->info.blob_bytes, offset, dst, len);
+}
+
+void mi_zpack_free(mi_zpack* z) {
+    if (z) zpack_delete(z);
+}
+
+int mi_packset_add_zblob(mi_packset* s, const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n, uint32_t flags,
+                         uint64_t* first_bad) {
+    if (first_bad) *first_bad = 0;
+    if (!s || (!blob && blob_bytes) || (!entries && n)) return MI_ERR_INVALID;
+    static const char* who = "mi_packset_add_zblob";
+    mi_ctx* c = nullptr;
+    const uint64_t* tags = nullptr;
+    const uint64_t* slots = nullptr;
+    u64 t_cap = 0;
+    int rc = mi_packset_table(s, who, &c, &tags, &slots, &t_cap);       // (a set in its sticky failed state: MI_ERR_STATE)
+    if (rc) return rc;
+    if (flags & ~(uint32_t)MI_PACKSET_VERIFY) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    if (n >> 32) return fail(c, MI_ERR_INVALID, "%s: %llu entries, a pack holds fewer than 2^32", who, (unsigned long long)n);
+    u64 bad = 0;
+    if (!structure_ok(blob_bytes, entries, n, &bad)) {                   // before a byte is uploaded
+        if (first_bad) *first_bad = bad;
+        return refuse_structure(c, who, blob_bytes, entries[bad], bad);
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return mi_packset_adopt(s, who, nullptr, 0, nullptr, 0, flags, 0, first_bad);
+    DevBuf d_zblob;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{c->stream};
+    const hipError_t e = d_zblob.ensure(blob_bytes);
+    if (e != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
+    double ms_upload = 0;
+    rc = mi_packset_upload(s, d_zblob.p, blob, blob_bytes, &ms_upload);
+    if (rc) return rc;
+    return add_compressed(s, c, who, d_zblob.as<u8>(), entries, n, flags, ms_upload, first_bad);
+}
+
+int mi_packset_add_zpack(mi_packset* s, const mi_zpack* z, uint32_t flags) {
+    if (!s || !z) return MI_ERR_INVALID;
+    static const char* who = "mi_packset_add_zpack";
+    mi_ctx* c = nullptr;
+    const uint64_t* tags = nullptr;
+    const uint64_t* slots = nullptr;
+    u64 t_cap = 0;
+    int rc = mi_packset_table(s, who, &c, &tags, &slots, &t_cap);
+    if (rc) return rc;
+    if (flags & ~(uint32_t)MI_PACKSET_VERIFY) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    if (z->ctx != c) return fail(c, MI_ERR_INVALID, "%s: the zpack belongs to another ctx; hand its bytes to mi_packset_add_zblob", who);
+    const u64 n = z->info.n_entries;
+    u64 bad = 0;
+    if (!structure_ok(z->info.blob_bytes, z->h_rows.data(), n, &bad)) return refuse_structure(c, who, z->info.blob_bytes, z->h_rows[bad], bad);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (n == 0) return mi_packset_adopt(s, who, nullptr, 0, nullptr, 0, flags, 0, nullptr);
+    return add_compressed(s, c, who, z->blob.as<u8>(), z->h_rows.data(), n, flags, 0, nullptr);       // decoded where it lies
+}
+
+// Host logic: what the pulling side runs before it trusts a zpack.  No ctx, no GPU.  The order the device path finds things
+// in: the structure of ALL entries first, then the first entry that does not decode (or whose pad is not zero), then the first
+// whose bytes do not hash to its digest
+int mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n, uint32_t alg, uint64_t* first_bad) {
+    if (first_bad) *first_bad = 0;
+    if ((!blob && blob_bytes) || (!entries && n)) return MI_ERR_INVALID;
+    if (alg != MI_DIGEST_SHA256 && alg != MI_DIGEST_BLAKE2S) return MI_ERR_INVALID;
+    u64 bad = 0;
+    if (n >> 32 || !structure_ok(blob_bytes, entries, n, &bad)) {
+        if (first_bad) *first_bad = bad;
+        return MI_ERR_INVALID;
+    }
+    const u8* base = (const u8*)blob;
+    std::vector<u8> plain;
+    u64 hash_bad = kZNone;
+    for (u64 k = 0; k < n; ++k) {
+        const mi_zpack_entry& en = entries[k];
+        const u8* src = base + en.offset;
+        const u8* chunk = src;
+        bool ok = true;
+        if (en.stored < en.length) {
+            plain.resize(en.length);
+            ok = mi_host::lz4_block_decode(src, en.stored, plain.data(), en.length) == mi_host::kLz4Ok;
+            chunk = plain.data();
+        }
+        for (u64 i = en.stored; i < z_round16(en.stored); ++i) ok = ok && src[i] == 0;
+        if (!ok) {                                     // the smallest entry that does not decode: nothing behind it matters
+            if (first_bad) *first_bad = k;
+            return MI_ERR_INVALID;
+        }
+        if (hash_bad != kZNone) continue;
+        u8 got[32];
+        if (alg == MI_DIGEST_BLAKE2S) {
+            mi_host::Blake2s hsh;
+            hsh.update(chunk, en.length);
+            hsh.final(got);
+        } else {
+            mi_host::Sha256 hsh;
+            hsh.update(chunk, en.length);
+            hsh.final(got);
+        }
+        if (memcmp(got, en.digest, 32) != 0) hash_bad = k;
+    }
+    if (hash_bad != kZNone) {
+        if (first_bad) *first_bad = hash_bad;
+        return MI_ERR_INVALID;
+    }
+    return MI_OK;
+}
+
+}  // extern "C"
