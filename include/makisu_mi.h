@@ -1220,6 +1220,67 @@ MI_BLOCK int  mi_packset_add_zpack(mi_packset* s, const mi_zpack* z, uint32_t fl
 MI_BLOCK int  mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n,
                              uint32_t alg, uint64_t* first_bad);
 
+/* ---- compressed pack sets: zpacks resident AS STORED, cut by digest and restored without recoding ------------------ *
+ * A chunk's stored form is a pure function of its bytes (every chunk is coded on its own), so a store server answers a want
+ * list by MOVING stored spans -- no decode, no parse -- and the result is byte for byte what mi_packset_pack followed by
+ * mi_pack_compress gives; a puller decodes every recipe row straight to its place in the arena, no plain blob in between.
+ *   mi_zset_create        a COMPRESSED PACK SET: a device hash table as mi_packset_create makes one (open addressing, the tag a
+ *                         digest's first 8 bytes, entries_hint sizes it, rebuilt at twice the size when it passes half full); a
+ *                         slot holds the digest, the device address of the stored span and length | stored << 32.  A child of
+ *                         its ctx: free it before mi_ctx_destroy, which refuses while one lives.
+ *   mi_zset_add_zblob     a zpack from host memory.  ALWAYS first, on the host: mi_packset_add_zblob's structural check, with
+ *                         its message and its *first_bad.  The blob goes up through two pinned windows of the set's own into
+ *                         device memory of its own (does not fit: MI_ERR_NOMEM naming both sizes, the set unchanged) and stays
+ *                         AS STORED.  A digest the set holds already is kept once, the first form wins; the same digest with
+ *                         another `length` fails the add with MI_ERR_INVALID and the set is unusable from then on (sticky:
+ *                         every later call is MI_ERR_STATE with that first message).  Without MI_ZSET_VERIFY no stream is
+ *                         decoded: what an unverified set costs is paid by its readers (below).  MI_ZSET_VERIFY: the blob is
+ *                         decoded on the device into a scratch laid out as a plain pack, hashed by the ctx's own hashing kernel
+ *                         and held against the entries; the scratch is freed before the call returns.  An entry that breaks a
+ *                         decoding rule, has a non-zero pad byte or does not hash to its digest is MI_ERR_INVALID with
+ *                         *first_bad = the entry mi_zpack_check names for the same input, the set unchanged.
+ *   mi_zset_add_zpack     the same for a zpack of the SAME ctx (a device-to-device copy); the zpack stays the caller's.
+ *   mi_zset_zpack         mi_packset_pack for stored forms: an ordinary mi_zpack of every distinct requested digest once, in
+ *                         order of first occurrence; entry k = {digest, offset, chunk_index = the request row of the first
+ *                         occurrence, length, stored} as the set holds them, entry k at the sum of the stored sizes before it,
+ *                         each rounded up to 16, the pad bytes ZERO whatever the source held.  Everything that takes a zpack
+ *                         takes it (mi_zpack_get_info, _entries, _read, _free, mi_packset_add_zpack, mi_zset_add_zpack); it
+ *                         owns a COPY and survives mi_zset_free.  mi_zpack_info: ms_encode is 0 (nothing is coded), ms_compact
+ *                         the device time of lookup, scan and gather.  MI_ERR_INVALID with *first_bad (may be NULL) = the
+ *                         smallest such row, the message giving row and digest: a digest the set lacks, a stated length of 0,
+ *                         a stated length other than the set's.  Fewer than 2^32 rows; n = 0: the empty zpack.  A blob that
+ *                         does not fit: MI_ERR_NOMEM naming both sizes, nothing has changed.  MI_ZPACK_VERIFY: the new blob is
+ *                         decoded and hashed as mi_pack_compress does it; an entry that does not decode or does not hash to
+ *                         the REQUESTED digest is MI_ERR_IO naming the request row (also in *first_bad), the entry's offset
+ *                         and the digest, and no zpack is returned.
+ *   mi_batch_add_zrecipes mi_batch_add_recipes from a compressed set, with its arguments, its placement, its errors and its
+ *                         stats (n_joined_units is 0, ms_assemble the one kernel's time): every row is decoded -- a raw row
+ *                         copied -- by one wave DIRECTLY to its byte position in the arena.  New: a row whose stored form does
+ *                         not decode under mi_zpack_check's rules (a non-zero pad byte among them) is MI_ERR_INVALID naming
+ *                         file, row within the file, digest and the rule; the smallest bad row is the one named.
+ *                         MI_RECIPE_VERIFY hashes the assembled ranges where they lie.  ANY failure leaves the batch as it was. */
+#define MI_ZSET_VERIFY 0x1u
+typedef struct mi_zset mi_zset;
+typedef struct {               /* 80 bytes */
+    uint64_t n_packs, n_entries, n_digests /* distinct */;
+    uint64_t blob_bytes;       /* stored spans held, each rounded up to 16: summed over the entries of every added zpack */
+    uint64_t stored_bytes;     /* sum of stored over the distinct digests */
+    uint64_t chunk_bytes;      /* sum of length over the distinct digests */
+    uint32_t alg /* MI_DIGEST_* of the ctx */, reserved;
+    double   ms_upload, ms_verify, ms_insert;      /* of the last add */
+} mi_zset_info;
+MI_BLOCK int  mi_zset_create(mi_ctx* ctx, uint64_t entries_hint, mi_zset** out);
+MI_BLOCK int  mi_zset_add_zblob(mi_zset* s, const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries,
+                                uint64_t n, uint32_t flags, uint64_t* first_bad);
+MI_BLOCK int  mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags);
+MI_BLOCK int  mi_zset_get_info(const mi_zset* s, mi_zset_info* out);
+MI_BLOCK void mi_zset_free(mi_zset* s);
+MI_BLOCK int  mi_zset_zpack(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                            uint32_t flags, mi_zpack** out, uint64_t* first_bad);
+MI_BLOCK int  mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, const uint64_t* n_chunks,
+                                    const uint8_t* digests, const uint32_t* lengths, const uint64_t* user_tags,
+                                    uint32_t flags, mi_recipe_stats* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -20,7 +20,8 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "SHA_LOADS_AUTO", "SHA_LOADS_LANE", "SHA_LOADS_COOP", "Digest", "digest_hex",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
-           "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check"]
+           "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
+           "ZSet", "ZSetInfo", "ZSET_VERIFY"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -175,6 +176,19 @@ class ZPackInfo(C.Structure):
     _fields_ = [("n_entries", C.c_uint64), ("blob_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64), ("stored_bytes", C.c_uint64),
                 ("n_raw", C.c_uint64), ("alg", C.c_uint32), ("verified", C.c_uint32), ("ms_encode", C.c_double),
                 ("ms_compact", C.c_double), ("ms_verify", C.c_double), ("ms_decode", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+ZSET_VERIFY = 0x1                        # mi_zset_add_*: the blob decoded into a scratch and hashed on the device before the set takes it
+
+
+class ZSetInfo(C.Structure):
+    """mi_zset_info."""
+    _fields_ = [("n_packs", C.c_uint64), ("n_entries", C.c_uint64), ("n_digests", C.c_uint64), ("blob_bytes", C.c_uint64),
+                ("stored_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64), ("alg", C.c_uint32), ("reserved", C.c_uint32),
+                ("ms_upload", C.c_double), ("ms_verify", C.c_double), ("ms_insert", C.c_double)]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -431,6 +445,13 @@ def load_library(rebuild=False):
         "mi_packset_add_zblob": ([vp, vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
         "mi_packset_add_zpack": ([vp, vp, C.c_uint32], C.c_int),
         "mi_zpack_check": ([vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
+        "mi_zset_create": ([vp, u64, C.POINTER(vp)], C.c_int),
+        "mi_zset_add_zblob": ([vp, vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
+        "mi_zset_add_zpack": ([vp, vp, C.c_uint32], C.c_int),
+        "mi_zset_get_info": ([vp, C.POINTER(ZSetInfo)], C.c_int),
+        "mi_zset_free": ([vp], None),
+        "mi_zset_zpack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
+        "mi_batch_add_zrecipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1336,6 +1357,73 @@ class PackSet:
         self.close()
 
 
+class ZSet:
+    """mi_zset_*: compressed packs resident on the engine's device AS STORED, addressed by digest (Engine.zset): what
+    ZSet.zpack cuts compressed sub-packs out of without a coder and what Batch.add_zrecipes decodes files from, row by row,
+    straight into the arena.  A child of its Engine."""
+
+    def __init__(self, engine, entries_hint=0):
+        self._eng = engine
+        self._lib = engine._lib
+        h = C.c_void_p()
+        engine._check(self._lib.mi_zset_create(engine._h, entries_hint, C.byref(h)))
+        self._h = h
+        engine._children.add(self)
+
+    def _raise(self, rc, first_bad=None):
+        err = MiError(rc, self._lib.mi_last_error(self._eng._h).decode())
+        if first_bad is not None:
+            err.first_bad = first_bad
+        raise err
+
+    def add_zblob(self, blob, entries, verify=False):
+        """mi_zset_add_zblob: a compressed pack from host memory (entries: ZPACK_ENTRY_DTYPE rows), kept as stored; verify:
+        decoded into a scratch and hashed on the device first.  A failure raises MiError with .first_bad = the entry named."""
+        b = np.frombuffer(blob, dtype=np.uint8) if not isinstance(blob, np.ndarray) else np.ascontiguousarray(blob).view(np.uint8)
+        e = np.ascontiguousarray(entries, dtype=ZPACK_ENTRY_DTYPE)
+        bad = C.c_uint64()
+        rc = self._lib.mi_zset_add_zblob(self._h, b.ctypes.data if b.size else None, b.size, e.ctypes.data if e.size else None, e.size,
+                                         ZSET_VERIFY if verify else 0, C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+
+    def add_zpack(self, zpack, verify=False):
+        """mi_zset_add_zpack: a ZPack of the same Engine, copied where it lies; the zpack stays the caller's"""
+        self._eng._check(self._lib.mi_zset_add_zpack(self._h, zpack._h, ZSET_VERIFY if verify else 0))
+
+    def zpack(self, digests, lengths=None, verify=False):
+        """mi_zset_zpack: a ZPack of every distinct requested digest once, in order of first occurrence, the stored forms moved
+        as they are -- byte for byte PackSet.pack(...).compress().  A failure raises MiError with .first_bad = the request row."""
+        d, ln = PackSet._request(digests, lengths)
+        n = len(d)
+        h, bad = C.c_void_p(), C.c_uint64()
+        rc = self._lib.mi_zset_zpack(self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n,
+                                     ZPACK_VERIFY if verify else 0, C.byref(h), C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+        return ZPack(self._eng, h)
+
+    @property
+    def info(self):
+        out = ZSetInfo()
+        self._eng._check(self._lib.mi_zset_get_info(self._h, C.byref(out)))
+        return out
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.mi_zset_free(self._h)
+            self._h = None
+
+    free = close
+    __del__ = close
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+
 def pack_check(blob, entries, alg=DIGEST_SHA256):
     """mi_pack_check (host logic, no GPU): None if the pack is sound, else the index of the first entry that is not -- off the
     16-byte grid, overlapping, past the end, a non-zero pad byte, a chunk that does not hash to its digest; an unknown alg
@@ -1474,6 +1562,11 @@ class Engine:
     def packset(self, entries_hint=0):
         """mi_packset_create: packs on this device, addressed by digest (the source of Batch.add_recipes)"""
         return PackSet(self, entries_hint)
+
+    def zset(self, entries_hint=0):
+        """mi_zset_create: compressed packs on this device as stored, addressed by digest (the source of ZSet.zpack and of
+        Batch.add_zrecipes)"""
+        return ZSet(self, entries_hint)
 
     # ---- native RCCL exchange (what a Go host would use; bench.py drives torch instead) ----
     @staticmethod
@@ -1720,6 +1813,14 @@ class Batch:
         """mi_batch_add_recipes: one file per recipe, assembled on the device from the pack set.  recipes: a list of (digests:
         (n, 32) uint8, lengths: n uint32) pairs, or of lists of (digest bytes, length) rows as a MEMFS_CHUNK_PACK commit's layer
         gives them under "chunks".  -> RecipeStats"""
+        return self._add_recipes(self._lib.mi_batch_add_recipes, packset, recipes, tags, verify)
+
+    def add_zrecipes(self, zset, recipes, tags=None, verify=False):
+        """mi_batch_add_zrecipes: add_recipes from a compressed set (Engine.zset): every row decoded by one wave straight to its
+        place in the arena, no plain blob in between.  -> RecipeStats"""
+        return self._add_recipes(self._lib.mi_batch_add_zrecipes, zset, recipes, tags, verify)
+
+    def _add_recipes(self, call, packset, recipes, tags, verify):
         dig, lens, counts = [], [], []
         for rec in recipes:
             if isinstance(rec, tuple) and len(rec) == 2 and not isinstance(rec[0], (bytes, bytearray)):
@@ -1740,10 +1841,9 @@ class Batch:
         if tg is not None and tg.size != cnt.size:
             raise ValueError("%d tags for %d recipes" % (tg.size, cnt.size))
         out = RecipeStats()
-        self._check(self._lib.mi_batch_add_recipes(self._h, packset._h, cnt.size, cnt.ctypes.data if cnt.size else None,
-                                                   d.ctypes.data if d.size else None, n.ctypes.data if n.size else None,
-                                                   tg.ctypes.data if tg is not None and tg.size else None, RECIPE_VERIFY if verify else 0,
-                                                   C.byref(out)))
+        self._check(call(self._h, packset._h, cnt.size, cnt.ctypes.data if cnt.size else None, d.ctypes.data if d.size else None,
+                         n.ctypes.data if n.size else None, tg.ctypes.data if tg is not None and tg.size else None,
+                         RECIPE_VERIFY if verify else 0, C.byref(out)))
         return out
 
     def add_tree(self, root, rel_base=None, blacklist=(), mode=TREE_CONTEXT):

@@ -82,6 +82,26 @@ MI_LOCAL int  mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ct
 MI_LOCAL int  mi_packset_upload(mi_packset* s, void* d_dst, const void* src, uint64_t bytes, double* ms);
 MI_LOCAL int  mi_packset_adopt(mi_packset* s, const char* who, void* blob, uint64_t blob_bytes, const mi_pack_entry* entries, uint64_t n,
                                uint32_t flags, double ms_upload, uint64_t* first_bad);
+// mi_zpack.hip, for mi_zset.hip.  The structural host check of a compressed add under `who` (MI_ERR_INVALID, *first_bad, the
+// message of mi_packset_add_zblob).  The decoding half of such an add: the compressed blob lies on the device, the entries on
+// the host, structurally sound, n > 0; plain_buf is a mi::DevBuf that receives the plain blob laid out as a pack's (exactly
+// *plain_bytes + the slack), plain[n] its entries; *bad = the smallest entry that breaks a decoding rule or has a non-zero pad
+// (~0: none) and *rule which one (mi_host::Lz4Rule) -- the caller words the refusal; ms_decode (may be NULL): the kernel's
+// time.  Blocking on the ctx stream; the plain blob does not fit: MI_ERR_NOMEM naming both sizes under `who`
+MI_LOCAL int  mi_zpack_structure(mi_ctx* ctx, const char* who, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n,
+                                 uint64_t* first_bad);
+MI_LOCAL int  mi_zpack_decode_plain(mi_ctx* ctx, const char* who, const void* d_zblob, const mi_zpack_entry* entries, uint64_t n,
+                                    void* plain_buf, uint64_t* plain_bytes, mi_pack_entry* plain, uint64_t* bad, uint32_t* rule,
+                                    double* ms_decode);
+// a zpack of n_entries rows and a blob of blob_bytes whose contents the CALLER writes on the ctx stream (mi_pack_alloc's
+// contract; n_entries = 0: the empty zpack, no blob), what the caller found out about it (ms_encode is 0: nothing was coded),
+// and a zpack where it lies: its ctx, its blob on the device and its rows on the host
+MI_LOCAL int  mi_zpack_alloc(mi_ctx* ctx, const char* who, uint64_t n_entries, uint64_t blob_bytes, mi_zpack** out, void** d_blob,
+                             mi_zpack_entry** h_rows);
+MI_LOCAL void mi_zpack_set_result(mi_zpack* z, uint64_t stored_bytes, uint64_t n_raw, uint64_t chunk_bytes, uint32_t verified,
+                                  double ms_compact, double ms_verify, double ms_decode);
+MI_LOCAL int  mi_zpack_device(const mi_zpack* z, mi_ctx** ctx, const void** d_blob, uint64_t* blob_bytes, const mi_zpack_entry** rows,
+                              uint64_t* n);
 // mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
 // it: what the arena holds stays, whichever kind it is)
 MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);

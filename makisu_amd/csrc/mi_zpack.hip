@@ -36,6 +36,7 @@
 // a scratch span.  The hashing of the verify pass reads up to 67 bytes behind the last scratch span: DevBuf's 256 bytes.
 #include "mi_internal.h"
 #include "mi_item_loads.h"
+#include "mi_lz4_wave.h"
 #include "host_blake2s.h"
 #include "host_lz4.h"
 #include "host_sha256.h"
@@ -65,8 +66,6 @@ constexpr int kZHashBits = 12;
 constexpr int kZTable = 1 << kZHashBits;                      // 32-bit positions: 16 KiB a wave
 constexpr u32 kZMinChunk = 13;                                // below: raw
 constexpr u32 kZMaxOffset = 65535;
-
-static __device__ __forceinline__ int z_first(u64 mask) { return __ffsll((unsigned long long)mask) - 1; }
 
 // `count` extension bytes for the value e behind a nibble of 15 (count = e / 255 + 1), by the wave
 static __device__ __forceinline__ void z_put_extension(u8* out, u32 e, int lane) {
@@ -381,56 +380,7 @@ void zpack_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ 
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------
-// the extension bytes behind a nibble of 15, 64 at a time; false: the span ended first (host_lz4.h lz4_extension)
-static __device__ __forceinline__ bool z_get_extension(const u8* __restrict__ src, u64 stored, u64* ip, u64* len, int lane) {
-    for (;;) {
-        const u64 idx = *ip + lane;
-        const bool in = idx < stored;
-        const u32 b = in ? src[idx] : 0u;
-        const u64 m = __ballot(!in || b != 255u);
-        if (m == 0) { *len += 255ull * 64; *ip += 64; continue; }
-        const int f = z_first(m);
-        if (*ip + f >= stored) { *len += 255ull * f; *ip += f; return false; }
-        *len += 255ull * f + __shfl(b, f);
-        *ip += f + 1;
-        return true;
-    }
-}
-
-// one LZ4 block src[0, stored) -> dst[0, n), by one wave, under host_lz4.h's rules: 0 or the rule that refuses it
-static __device__ __forceinline__ u32 z_decode_block(const u8* __restrict__ src, u64 stored, u8* dst, u64 n, int lane) {
-    u64 ip = 0, op = 0, seen = 0;                     // seen: the output below it is visible to every lane's loads
-    for (;;) {
-        if (ip >= stored) return mi_host::kLz4OutputShort;
-        const u32 token = src[ip++];
-        u64 lit = token >> 4;
-        if (lit == 15 && !z_get_extension(src, stored, &ip, &lit, lane)) return mi_host::kLz4ExtensionCut;
-        if (lit > stored - ip) return mi_host::kLz4LiteralsLeave;
-        if (lit > n - op) return mi_host::kLz4OutputPasses;
-        for (u64 i = lane; i < lit; i += 64) dst[op + i] = src[ip + i];
-        ip += lit;
-        op += lit;
-        if (ip == stored) return op == n ? mi_host::kLz4Ok : mi_host::kLz4OutputShort;
-        if (stored - ip < 2) return mi_host::kLz4ExtensionCut;
-        const u64 off = (u64)src[ip] | ((u64)src[ip + 1] << 8);
-        ip += 2;
-        if (off == 0) return mi_host::kLz4OffsetZero;
-        if (off > op) return mi_host::kLz4OffsetBeyond;
-        u64 len = token & 15u;
-        if (len == 15 && !z_get_extension(src, stored, &ip, &len, lane)) return mi_host::kLz4ExtensionCut;
-        len += 4;
-        if (len > n - op) return mi_host::kLz4OutputPasses;
-        // the match repeats the `off` bytes in front of op: every byte comes from [op - off, op), written before this match
-        if (op - off + (len < off ? len : off) > seen) {
-            __syncthreads();                          // the wave's earlier stores have landed
-            seen = op;
-        }
-        const u8* from = dst + (op - off);
-        for (u64 i = lane; i < len; i += 64) dst[op + i] = from[i < off ? i : (u32)i % (u32)off];
-        op += len;
-    }
-}
-
+// z_get_extension, z_decode_block: csrc/mi_lz4_wave.h (mi_zset.hip decodes with them too)
 // rows: the zpack's entries (offset into zblob | chunk_index | length, stored); p_off: where the plain chunk goes in `out`
 __global__ __launch_bounds__(64)
 void zpack_decode_kernel(const u8* __restrict__ zblob, const u64* __restrict__ rows, const u64* __restrict__ p_off, u64 n, u8* out,
@@ -627,42 +577,18 @@ int refuse_structure(mi_ctx* c, const char* who, u64 blob_bytes, const mi_zpack_
 }
 
 // The entries lie on the host, the compressed blob on the device (a copy into it may still be queued on the ctx stream): the
-// plain layout, the plain blob, the decode -- and the set takes it as it takes any plain blob (mi_packset_adopt)
+// plain layout, the plain blob, the decode (mi_zpack_decode_plain below) -- and the set takes it as it takes any plain blob
+// (mi_packset_adopt)
 int add_compressed(mi_packset* s, mi_ctx* c, const char* who, const u8* d_zblob, const mi_zpack_entry* entries, u64 n, uint32_t flags,
                    double ms_upload, u64* first_bad) {
-    hipStream_t st = c->stream;
     std::vector<mi_pack_entry> plain(n);
-    std::vector<u64> p_off(n);
-    u64 plain_bytes = 0;
-    for (u64 k = 0; k < n; ++k) {
-        memcpy(plain[k].digest, entries[k].digest, 32);
-        plain[k].offset = p_off[k] = plain_bytes;
-        plain[k].chunk_index = entries[k].chunk_index;
-        plain[k].length = entries[k].length;
-        plain[k].reserved = 0;
-        plain_bytes += z_round16(entries[k].length);
-    }
-    DevBuf d_plain, d_rows, d_poff, d_rule, d_bad;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
-    const hipError_t e = alloc_exact(&d_plain, plain_bytes);
-    if (e != hipSuccess) return does_not_fit(c, who, "the plain blob", e, plain_bytes, n);
-    HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
-    HIPCHK(c, d_poff.ensure(n * 8));
-    HIPCHK(c, d_rule.ensure(n * 4));
-    HIPCHK(c, d_bad.ensure(8));
-    HIPCHK(c, hipMemcpyAsync(d_rows.p, entries, n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemcpyAsync(d_poff.p, p_off.data(), n * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(d_bad.p, 0xFF, 8, st));
-    hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, st, d_zblob, d_rows.as<u64>(), d_poff.as<u64>(), n, d_plain.as<u8>(),
-                       d_rule.as<u32>(), d_bad.as<u64>());
-    u64* h = c->h_word.as<u64>();
-    HIPCHK(c, hipMemcpyAsync(h, d_bad.p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipStreamSynchronize(st));
-    HIPCHK(c, hipGetLastError());
-    const u64 bad = h[0];
+    DevBuf d_plain;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{c->stream};   // (goes first: the buffer above after it)
+    u64 plain_bytes = 0, bad = kZNone;
+    u32 rule = 0;
+    const int rc = mi_zpack_decode_plain(c, who, d_zblob, entries, n, &d_plain, &plain_bytes, plain.data(), &bad, &rule, nullptr);
+    if (rc) return rc;
     if (bad != kZNone) {                               // the plain blob goes with this frame: the set's table was not touched
-        u32 rule = 0;
-        if (bad < n) HIPCHK(c, hipMemcpy(&rule, d_rule.as<u32>() + bad, 4, hipMemcpyDeviceToHost));
         if (first_bad) *first_bad = bad;
         const mi_zpack_entry en = bad < n ? entries[bad] : mi_zpack_entry{};
         return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) does not decode: %s", who, (unsigned long long)bad,
@@ -674,6 +600,112 @@ int add_compressed(mi_packset* s, mi_ctx* c, const char* who, const u8* d_zblob,
 }  // namespace
 
 extern "C" {
+
+// (hidden: mi_local.h) the decoding half of a compressed add, for mi_packset_add_z* here and for mi_zset.hip's verifications
+int mi_zpack_decode_plain(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpack_entry* entries, uint64_t n, void* plain_buf,
+                          uint64_t* plain_bytes_out, mi_pack_entry* plain, uint64_t* bad_out, uint32_t* rule_out, double* ms_decode) {
+    if (!c || !who || !d_zblob || !entries || !n || !plain_buf || !plain_bytes_out || !plain || !bad_out || !rule_out) return MI_ERR_INVALID;
+    hipStream_t st = c->stream;
+    DevBuf* d_plain = (DevBuf*)plain_buf;
+    std::vector<u64> p_off(n);
+    u64 plain_bytes = 0;
+    for (u64 k = 0; k < n; ++k) {
+        memcpy(plain[k].digest, entries[k].digest, 32);
+        plain[k].offset = p_off[k] = plain_bytes;
+        plain[k].chunk_index = entries[k].chunk_index;
+        plain[k].length = entries[k].length;
+        plain[k].reserved = 0;
+        plain_bytes += z_round16(entries[k].length);
+    }
+    *plain_bytes_out = plain_bytes;
+    *bad_out = kZNone;
+    *rule_out = 0;
+    DevBuf d_rows, d_poff, d_rule, d_bad;
+    Event ev[2];
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    const hipError_t e = alloc_exact(d_plain, plain_bytes);
+    if (e != hipSuccess) return does_not_fit(c, who, "the plain blob", e, plain_bytes, n);
+    for (auto& v : ev) HIPCHK(c, v.create());
+    HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
+    HIPCHK(c, d_poff.ensure(n * 8));
+    HIPCHK(c, d_rule.ensure(n * 4));
+    HIPCHK(c, d_bad.ensure(8));
+    HIPCHK(c, hipMemcpyAsync(d_rows.p, entries, n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemcpyAsync(d_poff.p, p_off.data(), n * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(d_bad.p, 0xFF, 8, st));
+    HIPCHK(c, hipEventRecord(ev[0], st));
+    hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, st, (const u8*)d_zblob, d_rows.as<u64>(), d_poff.as<u64>(), n,
+                       d_plain->as<u8>(), d_rule.as<u32>(), d_bad.as<u64>());
+    HIPCHK(c, hipEventRecord(ev[1], st));
+    u64* h = c->h_word.as<u64>();
+    HIPCHK(c, hipMemcpyAsync(h, d_bad.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    if (ms_decode) {
+        float ms = 0;
+        HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+        *ms_decode = ms;
+    }
+    const u64 bad = h[0];
+    if (bad != kZNone) {
+        u32 rule = 0;
+        if (bad < n) HIPCHK(c, hipMemcpy(&rule, d_rule.as<u32>() + bad, 4, hipMemcpyDeviceToHost));
+        *bad_out = bad;
+        *rule_out = rule;
+    }
+    return MI_OK;
+}
+
+// (hidden: mi_local.h) the structural host check every compressed add begins with, in mi_packset_add_zblob's words
+int mi_zpack_structure(mi_ctx* c, const char* who, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n, uint64_t* first_bad) {
+    u64 bad = 0;
+    if (structure_ok(blob_bytes, entries, n, &bad)) return MI_OK;
+    if (first_bad) *first_bad = bad;
+    return refuse_structure(c, who, blob_bytes, entries[bad], bad);
+}
+
+// (hidden: mi_local.h) a zpack whose blob and rows the caller writes (mi_zset.hip's cut), and what the caller found out about it
+int mi_zpack_alloc(mi_ctx* c, const char* who, uint64_t n_entries, uint64_t blob_bytes, mi_zpack** out, void** d_blob, mi_zpack_entry** h_rows) {
+    if (!c || !who || !out || !d_blob || !h_rows) return MI_ERR_INVALID;
+    *out = nullptr;
+    mi_zpack* z = zpack_new(c);
+    z->h_rows.resize(n_entries);
+    const hipError_t e = n_entries ? alloc_exact(&z->blob, blob_bytes) : hipSuccess;
+    if (e != hipSuccess) {
+        zpack_delete(z);
+        return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n_entries);
+    }
+    z->info.n_entries = n_entries;
+    z->info.blob_bytes = blob_bytes;
+    *out = z;
+    *d_blob = z->blob.p;
+    *h_rows = z->h_rows.data();
+    return MI_OK;
+}
+
+void mi_zpack_set_result(mi_zpack* z, uint64_t stored_bytes, uint64_t n_raw, uint64_t chunk_bytes, uint32_t verified, double ms_compact,
+                         double ms_verify, double ms_decode) {
+    mi_zpack_info& zi = z->info;
+    zi.stored_bytes = stored_bytes;
+    zi.n_raw = n_raw;
+    zi.chunk_bytes = chunk_bytes;
+    zi.verified = verified;
+    zi.ms_encode = 0;
+    zi.ms_compact = ms_compact;
+    zi.ms_verify = ms_verify;
+    zi.ms_decode = ms_decode;
+}
+
+// (hidden: mi_local.h) a zpack where it lies: its ctx, its blob on the device (NULL for an empty one) and its rows on the host
+int mi_zpack_device(const mi_zpack* z, mi_ctx** ctx, const void** d_blob, uint64_t* blob_bytes, const mi_zpack_entry** rows, uint64_t* n) {
+    if (!z || !ctx || !d_blob || !blob_bytes || !rows || !n) return MI_ERR_INVALID;
+    *ctx = z->ctx;
+    *d_blob = z->blob.p;
+    *blob_bytes = z->info.blob_bytes;
+    *rows = z->h_rows.data();
+    *n = z->info.n_entries;
+    return MI_OK;
+}
 
 int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     if (out) *out = nullptr;
