@@ -908,6 +908,15 @@ MI_CORE int  mi_memfs_commit_stats(const mi_memfs* fs, mi_commit_stats* out);
  * windows (n_windows > 0) succeeds as before and has no pack (take: MI_ERR_STATE); a pack that cannot be built (MI_ERR_NOMEM) does
  * not fail the commit -- the layer is written -- and the take returns the error.  Without the option nothing changes.       */
 #define MI_MEMFS_CHUNK_PACK 0x2u
+/* MI_MEMFS_CHUNK_ZPACK: MI_MEMFS_CHUNK_PACK in every respect but the product -- the same rows (known[i] == 0 and dup_of < 0), the
+ * same recipes (mi_copy_layer_chunks works under either option), the same refusals (no index: MI_ERR_STATE; n_ctx > 1:
+ * MI_ERR_INVALID; both before anything is walked), a commit in windows succeeds and has no zpack (take: MI_ERR_STATE with the
+ * reason), a zpack that cannot be built does not fail the commit -- but the chunks are coded straight from the batch's arena into a
+ * COMPRESSED pack (mi_batch_zpack_chunks with MI_ZPACK_VERIFY, while the handle's batch still holds the tree's bytes), which
+ * mi_memfs_take_zpack hands over: byte for byte what mi_memfs_take_pack followed by mi_pack_compress gives.  Setting BOTH options
+ * is MI_ERR_INVALID from mi_memfs_set_options: mi_pack_compress, or a decode, makes the other form; the commit does not do the
+ * work twice.                                                                                                              */
+#define MI_MEMFS_CHUNK_ZPACK 0x4u
 MI_CORE int  mi_memfs_set_options(mi_memfs* fs, uint32_t options);
 /* From now on every content-aware commit of this handle adds its batch to `index` (NULL: stop).  The index must belong
  * to the ctx the commits run on and outlive them; the handle does not own it.                                          */
@@ -1280,6 +1289,45 @@ MI_BLOCK int  mi_zset_zpack(const mi_zset* s, const uint8_t* digests, const uint
 MI_BLOCK int  mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, const uint64_t* n_chunks,
                                     const uint8_t* digests, const uint32_t* lengths, const uint64_t* user_tags,
                                     uint32_t flags, mi_recipe_stats* stats_out);
+
+/* ---- zpacks straight from the arena; a compressed set asked what it lacks ------------------------------------------ *
+ * The producing side without the plain detour: the chunks of a batch are coded WHERE THEY LIE, so a commit hands a zpack over
+ * without the plain blob, its gather and its hashing pass; and the pulling side asks the compressed set it keeps.  With both,
+ * the compressed line needs no plain pack anywhere: commit -> zpack -> mi_zset_add_* -> mi_zset_zpack (the want list's cut) ->
+ * mi_zset_missing / mi_batch_add_zrecipes on the puller.
+ *   mi_batch_zpack_chunks mi_batch_pack_chunks' arguments and state rules, word for word: select: n_select flags in host memory,
+ *                         n_select = the batch's chunk count, NULL = every row, non-zero bytes count as set; a wrong n_select,
+ *                         a group head or unknown flags: MI_ERR_INVALID; a batch that has not run or is in flight:
+ *                         MI_ERR_STATE; 2^32 or more entries: MI_ERR_INVALID; an empty selection: a zpack of 0 entries.  The
+ *                         result is an ORDINARY mi_zpack, byte for byte (blob and entries) what mi_batch_pack_chunks +
+ *                         mi_pack_compress gives for the same selection: chunk_index is the batch row; a child of the batch's
+ *                         ctx that survives mi_batch_reset and mi_batch_free; everything that takes a zpack takes it.  Blocking,
+ *                         on the ctx stream; the batch is not changed.  The call needs the coder's scratch (the sum of the
+ *                         worst-case spans: the selected bytes + 0.4 % + up to 31 bytes a chunk) and the blob; if either does
+ *                         not fit: MI_ERR_NOMEM naming the size and what the device has free, nothing has changed, the caller
+ *                         splits the selection.  MI_ZPACK_VERIFY (the only flag): the new blob is decoded again on the device
+ *                         into the scratch, hashed by the ctx's own hashing kernel and held against THE BATCH'S digest table at
+ *                         chunk_index -- one decode and one hashing pass vouch for both hops, arena -> stored form -> plain
+ *                         again; an entry that differs or does not decode is MI_ERR_IO naming the entry, the chunk row, the
+ *                         arena offset, the blob offset and the digest, and no zpack is returned.  mi_zpack_info: ms_encode the
+ *                         coder's time, ms_compact plan + layout + gather, ms_verify / ms_decode as for mi_pack_compress.
+ *   mi_memfs_take_zpack   the zpack of the handle's last commit (MI_MEMFS_CHUNK_ZPACK); the caller owns it (mi_zpack_free).
+ *                         MI_ERR_STATE with no commit since the last take, and after a commit in windows; the zpack's own
+ *                         error if it could not be built (mi_memfs_error says why).  A zpack nobody took is freed by the next
+ *                         commit.
+ *   mi_zset_missing       mi_packset_missing's contract, word for word, over a compressed set: held (optional, n bytes): 1
+ *                         where the set holds the row's digest; want_rows (cap rows of room): the rows at which a digest the
+ *                         set lacks occurs for the FIRST time, ascending; cap < n_want: nothing is written to want_rows and the
+ *                         call is MI_ERR_CAPACITY with held and *info filled; cap = 0 with want_rows = NULL is the sizing call
+ *                         and MI_OK.  With lengths: a row of length 0 is MI_ERR_INVALID; a digest the set holds with another
+ *                         length than the row states is MI_ERR_INVALID naming the smallest such row, its digest and both
+ *                         lengths.  held_bytes is the sum of the set's PLAIN lengths.  A set in its sticky failed state:
+ *                         MI_ERR_STATE with the first message; fewer than 2^32 rows; n = 0: MI_OK, *info zero.  Blocking, on
+ *                         the ctx stream; the set is not changed.                                                        */
+MI_BLOCK int  mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select, uint32_t flags, mi_zpack** out);
+MI_BLOCK int  mi_memfs_take_zpack(mi_memfs* fs, mi_zpack** out);
+MI_BLOCK int  mi_zset_missing(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                              uint8_t* held, uint64_t* want_rows, uint64_t cap, mi_want_info* info);
 
 #ifdef __cplusplus
 }

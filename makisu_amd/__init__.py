@@ -21,7 +21,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
-           "ZSet", "ZSetInfo", "ZSET_VERIFY"]
+           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -109,6 +109,7 @@ class LayerConfig(C.Structure):
 LAYER_MODE_WITH_TYPE = 0x1
 MEMFS_TRUST_CTIME = 0x1
 MEMFS_CHUNK_PACK = 0x2                   # a commit also packs the chunks its index did not know (MemFS.take_pack) and keeps the recipes
+MEMFS_CHUNK_ZPACK = 0x4                  # ... codes them straight from the arena into a compressed pack instead (MemFS.take_zpack)
 PACK_VERIFY = 0x1                        # mi_batch_pack_chunks: hash the blob again on the device
 
 
@@ -452,6 +453,9 @@ def load_library(rebuild=False):
         "mi_zset_free": ([vp], None),
         "mi_zset_zpack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
         "mi_batch_add_zrecipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
+        "mi_batch_zpack_chunks": ([vp, vp, u64, C.c_uint32, C.POINTER(vp)], C.c_int),
+        "mi_memfs_take_zpack": ([vp, C.POINTER(vp)], C.c_int),
+        "mi_zset_missing": ([vp, vp, vp, u64, vp, vp, u64, C.POINTER(WantInfo)], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -783,6 +787,7 @@ class MemFS:
             raise MiError(rc, "mi_memfs_create: unable to stat root dir: %s" % root)
         self.root, self.blacklist = root, list(blacklist)
         self._chunk_pack = False                              # set_options(chunk_pack=True)
+        self._chunk_zpack = False                             # set_options(chunk_zpack=True)
         self._pack_engine = None                              # the Engine of the last commit that could make a pack: take_pack's Pack is its child
 
     def _check(self, rc, what):
@@ -872,7 +877,7 @@ class MemFS:
                                                           C.byref(res), hp, C.byref(done)), "mi_memfs_commit_layer_n")
         else:
             ctx = engine._h if engine is not None else None
-            if engine is not None and self._chunk_pack:
+            if engine is not None and (self._chunk_pack or self._chunk_zpack):
                 self._pack_engine = engine                    # only such a commit makes (or drops) the handle's pack
             if engine is not None:
                 engine._children.add(self)                    # the handle keeps a batch of that ctx: given back before it dies
@@ -882,7 +887,7 @@ class MemFS:
             return None
         return {"tar_digest": Digest.from_raw(res.tar_sha256), "gzip_digest": Digest.from_raw(res.gzip_sha256),
                 "tar_bytes": res.tar_bytes, "gzip_bytes": res.gzip_bytes, "n_entries": res.n_entries,
-                "layer": _take_copy_layer(self._lib, h, int(res.n_entries), self._chunk_pack) if want_layer else None, "stats": self.commit_stats()}
+                "layer": _take_copy_layer(self._lib, h, int(res.n_entries), self._chunk_pack or self._chunk_zpack) if want_layer else None, "stats": self.commit_stats()}
 
     def commit_stats(self):
         st = CommitStats()
@@ -899,19 +904,27 @@ class MemFS:
         engine._children.add(self)
         self._check(self._lib.mi_memfs_reserve_device(self._h, engine._h, files, nbytes), "mi_memfs_reserve_device")
 
-    def set_options(self, trust_ctime=False, chunk_pack=False):
+    def set_options(self, trust_ctime=False, chunk_pack=False, chunk_zpack=False):
         """MI_MEMFS_TRUST_CTIME: scan commits do not read files again whose inode is what it was when they were hashed.
         MI_MEMFS_CHUNK_PACK: a commit (one Engine, an index set) also packs the chunks the index did not know -- take_pack() --
-        and its layer's regular files carry "chunks": [(digest, length), ...], their recipes"""
-        self._check(self._lib.mi_memfs_set_options(self._h, (MEMFS_TRUST_CTIME if trust_ctime else 0) | (MEMFS_CHUNK_PACK if chunk_pack else 0)),
-                    "mi_memfs_set_options")
-        self._chunk_pack = bool(chunk_pack)
+        and its layer's regular files carry "chunks": [(digest, length), ...], their recipes.
+        MI_MEMFS_CHUNK_ZPACK: the same with the chunks coded straight from the arena into a compressed pack -- take_zpack();
+        both at once are refused (MI_ERR_INVALID)"""
+        self._check(self._lib.mi_memfs_set_options(self._h, (MEMFS_TRUST_CTIME if trust_ctime else 0) | (MEMFS_CHUNK_PACK if chunk_pack else 0) |
+                                                   (MEMFS_CHUNK_ZPACK if chunk_zpack else 0)), "mi_memfs_set_options")
+        self._chunk_pack, self._chunk_zpack = bool(chunk_pack), bool(chunk_zpack)
 
     def take_pack(self):
         """mi_memfs_take_pack: the Pack of the last commit made with chunk_pack, a child of the Engine that commit ran on"""
         h = C.c_void_p()
         self._check(self._lib.mi_memfs_take_pack(self._h, C.byref(h)), "mi_memfs_take_pack")
         return Pack(self._pack_engine, h)
+
+    def take_zpack(self):
+        """mi_memfs_take_zpack: the ZPack of the last commit made with chunk_zpack, a child of the Engine that commit ran on"""
+        h = C.c_void_p()
+        self._check(self._lib.mi_memfs_take_zpack(self._h, C.byref(h)), "mi_memfs_take_zpack")
+        return ZPack(self._pack_engine, h)
 
     def release_device(self):
         if self._h:
@@ -1403,6 +1416,25 @@ class ZSet:
             self._raise(rc, bad.value)
         return ZPack(self._eng, h)
 
+    def missing(self, digests, lengths=None):
+        """mi_zset_missing: PackSet.missing over the compressed set -- which of the request's digests (n x 32 bytes; lengths:
+        n or None) the set lacks.  -> (held: uint8[n], want_rows: uint64[n_want] -- the rows of first occurrence of every
+        missing digest, ascending --, WantInfo with held_bytes = the set's PLAIN lengths)"""
+        d, ln = PackSet._request(digests, lengths)
+        n = len(d)
+        args = (self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n)
+        held = np.zeros(max(n, 1), dtype=np.uint8)
+        info = WantInfo()
+        rc = self._lib.mi_zset_missing(*args, held.ctypes.data, None, 0, C.byref(info))          # the sizing call
+        if rc:
+            self._raise(rc)
+        want = np.zeros(max(info.n_want, 1), dtype=np.uint64)
+        if info.n_want:
+            rc = self._lib.mi_zset_missing(*args, held.ctypes.data, want.ctypes.data, info.n_want, C.byref(info))
+            if rc:
+                self._raise(rc)
+        return held[:n], want[:info.n_want], info
+
     @property
     def info(self):
         out = ZSetInfo()
@@ -1808,6 +1840,18 @@ class Batch:
             ptr, n = sel.ctypes.data, len(select)
         self._check(self._lib.mi_batch_pack_chunks(self._h, ptr, n, PACK_VERIFY if verify else 0, C.byref(h)))
         return Pack(self.engine, h)
+
+    def zpack(self, select=None, verify=False):
+        """mi_batch_zpack_chunks: pack(select).compress() without the plain pack -- the selected rows coded where they lie in
+        the arena, byte for byte the same ZPack; verify: decoded again and held against the batch's own digests"""
+        h = C.c_void_p()
+        ptr, n = None, 0
+        if select is not None:
+            sel = np.zeros(max(len(select), 1), dtype=np.uint8)      # (never NULL: NULL means every row)
+            sel[:len(select)] = np.asarray(select) != 0
+            ptr, n = sel.ctypes.data, len(select)
+        self._check(self._lib.mi_batch_zpack_chunks(self._h, ptr, n, ZPACK_VERIFY if verify else 0, C.byref(h)))
+        return ZPack(self.engine, h)
 
     def add_recipes(self, packset, recipes, tags=None, verify=False):
         """mi_batch_add_recipes: one file per recipe, assembled on the device from the pack set.  recipes: a list of (digests:

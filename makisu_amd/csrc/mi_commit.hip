@@ -37,8 +37,16 @@ static void memfs_pack_drop(mi_memfs* m, int rc, const std::string& why) {
     m->pack_rc = rc;
     m->pack_err = why;
 }
+// MI_MEMFS_CHUNK_ZPACK: the same for the compressed pack
+static void memfs_zpack_drop(mi_memfs* m, int rc, const std::string& why) {
+    if (m->zpack) mi_zpack_free(m->zpack);
+    m->zpack = nullptr;
+    m->zpack_rc = rc;
+    m->zpack_err = why;
+}
 static int memfs_batch_drop(mi_memfs* m) {
     memfs_pack_drop(m, MI_ERR_STATE, "no commit since the device was released");      // (a pack is a child of the ctx, as the batch is)
+    memfs_zpack_drop(m, MI_ERR_STATE, "no commit since the device was released");
     int rc = MI_OK;
     if (m->batch) rc = mi_batch_free(m->batch);
     m->batch = nullptr;
@@ -456,7 +464,7 @@ struct Commit {
                     for (uint64_t i = 0; i < nc; ++i)
                         if (!known[i] && rows[i].dup_of < 0) m->last.index_new_bytes += rows[i].length;
                 }
-                if (!rc && m->chunk_pack && !windowed) pack_and_recipes(mb, rows, nc, known.data());     // (one ctx: one member)
+                if (!rc && (m->chunk_pack || m->chunk_zpack) && !windowed) pack_and_recipes(mb, rows, nc, known.data());     // (one ctx: one member)
             }
             if (rc) m->err = std::string("failed to generate diff layer: chunk index: ") + mi_last_error(ctx);
         } else if (b && m->chunk_pack && !windowed) {                             // nothing was scanned: a pack of nothing
@@ -469,18 +477,39 @@ struct Commit {
         if (b && m->chunk_pack && windowed)
             memfs_pack_drop(m, MI_ERR_STATE, "the last commit's tree did not fit the device and was scanned in " + std::to_string(m->last.n_windows) +
                                              " windows: no batch holds its bytes, there is no pack (packs window by window are not built)");
+        if (b && m->chunk_zpack && !windowed && !(m->index && m->last.n_scanned_files)) {      // nothing was scanned: a zpack of nothing
+            mi_zpack* z = nullptr;
+            void* d_blob = nullptr;
+            mi_zpack_entry* h_rows = nullptr;
+            const int zrc = mi_zpack_alloc(ctx, "mi_memfs_commit_layer", 0, 0, &z, &d_blob, &h_rows);
+            if (!zrc) mi_zpack_set_result(z, 0, 0, 0, 1, 0, 0, 0);
+            memfs_zpack_drop(m, zrc, zrc ? "the empty zpack of a commit that scanned nothing" : "");
+            m->zpack = z;
+            cl->chunk_first.assign(cl->nodes.size() + 1, 0);
+        }
+        if (b && m->chunk_zpack && windowed)
+            memfs_zpack_drop(m, MI_ERR_STATE, "the last commit's tree did not fit the device and was scanned in " + std::to_string(m->last.n_windows) +
+                                              " windows: no batch holds its bytes, there is no zpack (packs window by window are not built)");
         return rc;
     }
     // MI_MEMFS_CHUNK_PACK: the rows whose bytes index_new_bytes counts as ONE blob (mi_batch_pack_chunks with MI_PACK_VERIFY: the
     // batch still holds the tree's bytes), and every layer file's ordered chunks.  A pack that cannot be built does not fail the
-    // commit -- the layer is written: mi_memfs_take_pack returns the error and the message.
+    // commit -- the layer is written: mi_memfs_take_pack returns the error and the message.  MI_MEMFS_CHUNK_ZPACK: the same rows
+    // coded straight from the arena (mi_batch_zpack_chunks with MI_ZPACK_VERIFY), the same recipes.
     void pack_and_recipes(mi_batch* mb, const mi_chunk_result* rows, uint64_t nc, const uint8_t* known) {
         std::vector<uint8_t> select(nc ? nc : 1);
         for (uint64_t i = 0; i < nc; ++i) select[i] = !known[i] && rows[i].dup_of < 0;
-        mi_pack* p = nullptr;
-        const int prc = mi_batch_pack_chunks(mb, select.data(), nc, MI_PACK_VERIFY, &p);
-        memfs_pack_drop(m, prc, prc ? std::string("chunk pack: ") + mi_last_error(ctx) : std::string());
-        m->pack = p;
+        if (m->chunk_zpack) {
+            mi_zpack* z = nullptr;
+            const int zrc = mi_batch_zpack_chunks(mb, select.data(), nc, MI_ZPACK_VERIFY, &z);
+            memfs_zpack_drop(m, zrc, zrc ? std::string("chunk zpack: ") + mi_last_error(ctx) : std::string());
+            m->zpack = z;
+        } else {
+            mi_pack* p = nullptr;
+            const int prc = mi_batch_pack_chunks(mb, select.data(), nc, MI_PACK_VERIFY, &p);
+            memfs_pack_drop(m, prc, prc ? std::string("chunk pack: ") + mi_last_error(ctx) : std::string());
+            m->pack = p;
+        }
         const mi_file_result* files = nullptr;
         uint64_t nf = 0;
         cl->chunk_first.assign(cl->nodes.size() + 1, 0);
@@ -561,6 +590,11 @@ static int memfs_commit(mi_memfs* m, mi_ctx* const* ctxs, uint32_t n_ctx, int mu
         if (n_ctx > 1) { m->err = "failed to generate diff layer: chunk pack: a pack over several GPUs' arenas is not built (MI_MEMFS_CHUNK_PACK with n_ctx > 1)"; return MI_ERR_INVALID; }
         memfs_pack_drop(m, MI_ERR_STATE, "the last commit made no pack");         // (an earlier commit's pack nobody took goes)
     }
+    if (n_ctx && m->chunk_zpack) {                                                // MI_MEMFS_CHUNK_ZPACK: the same refusals
+        if (!m->index) { m->err = "failed to generate diff layer: chunk zpack: MI_MEMFS_CHUNK_ZPACK packs the chunks the index did not know: set one first (mi_memfs_set_index)"; return MI_ERR_STATE; }
+        if (n_ctx > 1) { m->err = "failed to generate diff layer: chunk zpack: a pack over several GPUs' arenas is not built (MI_MEMFS_CHUNK_ZPACK with n_ctx > 1)"; return MI_ERR_INVALID; }
+        memfs_zpack_drop(m, MI_ERR_STATE, "the last commit made no zpack");       // (an earlier commit's zpack nobody took goes)
+    }
     Commit c(m, ctxs, n_ctx, must_scan != 0, ops, n_ops);
     int rc = c.open_batch();
     if (!rc && n_ctx) m->root_alg = (int)alg;                                     // (from here on roots of this algorithm may land)
@@ -601,9 +635,27 @@ extern "C" int mi_memfs_commit_stats(const mi_memfs* m, mi_commit_stats* out) {
     return MI_OK;
 }
 extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
-    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK))) return MI_ERR_INVALID;
+    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK | MI_MEMFS_CHUNK_ZPACK))) return MI_ERR_INVALID;
+    if ((options & MI_MEMFS_CHUNK_PACK) && (options & MI_MEMFS_CHUNK_ZPACK)) {    // mi_pack_compress, or a decode, makes the other form
+        m->err = "mi_memfs_set_options: MI_MEMFS_CHUNK_PACK and MI_MEMFS_CHUNK_ZPACK exclude each other: the commit does not do the work twice";
+        return MI_ERR_INVALID;
+    }
     m->fs.trust_ctime = (options & MI_MEMFS_TRUST_CTIME) != 0;
     m->chunk_pack = (options & MI_MEMFS_CHUNK_PACK) != 0;
+    m->chunk_zpack = (options & MI_MEMFS_CHUNK_ZPACK) != 0;
+    return MI_OK;
+}
+extern "C" int mi_memfs_take_zpack(mi_memfs* m, mi_zpack** out) {
+    if (!m || !out) return MI_ERR_INVALID;
+    *out = nullptr;
+    if (!m->zpack) {
+        m->err = "mi_memfs_take_zpack: " + m->zpack_err;
+        return m->zpack_rc ? m->zpack_rc : MI_ERR_STATE;
+    }
+    *out = m->zpack;
+    m->zpack = nullptr;
+    m->zpack_rc = MI_ERR_STATE;
+    m->zpack_err = "no commit since the last mi_memfs_take_zpack";
     return MI_OK;
 }
 extern "C" int mi_memfs_take_pack(mi_memfs* m, mi_pack** out) {

@@ -625,7 +625,7 @@ inline bool eval_symlinks(const std::string& p, const std::string& root, std::st
 
 struct mi_copy_layer {
     std::vector<mi_copy::Node> nodes;                       // commit order
-    // MI_MEMFS_CHUNK_PACK: the recipes -- entry i's ordered chunks are rows [chunk_first[i], chunk_first[i + 1]) of the two
+    // MI_MEMFS_CHUNK_PACK / _ZPACK: the recipes -- entry i's ordered chunks are rows [chunk_first[i], chunk_first[i + 1]) of the two
     // arrays (32 bytes / one length per row); chunk_first is empty for a layer of a commit without the option
     std::vector<uint64_t> chunk_first;
     std::vector<uint8_t>  chunk_digests;
@@ -658,8 +658,13 @@ struct mi_memfs {
     mi_pack* pack = nullptr;
     int pack_rc = MI_ERR_STATE;
     std::string pack_err = "no commit since the last mi_memfs_take_pack";
+    // MI_MEMFS_CHUNK_ZPACK: the same for the compressed pack (mi_memfs_take_zpack); the two options exclude each other
+    bool chunk_zpack = false;
+    mi_zpack* zpack = nullptr;
+    int zpack_rc = MI_ERR_STATE;
+    std::string zpack_err = "no commit since the last mi_memfs_take_zpack";
     mi_memfs() { memset(&last, 0, sizeof last); }
-    ~mi_memfs() { if (pack) mi_pack_free(pack); if (batch) mi_batch_free(batch); }
+    ~mi_memfs() { if (pack) mi_pack_free(pack); if (zpack) mi_zpack_free(zpack); if (batch) mi_batch_free(batch); }
 };
 
 // MI_MEMFS_TIMING=1: one line per merge / scan on stderr

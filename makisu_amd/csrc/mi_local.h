@@ -102,6 +102,20 @@ MI_LOCAL void mi_zpack_set_result(mi_zpack* z, uint64_t stored_bytes, uint64_t n
                                   double ms_compact, double ms_verify, double ms_decode);
 MI_LOCAL int  mi_zpack_device(const mi_zpack* z, mi_ctx** ctx, const void** d_blob, uint64_t* blob_bytes, const mi_zpack_entry** rows,
                               uint64_t* n);
+// mi_zpack.hip, for mi_zbatch.hip (a zpack coded straight from a batch's arena): the decode kernel ENQUEUED on the ctx stream,
+// nothing allocated, nothing waited for -- d_rows: the zpack's entries on the device, d_poff[k]: where entry k's plain bytes go
+// in d_out (round16(length) bytes each are written), d_rule[k]: 0 or the rule that refuses it, *d_first_bad: atomicMin of the
+// refused entries; and the coder's time, which mi_zpack_set_result leaves 0
+MI_LOCAL int  mi_zpack_decode_enqueue(mi_ctx* ctx, const void* d_zblob, const uint64_t* d_rows, const uint64_t* d_poff, uint64_t n,
+                                      void* d_out, uint32_t* d_rule, uint64_t* d_first_bad);
+MI_LOCAL void mi_zpack_set_encode_ms(mi_zpack* z, double ms_encode);
+// mi_zset.hip, for mi_zbatch.hip (mi_zset_missing): the set's ctx -- MI_ERR_STATE under `who` with the first message for a set in
+// its sticky failed state, MI_ERR_INVALID for NULL -- and zset_lookup_kernel ENQUEUED on the ctx stream over n digests on the
+// device: d_src[r] / d_word[r] = where the set holds row r's stored span and its length | stored << 32 (0, 0: not held),
+// d_len64[r] the set's length, *d_first_bad as the kernel states it (d_lengths may be NULL)
+MI_LOCAL int  mi_zset_ctx(const mi_zset* s, const char* who, mi_ctx** ctx);
+MI_LOCAL int  mi_zset_lookup_enqueue(const mi_zset* s, const uint8_t* d_digests, const uint32_t* d_lengths, uint64_t n, uint64_t* d_src,
+                                     uint64_t* d_word, uint64_t* d_len64, uint64_t* d_first_bad);
 // mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
 // it: what the arena holds stays, whichever kind it is)
 MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);

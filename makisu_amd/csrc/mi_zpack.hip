@@ -3,7 +3,8 @@
 // plain blob an ordinary pack set holds (mi_packset_add_zblob, mi_packset_add_zpack); mi_zpack_check is the host's opinion
 // (csrc/host_lz4.h).  What a chunk store keeps at rest and sends over the wire instead of plain bytes.
 //
-//   encode    one wave a chunk, a hash table of 4 096 32-bit positions in LDS (16 KiB, cleared per chunk; the workgroup IS the
+//   encode    (z_encode_block, csrc/mi_lz4_wave_enc.h: mi_zbatch.hip codes a batch's chunks where they lie with the same function)
+//             one wave a chunk, a hash table of 4 096 32-bit positions in LDS (16 KiB, cleared per chunk; the workgroup IS the
 //             wave).  The wave advances in STEPS of 64 consecutive positions [p, p + 64), capped at n - 12: lane i reads its 4
 //             bytes and the slot (u32 * 2654435761) >> 20 AS THE TABLE WAS BEFORE THE STEP.  A candidate c counts if c < pos,
 //             pos - c <= 65535 and the 4 bytes are equal (a table of zeros needs no "empty" mark).  No candidate: all 64
@@ -37,6 +38,7 @@
 #include "mi_internal.h"
 #include "mi_item_loads.h"
 #include "mi_lz4_wave.h"
+#include "mi_lz4_wave_enc.h"
 #include "host_blake2s.h"
 #include "host_lz4.h"
 #include "host_sha256.h"
@@ -52,27 +54,13 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kZNone = ~0ull;
-__host__ __device__ static inline u64 z_round16(u64 v) { return (v + 15) & ~15ull; }
-// what one chunk of n bytes takes in scratch: the LZ4 bound for a block of literals, on the 16-byte grid
-__host__ __device__ static inline u64 z_worst_span(u64 n) { return z_round16(n + n / 255 + 16); }
+// z_round16, z_worst_span (what one chunk of n bytes takes in scratch): csrc/mi_lz4_wave_enc.h
 
 constexpr int kZEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
 static_assert(sizeof(mi_zpack_entry) == 56 && kZEntryWords == 7 && sizeof(mi_pack_entry) == 56, "mi_zpack_entry is seven 8-byte words");
 
-typedef u32 u32_unaligned __attribute__((aligned(1)));
-
 // ---- encode ---------------------------------------------------------------------------------------------------------------------
-constexpr int kZHashBits = 12;
-constexpr int kZTable = 1 << kZHashBits;                      // 32-bit positions: 16 KiB a wave
-constexpr u32 kZMinChunk = 13;                                // below: raw
-constexpr u32 kZMaxOffset = 65535;
-
-// `count` extension bytes for the value e behind a nibble of 15 (count = e / 255 + 1), by the wave
-static __device__ __forceinline__ void z_put_extension(u8* out, u32 e, int lane) {
-    const u32 count = e / 255 + 1;
-    for (u32 j = lane; j < count; j += 64) out[j] = j + 1 < count ? (u8)255 : (u8)(e % 255);
-}
-
+// z_put_extension, z_encode_block: csrc/mi_lz4_wave_enc.h (mi_zbatch.hip codes with them too)
 // rows[k]: digest | the chunk's offset in the pack's blob | chunk_index | length (the high half is written here: stored)
 __global__ __launch_bounds__(64)
 void zpack_encode_kernel(const u8* __restrict__ blob, u64* __restrict__ rows, const u64* __restrict__ w_off, u8* __restrict__ scratch, u64 n) {
@@ -80,77 +68,8 @@ void zpack_encode_kernel(const u8* __restrict__ blob, u64* __restrict__ rows, co
     const int lane = threadIdx.x;
     for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
         const u64* r = rows + kZEntryWords * k;
-        const u8* src = blob + r[4];
         const u32 len = (u32)r[6];
-        u8* out = scratch + w_off[k];
-        const u64 cap = z_worst_span(len);
-        u32 stored = len;
-        if (len >= kZMinChunk) {
-            for (int i = lane; i < kZTable; i += 64) table[i] = 0;
-            __syncthreads();
-            const u32 last = len - 12, limit = len - 5;      // a match starts at or before `last` and ends at or before `limit`
-            u32 p = 0, anchor = 0;
-            u64 op = 0;
-            bool fits = true;
-            while (p <= last) {
-                const u32 cnt = last + 1 - p < 64u ? last + 1 - p : 64u;
-                const u32 pos = p + lane;
-                const bool active = (u32)lane < cnt;
-                u32 v = 0, h = 0, c = 0;
-                bool ok = false;
-                if (active) {
-                    v = *(const u32_unaligned*)(src + pos);
-                    h = (v * 2654435761u) >> (32 - kZHashBits);
-                    c = table[h];
-                    ok = c < pos && pos - c <= kZMaxOffset && *(const u32_unaligned*)(src + c) == v;
-                }
-                const u64 m = __ballot(ok);
-                __syncthreads();                              // every lane has read the table as it was before the step
-                if (m == 0) {
-                    if (active) atomicMax(&table[h], pos);
-                    p += cnt;
-                    __syncthreads();
-                    continue;
-                }
-                const int f = z_first(m);
-                const u32 mpos = p + f, mc = __shfl(c, f);
-                u32 mlen = 4;
-                for (;;) {                                    // 64 bytes a round; mpos + 4 < limit, so the first round has a lane inside
-                    const u32 i = mpos + mlen + lane;
-                    const bool differs = i >= limit || src[i] != src[mc + mlen + lane];
-                    const u64 d = __ballot(differs);
-                    if (d == 0) { mlen += 64; continue; }
-                    mlen += z_first(d);
-                    break;
-                }
-                const u32 lit = mpos - anchor, ml = mlen - 4;
-                const u64 need = 1 + (lit >= 15 ? (lit - 15) / 255 + 1 : 0) + lit + 2 + (ml >= 15 ? (ml - 15) / 255 + 1 : 0);
-                if (op + need > cap) { fits = false; break; }
-                if (lane == 0) out[op] = (u8)(((lit < 15 ? lit : 15u) << 4) | (ml < 15 ? ml : 15u));
-                op += 1;
-                if (lit >= 15) { z_put_extension(out + op, lit - 15, lane); op += (lit - 15) / 255 + 1; }
-                for (u32 j = lane; j < lit; j += 64) out[op + j] = src[anchor + j];
-                op += lit;
-                if (lane == 0) { out[op] = (u8)((mpos - mc) & 255); out[op + 1] = (u8)((mpos - mc) >> 8); }
-                op += 2;
-                if (ml >= 15) { z_put_extension(out + op, ml - 15, lane); op += (ml - 15) / 255 + 1; }
-                const u32 next = mpos + mlen;
-                if (active && pos < next) atomicMax(&table[h], pos);
-                p = anchor = next;
-                __syncthreads();
-            }
-            const u32 lit = len - anchor;                     // the last sequence: literals only (at least 5)
-            const u64 need = 1 + (lit >= 15 ? (lit - 15) / 255 + 1 : 0) + lit;
-            if (fits && op + need <= cap) {
-                if (lane == 0) out[op] = (u8)((lit < 15 ? lit : 15u) << 4);
-                op += 1;
-                if (lit >= 15) { z_put_extension(out + op, lit - 15, lane); op += (lit - 15) / 255 + 1; }
-                for (u32 j = lane; j < lit; j += 64) out[op + j] = src[anchor + j];
-                op += lit;
-                if (op < (u64)(len - (len >> 4))) stored = (u32)op;
-            }
-            __syncthreads();                                  // the next chunk clears the table
-        }
+        const u32 stored = z_encode_block(blob + r[4], len, scratch + w_off[k], z_worst_span(len), table, lane);
         if (lane == 0) rows[kZEntryWords * k + 6] = (u64)len | ((u64)stored << 32);
     }
 }
@@ -695,6 +614,17 @@ void mi_zpack_set_result(mi_zpack* z, uint64_t stored_bytes, uint64_t n_raw, uin
     zi.ms_verify = ms_verify;
     zi.ms_decode = ms_decode;
 }
+
+// (hidden: mi_local.h) the decode kernel behind whatever the ctx stream holds, for mi_zbatch.hip's verification
+int mi_zpack_decode_enqueue(mi_ctx* c, const void* d_zblob, const uint64_t* d_rows, const uint64_t* d_poff, uint64_t n, void* d_out,
+                            uint32_t* d_rule, uint64_t* d_first_bad) {
+    if (!c || !d_zblob || !d_rows || !d_poff || !n || !d_out || !d_rule || !d_first_bad) return MI_ERR_INVALID;
+    hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, c->stream, (const u8*)d_zblob, d_rows, d_poff, n, (u8*)d_out, d_rule,
+                       d_first_bad);
+    return MI_OK;
+}
+
+void mi_zpack_set_encode_ms(mi_zpack* z, double ms_encode) { z->info.ms_encode = ms_encode; }
 
 // (hidden: mi_local.h) a zpack where it lies: its ctx, its blob on the device (NULL for an empty one) and its rows on the host
 int mi_zpack_device(const mi_zpack* z, mi_ctx** ctx, const void** d_blob, uint64_t* blob_bytes, const mi_zpack_entry** rows, uint64_t* n) {

@@ -831,6 +831,21 @@ int mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags) {
     return set_add(s, who, std::move(d_blob), rows, n, flags, nullptr);
 }
 
+// (hidden: mi_local.h) for mi_zbatch.hip's mi_zset_missing: the set's ctx, and the lookup behind whatever the ctx stream holds
+int mi_zset_ctx(const mi_zset* s, const char* who, mi_ctx** ctx) {
+    if (!s || !who || !ctx) return MI_ERR_INVALID;
+    *ctx = s->ctx;
+    return set_state(s, who);
+}
+
+int mi_zset_lookup_enqueue(const mi_zset* s, const uint8_t* d_digests, const uint32_t* d_lengths, uint64_t n, uint64_t* d_src, uint64_t* d_word,
+                           uint64_t* d_len64, uint64_t* d_first_bad) {
+    if (!s || !d_digests || !n || !d_src || !d_word || !d_len64 || !d_first_bad) return MI_ERR_INVALID;
+    hipLaunchKernelGGL(zset_lookup_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s->ctx->stream, d_digests, d_lengths, n, s->tags.as<u64>(),
+                       s->slots.as<u64>(), s->cap - 1, d_src, d_word, d_len64, d_first_bad);
+    return MI_OK;
+}
+
 int mi_zset_get_info(const mi_zset* s, mi_zset_info* out) {
     if (!s || !out) return MI_ERR_INVALID;
     const int rc = set_state(s, "mi_zset_get_info");
