@@ -1329,6 +1329,56 @@ MI_BLOCK int  mi_memfs_take_zpack(mi_memfs* fs, mi_zpack** out);
 MI_BLOCK int  mi_zset_missing(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
                               uint8_t* held, uint64_t* want_rows, uint64_t cap, mi_want_info* info);
 
+/* ---- pruning a compressed set in place ---------------------------------------------------------------------------- *
+ * A set drops digests and gives device memory back without being cut into a new set: what a mark-and-sweep collector (the
+ * digests that STAY) or an eviction list (the digests that GO) needs.  For every digest still held the set answers
+ * mi_zset_zpack, mi_zset_missing and mi_batch_add_zrecipes exactly as before; a dropped digest is one that was never added.
+ *   mi_zset_prune         digests: n x 32 bytes of host memory, n < 2^32, repeats allowed; a digest the set does not hold is
+ *                         no error, its rows are counted in n_unknown.  flags: exactly one of MI_ZSET_PRUNE_KEEP (everything
+ *                         else goes; n = 0 empties the set) and MI_ZSET_PRUNE_DROP (everything else stays; n = 0 changes
+ *                         nothing); both, neither, an unknown flag or min_live_permille > 1000: MI_ERR_INVALID.  A BLOB is one
+ *                         added zpack's bytes or an earlier prune's compaction blob; its live bytes are the sum of
+ *                         round16(stored) over the surviving digests the set holds IN it (an entry that lost to "the first
+ *                         form wins" was never live).  A blob with no live bytes is freed.  A blob with
+ *                         live * 1000 < min_live_permille * its bytes as added is COMPACTED: its survivors are moved into ONE
+ *                         new blob shared by all such blobs of the call, then it is freed; 0 never moves anything.  Moves are
+ *                         VERBATIM: whole 16-byte units, round16(stored) bytes a span, the pad as it was (an unverified set's
+ *                         non-zero pad stays what mi_batch_add_zrecipes refuses); stored form, length and stored size never
+ *                         change.  The table is REBUILT for the survivors (a power of two, at least 1 024 slots, at most half
+ *                         full): it shrinks.  mi_zset_info afterwards: n_digests, stored_bytes, chunk_bytes describe what is
+ *                         held; n_packs, n_entries, blob_bytes stay sums over the zpacks that were added (residency:
+ *                         mi_zset_get_usage).  Nothing to drop: the set is untouched, *info (may be NULL) still filled.  The
+ *                         new table, the new blob and all scratch are allocated before anything changes and the old table
+ *                         and blobs go only when the new table is complete: a failure leaves the set as it was.  A compaction
+ *                         blob that does not fit is not an error: dead blobs still go, n_blobs_sparse_kept says how many
+ *                         stayed; a table or scratch that does not fit: MI_ERR_NOMEM naming the size and what the device has
+ *                         free.  A set in its sticky failed state: MI_ERR_STATE with the first message.  Zpacks cut and
+ *                         batches restored earlier own their bytes and are not affected.  Blocking, on the ctx stream.
+ *   mi_zset_get_usage     what is resident: blobs and the device bytes allocated for them, the live bytes, the table.
+ *   mi_zset_entries       what the set holds, in no stated order: digests (32 bytes each), lengths, stored sizes -- any of the
+ *                         three may be NULL; *n = how many there are; cap = 0 is the sizing call; 0 < cap < *n: MI_ERR_INVALID. */
+#define MI_ZSET_PRUNE_KEEP 0x1u   /* digests = what stays; everything else goes */
+#define MI_ZSET_PRUNE_DROP 0x2u   /* digests = what goes; everything else stays  (exactly one of the two) */
+typedef struct {               /* 112 bytes */
+    uint64_t n_rows, n_unknown;              /* request rows; rows whose digest the set did not hold (repeats counted per row) */
+    uint64_t n_dropped, dropped_stored_bytes, dropped_chunk_bytes;   /* distinct digests removed, and their stored / length sums */
+    uint64_t n_blobs_freed, freed_bytes;     /* blobs given back (wholly dead, or compacted away) and their ALLOCATED bytes */
+    uint64_t n_blobs_compacted, moved_bytes; /* blobs whose survivors were moved; sum of round16(stored) moved */
+    uint64_t n_blobs_sparse_kept;            /* blobs under the threshold that stayed because the new blob did not fit */
+    uint64_t peak_extra_bytes;               /* device bytes this call allocated before it freed anything (new table + new blob + scratch), from the sizes */
+    double   ms_mark, ms_move, ms_rebuild;   /* HIP events on the ctx stream */
+} mi_prune_info;
+typedef struct {               /* 40 bytes */
+    uint64_t n_blobs, resident_bytes;        /* blobs held and the device bytes allocated for them */
+    uint64_t live_bytes;                     /* sum of round16(stored) over the held digests */
+    uint64_t table_slots, table_bytes;
+} mi_zset_usage;
+MI_BLOCK int  mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags, uint32_t min_live_permille,
+                            mi_prune_info* info);
+MI_BLOCK int  mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out);
+MI_BLOCK int  mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint32_t* stored, uint64_t cap,
+                              uint64_t* n);
+
 #ifdef __cplusplus
 }
 #endif

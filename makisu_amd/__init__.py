@@ -21,7 +21,8 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
-           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK"]
+           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK",
+           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -190,6 +191,28 @@ class ZSetInfo(C.Structure):
     _fields_ = [("n_packs", C.c_uint64), ("n_entries", C.c_uint64), ("n_digests", C.c_uint64), ("blob_bytes", C.c_uint64),
                 ("stored_bytes", C.c_uint64), ("chunk_bytes", C.c_uint64), ("alg", C.c_uint32), ("reserved", C.c_uint32),
                 ("ms_upload", C.c_double), ("ms_verify", C.c_double), ("ms_insert", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+ZSET_PRUNE_KEEP = 0x1                    # mi_zset_prune: the digests are what stays
+ZSET_PRUNE_DROP = 0x2                    # ... what goes (exactly one of the two)
+
+
+class PruneInfo(C.Structure):
+    """mi_prune_info."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_unknown", "n_dropped", "dropped_stored_bytes", "dropped_chunk_bytes", "n_blobs_freed",
+                                          "freed_bytes", "n_blobs_compacted", "moved_bytes", "n_blobs_sparse_kept", "peak_extra_bytes")] + \
+               [(n, C.c_double) for n in ("ms_mark", "ms_move", "ms_rebuild")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class ZSetUsage(C.Structure):
+    """mi_zset_usage."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_blobs", "resident_bytes", "live_bytes", "table_slots", "table_bytes")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -456,6 +479,9 @@ def load_library(rebuild=False):
         "mi_batch_zpack_chunks": ([vp, vp, u64, C.c_uint32, C.POINTER(vp)], C.c_int),
         "mi_memfs_take_zpack": ([vp, C.POINTER(vp)], C.c_int),
         "mi_zset_missing": ([vp, vp, vp, u64, vp, vp, u64, C.POINTER(WantInfo)], C.c_int),
+        "mi_zset_prune": ([vp, vp, u64, C.c_uint32, C.c_uint32, C.POINTER(PruneInfo)], C.c_int),
+        "mi_zset_get_usage": ([vp, C.POINTER(ZSetUsage)], C.c_int),
+        "mi_zset_entries": ([vp, vp, vp, vp, u64, u64p], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1434,6 +1460,35 @@ class ZSet:
             if rc:
                 self._raise(rc)
         return held[:n], want[:info.n_want], info
+
+    def prune(self, digests, keep=True, min_live_permille=0):
+        """mi_zset_prune: drop digests in place and give memory back.  digests (n x 32 bytes, repeats and unknown ones allowed):
+        what STAYS (keep=True: everything else goes) or what GOES (keep=False).  Blobs left with nothing live are freed; blobs
+        whose live bytes fall under min_live_permille of their size have their survivors moved, verbatim, into one new blob.
+        -> PruneInfo"""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        info = PruneInfo()
+        rc = self._lib.mi_zset_prune(self._h, d.ctypes.data if len(d) else None, len(d), ZSET_PRUNE_KEEP if keep else ZSET_PRUNE_DROP,
+                                     min_live_permille, C.byref(info))
+        if rc:
+            self._raise(rc)
+        return info
+
+    def usage(self):
+        """mi_zset_get_usage: blobs resident and the device bytes allocated for them, live bytes, the table -> ZSetUsage"""
+        out = ZSetUsage()
+        self._eng._check(self._lib.mi_zset_get_usage(self._h, C.byref(out)))
+        return out
+
+    def entries(self):
+        """mi_zset_entries: what the set holds, in no stated order -> (digests uint8[n, 32], lengths uint32[n], stored uint32[n])"""
+        n = C.c_uint64()
+        self._eng._check(self._lib.mi_zset_entries(self._h, None, None, None, 0, C.byref(n)))
+        k = n.value
+        d, ln, st = np.zeros((max(k, 1), 32), dtype=np.uint8), np.zeros(max(k, 1), dtype=np.uint32), np.zeros(max(k, 1), dtype=np.uint32)
+        if k:
+            self._eng._check(self._lib.mi_zset_entries(self._h, d.ctypes.data, ln.ctypes.data, st.ctypes.data, k, C.byref(n)))
+        return d[:k], ln[:k], st[:k]
 
     @property
     def info(self):

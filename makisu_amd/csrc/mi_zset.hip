@@ -30,6 +30,7 @@
 #include "mi_internal.h"
 #include "mi_item_loads.h"
 #include "mi_lz4_wave.h"
+#include "mi_zset_local.h"
 
 #include <string.h>
 
@@ -487,62 +488,7 @@ void zset_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ wan
     if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
 }
 
-// ---- the way up: two pinned windows, one filled by the host while the other's copy runs (mi_restore.hip's SetUploader) -------
-constexpr u64 kQWinBytes = 8ull << 20;
-struct MI_LOCAL ZsetUploader {
-    Stream stream;
-    PinBuf buf[2];
-    Event ev[2];
-    bool busy[2] = {false, false};
-    ~ZsetUploader() { if (stream) (void)hipStreamSynchronize(stream); }    // no copy out of a window is under way when the windows go
-    int prepare(mi_ctx* c, u64 bytes) {
-        const u64 want = std::min<u64>(kQWinBytes, (bytes + 4095) & ~(u64)4095);    // a small blob does not pay for 16 MiB of pinned memory
-        HIPCHK(c, stream.create());
-        for (int i = 0; i < 2; ++i) {
-            HIPCHK(c, buf[i].ensure(want));
-            HIPCHK(c, ev[i].create(hipEventDisableTiming));
-        }
-        return MI_OK;
-    }
-    int pieces(mi_ctx* c, u8* dst, const u8* src, u64 bytes) {
-        const u64 win = std::min(buf[0].bytes, buf[1].bytes);
-        int w = 0;
-        for (u64 at = 0; at < bytes; w ^= 1) {
-            const u64 take = std::min(win, bytes - at);
-            if (busy[w]) { HIPCHK(c, hipEventSynchronize(ev[w])); busy[w] = false; }
-            memcpy(buf[w].p, src + at, take);
-            HIPCHK(c, hipMemcpyAsync(dst + at, buf[w].p, take, hipMemcpyHostToDevice, stream));
-            HIPCHK(c, hipEventRecord(ev[w], stream));
-            busy[w] = true;
-            at += take;
-        }
-        return MI_OK;
-    }
-    // blocking; whatever happened, no copy is in flight when it returns
-    int upload(mi_ctx* c, u8* dst, const void* src, u64 bytes) {
-        if (!bytes) return MI_OK;
-        int rc = prepare(c, bytes);
-        if (rc == MI_OK) rc = pieces(c, dst, (const u8*)src, bytes);
-        const hipError_t e = stream ? hipStreamSynchronize(stream) : hipSuccess;
-        busy[0] = busy[1] = false;
-        if (rc == MI_OK && e != hipSuccess) rc = fail(c, MI_ERR_HIP, "mi_zset_add_zblob: upload: %s", hipGetErrorString(e));
-        return rc;
-    }
-};
-
 }  // namespace mi
-
-struct mi_zset {
-    mi_ctx* ctx = nullptr;
-    mi_zset_info info = {};
-    std::vector<DevBuf> blobs;                   // every added zpack's bytes as stored, each in memory of its own: the table points into them
-    DevBuf tags, slots;                          // the table: cap tags, cap slots of kQSlotWords words
-    DevBuf counter, row_state, row_slot;
-    u64 cap = 0;                                 // slots, a power of two
-    u64 count = 0;                               // distinct digests held
-    std::string broken;                          // sticky: the first message of an add that left the table in doubt
-    ZsetUploader up;
-};
 
 namespace {
 
@@ -693,7 +639,7 @@ int verify_stored(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpac
 
 // The blob lies on the device as stored (the copy into it may still be queued on the ctx stream); entries are structurally
 // sound.  Verification, the table, the set's counters.  Until the insert begins every failure leaves the set as it was.
-int set_add(mi_zset* s, const char* who, DevBuf&& blob, const mi_zpack_entry* entries, u64 n, uint32_t flags, u64* first_bad) {
+int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi_zpack_entry* entries, u64 n, uint32_t flags, u64* first_bad) {
     mi_ctx* c = s->ctx;
     hipStream_t st = c->stream;
     DevBuf mine = std::move(blob);                     // freed on every early return -- after the stream has drained
@@ -735,7 +681,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, const mi_zpack_entry* en
     s->info.n_digests = s->count;
     s->info.stored_bytes += sums[1];
     s->info.chunk_bytes += sums[2];
-    s->blobs.push_back(std::move(mine));               // the table may point into it by now
+    s->blobs.push_back(ZsetBlob{std::move(mine), blob_bytes});   // the table may point into it by now
     if (rc == MI_OK && conflict != kQNone) {
         if (first_bad) *first_bad = conflict;
         rc = fail(c, MI_ERR_INVALID, "%s: entry %llu (%u bytes) has a digest the set holds with another length -- unverified input; the set "
@@ -798,7 +744,7 @@ int mi_zset_add_zblob(mi_zset* s, const void* blob, uint64_t blob_bytes, const m
         if (rc) return rc;
         s->info.ms_upload = ms_since(t0);
     }
-    return set_add(s, who, std::move(d_blob), entries, n, flags, first_bad);
+    return set_add(s, who, std::move(d_blob), blob_bytes, entries, n, flags, first_bad);
 }
 
 int mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags) {
@@ -828,7 +774,7 @@ int mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags) {
         if (ce != hipSuccess) return fail(c, MI_ERR_HIP, "%s: the device-to-device copy: %s", who, hipGetErrorString(ce));
         s->info.ms_upload = ms_since(t0);
     }
-    return set_add(s, who, std::move(d_blob), rows, n, flags, nullptr);
+    return set_add(s, who, std::move(d_blob), blob_bytes, rows, n, flags, nullptr);
 }
 
 // (hidden: mi_local.h) for mi_zbatch.hip's mi_zset_missing: the set's ctx, and the lookup behind whatever the ctx stream holds
@@ -843,6 +789,50 @@ int mi_zset_lookup_enqueue(const mi_zset* s, const uint8_t* d_digests, const uin
     if (!s || !d_digests || !n || !d_src || !d_word || !d_len64 || !d_first_bad) return MI_ERR_INVALID;
     hipLaunchKernelGGL(zset_lookup_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s->ctx->stream, d_digests, d_lengths, n, s->tags.as<u64>(),
                        s->slots.as<u64>(), s->cap - 1, d_src, d_word, d_len64, d_first_bad);
+    return MI_OK;
+}
+
+// (hidden: mi_local.h) for mi_zprune.hip: the table's helpers above, as they are
+int mi_zset_table_alloc(mi_ctx* c, mi::DevBuf* tags, mi::DevBuf* slots, uint64_t cap) { return table_alloc(c, tags, slots, cap); }
+
+int mi_zset_table_insert(mi_zset* s, uint64_t* tags, uint64_t* slots, uint64_t cap, const uint64_t* d_recs, uint64_t n, uint64_t sums[3],
+                         uint64_t* conflict) {
+    return table_insert(s, tags, slots, cap, d_recs, n, sums, conflict);
+}
+
+int mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint32_t* stored, uint64_t cap, uint64_t* n) {
+    if (!s || !n) return MI_ERR_INVALID;
+    static const char* who = "mi_zset_entries";
+    mi_ctx* c = s->ctx;
+    const int rc = set_state(s, who);
+    if (rc) return rc;
+    *n = s->count;
+    if (cap == 0 || s->count == 0) return MI_OK;                       // the sizing call; a set of nothing
+    if (cap < s->count)
+        return fail(c, MI_ERR_INVALID, "%s: room for %llu entries, the set holds %llu", who, (unsigned long long)cap, (unsigned long long)s->count);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DevBuf d_recs, d_cursor;
+    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    std::vector<u64> recs(s->count * kQSlotWords);
+    HIPCHK(c, d_recs.ensure(s->count * kQSlotWords * 8));
+    HIPCHK(c, d_cursor.ensure(8));
+    HIPCHK(c, hipMemsetAsync(d_cursor.p, 0, 8, st));
+    hipLaunchKernelGGL(zset_export_kernel, dim3((u32)((s->cap + 255) / 256)), dim3(256), 0, st, s->tags.as<u64>(), s->slots.as<u64>(), s->cap,
+                       d_recs.as<u64>(), s->count, d_cursor.as<u64>());
+    HIPCHK(c, hipMemcpyAsync(c->h_word.p, d_cursor.p, 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(recs.data(), d_recs.p, s->count * kQSlotWords * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipStreamSynchronize(st));
+    HIPCHK(c, hipGetLastError());
+    const u64 have = c->h_word.as<u64>()[0];
+    if (have != s->count)
+        return fail(c, MI_ERR_STATE, "%s: the set holds %llu digests, counted %llu", who, (unsigned long long)have, (unsigned long long)s->count);
+    for (u64 k = 0; k < s->count; ++k) {
+        const u64* r = recs.data() + kQSlotWords * k;
+        if (digests) memcpy(digests + 32 * k, r, 32);
+        if (lengths) lengths[k] = (u32)r[5];
+        if (stored) stored[k] = (u32)(r[5] >> 32);
+    }
     return MI_OK;
 }
 

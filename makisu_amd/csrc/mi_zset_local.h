@@ -1,0 +1,77 @@
+// mi_zset_local.h -- what a compressed pack set IS, for the two translation units that work on one: mi_zset.hip (create, add,
+// cut, restore) and mi_zprune.hip (prune in place, usage).  Host types only: no kernel lives here, and mi_zset.hip's device
+// code does not depend on it.  The table's helpers of mi_zset.hip that mi_zprune.hip reuses are declared in mi_local.h.
+#pragma once
+#include "mi_internal.h"
+
+#include <string.h>
+
+#include <algorithm>
+#include <string>
+#include <vector>
+
+namespace mi {
+
+// ---- the way up: two pinned windows, one filled by the host while the other's copy runs (mi_restore.hip's SetUploader) -------
+constexpr u64 kQWinBytes = 8ull << 20;
+struct MI_LOCAL ZsetUploader {
+    Stream stream;
+    PinBuf buf[2];
+    Event ev[2];
+    bool busy[2] = {false, false};
+    ~ZsetUploader() { if (stream) (void)hipStreamSynchronize(stream); }    // no copy out of a window is under way when the windows go
+    int prepare(mi_ctx* c, u64 bytes) {
+        const u64 want = std::min<u64>(kQWinBytes, (bytes + 4095) & ~(u64)4095);    // a small blob does not pay for 16 MiB of pinned memory
+        HIPCHK(c, stream.create());
+        for (int i = 0; i < 2; ++i) {
+            HIPCHK(c, buf[i].ensure(want));
+            HIPCHK(c, ev[i].create(hipEventDisableTiming));
+        }
+        return MI_OK;
+    }
+    int pieces(mi_ctx* c, u8* dst, const u8* src, u64 bytes) {
+        const u64 win = std::min(buf[0].bytes, buf[1].bytes);
+        int w = 0;
+        for (u64 at = 0; at < bytes; w ^= 1) {
+            const u64 take = std::min(win, bytes - at);
+            if (busy[w]) { HIPCHK(c, hipEventSynchronize(ev[w])); busy[w] = false; }
+            memcpy(buf[w].p, src + at, take);
+            HIPCHK(c, hipMemcpyAsync(dst + at, buf[w].p, take, hipMemcpyHostToDevice, stream));
+            HIPCHK(c, hipEventRecord(ev[w], stream));
+            busy[w] = true;
+            at += take;
+        }
+        return MI_OK;
+    }
+    // blocking; whatever happened, no copy is in flight when it returns
+    int upload(mi_ctx* c, u8* dst, const void* src, u64 bytes) {
+        if (!bytes) return MI_OK;
+        int rc = prepare(c, bytes);
+        if (rc == MI_OK) rc = pieces(c, dst, (const u8*)src, bytes);
+        const hipError_t e = stream ? hipStreamSynchronize(stream) : hipSuccess;
+        busy[0] = busy[1] = false;
+        if (rc == MI_OK && e != hipSuccess) rc = fail(c, MI_ERR_HIP, "mi_zset_add_zblob: upload: %s", hipGetErrorString(e));
+        return rc;
+    }
+};
+
+// a blob the table points into: one added zpack's bytes as stored, or a prune's compaction blob -- memory of its own, and how
+// many of its bytes were given (the allocation is that rounded up to 256, plus DevBuf's 256 bytes of slack)
+struct ZsetBlob {
+    DevBuf mem;
+    u64 bytes = 0;
+};
+
+}  // namespace mi
+
+struct mi_zset {
+    mi_ctx* ctx = nullptr;
+    mi_zset_info info = {};
+    std::vector<mi::ZsetBlob> blobs;             // every blob that is resident: the table points into them
+    mi::DevBuf tags, slots;                      // the table: cap tags, cap slots of kQSlotWords words
+    mi::DevBuf counter, row_state, row_slot;
+    mi::u64 cap = 0;                             // slots, a power of two
+    mi::u64 count = 0;                           // distinct digests held
+    std::string broken;                          // sticky: the first message of an add that left the table in doubt
+    mi::ZsetUploader up;
+};
