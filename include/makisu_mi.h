@@ -1379,6 +1379,48 @@ MI_BLOCK int  mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out);
 MI_BLOCK int  mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint32_t* stored, uint64_t cap,
                               uint64_t* n);
 
+/* ---- the chunk index: asking without adding, forgetting ------------------------------------------------------------ *
+ * The index's half of garbage collection.  A store that prunes its set (mi_zset_prune) hands the same list to the index, or a
+ * builder's index would go on calling a dropped chunk "known", the commit would leave it out of its pack, and the layer's
+ * recipe would name a digest no store holds.  A dropped digest is one that was never added: the next mi_index_add_batch or
+ * mi_index_import reports it new and takes it again.
+ *   mi_index_query        digests: n x 32 bytes of host memory, n < 2^32 (more, or NULL with n > 0: MI_ERR_INVALID).  held[i] =
+ *                         1 if the index holds row i's digest -- every row is answered by the table alone, repeats each get
+ *                         the answer; *n_held = the rows held; either may be NULL.  READ-ONLY: the count, the table's size and
+ *                         the export are the same before and after; the table never grows.
+ *   mi_index_query_batch  the same over the device-resident digests of a batch that has run (nothing is uploaded): held[i] for
+ *                         every chunk row -- what a second mi_index_add_batch of an unchanged index would report as known; an
+ *                         in-batch repeat of a digest the index lacks is 0.  mi_index_add_batch's rules: a batch of another
+ *                         ctx: MI_ERR_INVALID; one that has not run: MI_ERR_STATE; held given and cap < n_chunks:
+ *                         MI_ERR_CAPACITY.
+ *   mi_index_prune        mi_zset_prune's argument rules: digests n x 32 bytes of host memory, n < 2^32, repeats allowed; a
+ *                         digest the index does not hold is no error, its rows are counted in n_unknown, and a prune never
+ *                         adds it.  flags: exactly one of MI_INDEX_PRUNE_KEEP (everything else goes; n = 0 empties the index)
+ *                         and MI_INDEX_PRUNE_DROP (everything else stays; n = 0 changes nothing); both, neither or an unknown
+ *                         bit: MI_ERR_INVALID.  The table is REBUILT for the survivors (a power of two, at least 1 024 slots,
+ *                         at most half full): it shrinks.  Nothing to drop: the table is not touched (rebuilt = 0), *info (may
+ *                         be NULL) still filled.  The old table is never written; the new one, the survivors' records and all
+ *                         scratch are allocated before the launch they serve, and the tables are swapped only when the new
+ *                         one is complete and its count checked: whatever fails, the index is as it was (what does not fit:
+ *                         MI_ERR_NOMEM naming the size and what the device has free).  Blocking, on the ctx stream.
+ *   mi_index_retain_zset  keeps exactly the digests the set holds; no list crosses the host (n_rows = n_unknown = 0).  The
+ *                         index and the set belong to the same ctx, otherwise MI_ERR_INVALID; a set in its sticky failed
+ *                         state: MI_ERR_STATE with the first message, the index unchanged.                                     */
+MI_BLOCK int  mi_index_query(mi_index* index, const uint8_t* digests, uint64_t n, uint8_t* held, uint64_t* n_held);
+MI_BLOCK int  mi_index_query_batch(mi_index* index, mi_batch* b, uint8_t* held, uint64_t cap, uint64_t* n_held);
+#define MI_INDEX_PRUNE_KEEP 0x1u  /* digests = what stays; everything else goes */
+#define MI_INDEX_PRUNE_DROP 0x2u  /* digests = what goes; everything else stays  (exactly one of the two) */
+typedef struct {               /* 88 bytes */
+    uint64_t n_rows, n_unknown;              /* request rows; rows whose digest the index did not hold (repeats counted per row) */
+    uint64_t n_before, n_dropped, n_after;   /* distinct digests held before, removed, held after */
+    uint64_t slots_before, slots_after;
+    uint64_t rebuilt;                        /* 0: nothing was dropped, the table was not touched */
+    uint64_t peak_extra_bytes;               /* device bytes the call allocated before it freed anything, from the sizes */
+    double   ms_mark, ms_rebuild;            /* HIP events on the ctx stream */
+} mi_index_prune_info;
+MI_BLOCK int  mi_index_prune(mi_index* index, const uint8_t* digests, uint64_t n, uint32_t flags, mi_index_prune_info* info);
+MI_BLOCK int  mi_index_retain_zset(mi_index* index, const mi_zset* set, mi_index_prune_info* info);
+
 #ifdef __cplusplus
 }
 #endif

@@ -22,7 +22,8 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
            "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK",
-           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP"]
+           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP",
+           "IndexPruneInfo", "INDEX_PRUNE_KEEP", "INDEX_PRUNE_DROP"]
 
 FLAG_FILE_SHA256 = 0x1
 FLAG_FILE_CRC32 = 0x2
@@ -213,6 +214,20 @@ class PruneInfo(C.Structure):
 class ZSetUsage(C.Structure):
     """mi_zset_usage."""
     _fields_ = [(n, C.c_uint64) for n in ("n_blobs", "resident_bytes", "live_bytes", "table_slots", "table_bytes")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+INDEX_PRUNE_KEEP = 0x1                   # mi_index_prune: the digests are what stays
+INDEX_PRUNE_DROP = 0x2                   # ... what goes (exactly one of the two)
+
+
+class IndexPruneInfo(C.Structure):
+    """mi_index_prune_info."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_unknown", "n_before", "n_dropped", "n_after", "slots_before", "slots_after",
+                                          "rebuilt", "peak_extra_bytes")] + \
+               [(n, C.c_double) for n in ("ms_mark", "ms_rebuild")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -482,6 +497,10 @@ def load_library(rebuild=False):
         "mi_zset_prune": ([vp, vp, u64, C.c_uint32, C.c_uint32, C.POINTER(PruneInfo)], C.c_int),
         "mi_zset_get_usage": ([vp, C.POINTER(ZSetUsage)], C.c_int),
         "mi_zset_entries": ([vp, vp, vp, vp, u64, u64p], C.c_int),
+        "mi_index_query": ([vp, vp, u64, vp, u64p], C.c_int),
+        "mi_index_query_batch": ([vp, vp, vp, u64, u64p], C.c_int),
+        "mi_index_prune": ([vp, vp, u64, C.c_uint32, C.POINTER(IndexPruneInfo)], C.c_int),
+        "mi_index_retain_zset": ([vp, vp, C.POINTER(IndexPruneInfo)], C.c_int),
     }
     for name, (args, res) in sigs.items():
         fn = getattr(L, name)          # AttributeError here = header/library drift
@@ -1159,6 +1178,39 @@ class ChunkIndex:
         self._eng._check(self._lib.mi_index_import(self._h, arr.ctypes.data if arr.size else None,
                                                    len(blob) // 32, C.byref(n_new)))
         return n_new.value
+
+    def query(self, digests):
+        """mi_index_query: which of the digests (n x 32 bytes, repeats allowed) the index holds, without adding any
+        -> held flags per row as np.uint8"""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        n = len(d)
+        held = np.zeros(max(n, 1), dtype=np.uint8)
+        self._eng._check(self._lib.mi_index_query(self._h, d.ctypes.data if n else None, n, held.ctypes.data, None))
+        return held[:n]
+
+    def query_batch(self, batch):
+        """mi_index_query_batch: the same over the device-resident chunk digests of a batch that has run -- what add_batch
+        would report as known, without adding -> held flags per chunk as np.uint8"""
+        n = batch.counts()[1]
+        held = np.zeros(max(n, 1), dtype=np.uint8)
+        self._eng._check(self._lib.mi_index_query_batch(self._h, batch._h, held.ctypes.data, n, None))
+        return held[:n]
+
+    def prune(self, digests, keep=True):
+        """mi_index_prune: forget digests.  digests (n x 32 bytes, repeats and unknown ones allowed): what STAYS (keep=True:
+        everything else goes) or what GOES (keep=False).  The table is rebuilt for the survivors -> IndexPruneInfo"""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        info = IndexPruneInfo()
+        self._eng._check(self._lib.mi_index_prune(self._h, d.ctypes.data if len(d) else None, len(d),
+                                                  INDEX_PRUNE_KEEP if keep else INDEX_PRUNE_DROP, C.byref(info)))
+        return info
+
+    def retain(self, zset):
+        """mi_index_retain_zset: keep exactly the digests a ZSet of the same Engine holds; no list crosses the host
+        -> IndexPruneInfo"""
+        info = IndexPruneInfo()
+        self._eng._check(self._lib.mi_index_retain_zset(self._h, zset._h, C.byref(info)))
+        return info
 
     def close(self):
         if getattr(self, "_h", None):
