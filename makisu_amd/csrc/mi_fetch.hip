@@ -5,7 +5,7 @@
 // its live digests.  Everything runs on the ctx stream.
 //
 //   resolve   36 (or 32) bytes a request row go up; one thread per row walks the set's table -- tag first, then all 32 bytes:
-//             restore_lookup_kernel's walk, the length compared only when lengths were given -- and writes the chunk's device
+//             slot_table_find (mi_slot_table.h), the length compared only when lengths were given -- and writes the chunk's device
 //             address, the SET'S length and the held flag; the smallest bad row by atomicMin;
 //   firsts    a row counts only if no smaller row carries its digest: the engine's marking over the uploaded digests
 //             (launch_dedup_mark, what mi_dedup_mark runs: whole digests, dup_of < 0 = a first occurrence);
@@ -26,8 +26,8 @@
 // (offset + round16(length) <= blob_bytes, always, on the host) keeps inside the source blob.  Nothing in front of an entry and
 // nothing behind its padded span is read -- not even the blob's slack.  The verify pass reads what the hashing kernels read
 // behind a string (up to 67 bytes) behind the NEW blob's last entry: inside the 256 bytes it is allocated with.
-#include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_gather.h"
+#include "mi_slot_table.h"
 
 #include <string.h>
 
@@ -38,18 +38,9 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kFetchNone = ~0ull;
-__host__ __device__ static inline u64 fetch_round16(u64 v) { return (v + 15) & ~15ull; }
 
 constexpr int kFetchEntryWords = sizeof(mi_pack_entry) / 8;     // digest 4 | offset | chunk_index | length, reserved
-constexpr int kFetchSlotWords = 6;                              // mi_restore.hip's slot: digest 4 | device address | length
 static_assert(sizeof(mi_pack_entry) == 56 && kFetchEntryWords == 7, "mi_pack_entry is seven 8-byte words");
-
-static __device__ __forceinline__ bool fetch_digest_eq32(const u8* a, const u8* b) {
-    const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
-    const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
-    const u32x4 d0 = a0 ^ b0, d1 = a1 ^ b1;
-    return (d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0;
-}
 
 // ---- resolve ------------------------------------------------------------------------------------------------------------------
 // src[r], len64[r]: where the set holds row r's chunk and with how many bytes (0, 0: it does not); held[r]: whether it does.
@@ -62,21 +53,12 @@ void fetch_lookup_kernel(const u8* __restrict__ digests, const u32* __restrict__
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
     const u8* d = digests + 32 * r;
-    const u64 first8 = *(const u64*)d;
-    const u64 tag = first8 ? first8 : 1ull;
     u64 at = 0, has = 0;
-    bool found = false;
-    u64 slot = tag & mask;
-    for (u64 walked = 0; walked <= mask; ++walked) {         // (the table is under half full: an empty slot ends every walk)
-        const u64 t = tags[slot];
-        if (t == 0ull) break;
-        if (t == tag && fetch_digest_eq32((const u8*)(slots + kFetchSlotWords * slot), d)) {
-            at = slots[kFetchSlotWords * slot + 4];
-            has = slots[kFetchSlotWords * slot + 5] & 0xFFFFFFFFull;
-            found = true;
-            break;
-        }
-        slot = (slot + 1) & mask;
+    const u64 slot = slot_table_find(tags, slots, mask, d);
+    const bool found = slot != kSlotNone;
+    if (found) {
+        at = slots[kSlotWords * slot + 4];
+        has = slots[kSlotWords * slot + 5] & 0xFFFFFFFFull;
     }
     src[r] = at;
     len64[r] = has;
@@ -94,38 +76,6 @@ constexpr int kFetchBlock = 256;
 constexpr int kFetchPer   = 8;                          // rows per thread
 constexpr int kFetchTile  = kFetchBlock * kFetchPer;    // 2048 rows per block
 enum : int { kTotEntries = 0, kTotBlob = 1, kTotRaw = 2, kTotFirst = 3, kTotHeld = 4, kTotHeldBytes = 5, kTotBad = 6, kTotDiffer = 7 };
-
-static __device__ __forceinline__ u64 fetch_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kFetchBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-static __device__ __forceinline__ u64 fetch_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
 
 // the selection: a first occurrence that the set holds (want_held: the sub-pack's entries) or lacks (the want list)
 static __device__ __forceinline__ bool fetch_selected(const i64* __restrict__ dup_of, const u8* __restrict__ held, u64 row, int want_held) {
@@ -153,13 +103,13 @@ void fetch_block_sums_kernel(const i64* __restrict__ dup_of, const u8* __restric
         if (h) { ++v[4]; v[5] += len; }
         if (h == (want_held != 0)) {
             ++v[0];
-            v[1] += fetch_round16(len);
+            v[1] += round16(len);
             v[2] += want_held ? len : stated ? (u64)stated[row] : 0ull;
         }
     }
 #pragma unroll
     for (int q = 0; q < 6; ++q) {
-        v[q] = fetch_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -189,8 +139,8 @@ void fetch_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ b
         const u64 i = b0 + threadIdx.x;
         const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
         u64 tc, tb;
-        const u64 ec = fetch_exclusive_scan(vc, &tc, lds);
-        const u64 eb = fetch_exclusive_scan(vb, &tb, lds);
+        const u64 ec = block_exclusive_scan_u64<kFetchBlock>(vc, &tc, lds);
+        const u64 eb = block_exclusive_scan_u64<kFetchBlock>(vb, &tb, lds);
         if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
         carry_c += tc;
         carry_b += tb;
@@ -210,7 +160,7 @@ void fetch_compact_rows_kernel(const i64* __restrict__ dup_of, const u8* __restr
     for (int k = 0; k < kFetchPer; ++k)
         if (base + k < n && fetch_selected(dup_of, held, base + k, 0)) { sel |= 1u << k; ++cnt; }
     u64 t;
-    u64 at = fetch_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kFetchBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kFetchPer; ++k)
         if (sel & (1u << k)) want_rows[at++] = base + k;
@@ -231,11 +181,11 @@ void fetch_compact_entries_kernel(const i64* __restrict__ dup_of, const u8* __re
     for (int k = 0; k < kFetchPer; ++k) {
         const bool sel = base + k < n && fetch_selected(dup_of, held, base + k, 1);
         len[k] = sel ? len64[base + k] : kFetchNone;
-        if (sel) { ++cnt; bytes += fetch_round16(len[k]); }
+        if (sel) { ++cnt; bytes += round16(len[k]); }
     }
     u64 t;
-    u64 at = fetch_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = fetch_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kFetchBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kFetchBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kFetchPer; ++k) {
         if (len[k] == kFetchNone) continue;
@@ -250,108 +200,16 @@ void fetch_compact_entries_kernel(const i64* __restrict__ dup_of, const u8* __re
         r[5] = row;
         r[6] = len[k] & 0xFFFFFFFFull;                 // length | reserved = 0
         ++at;
-        dst += fetch_round16(len[k]);
+        dst += round16(len[k]);
     }
 }
 
-// ---- gather -----------------------------------------------------------------------------------------------------------------
-constexpr int kFetchWG = 256;
-constexpr u32 kFetchGatherTile = 16384;                    // bytes of the blob a workgroup writes
-constexpr u32 kFetchUnits = kFetchGatherTile / 16;         // ... in 16-byte units: an entry takes at least one, so at most as many entries
-constexpr int kFetchUnitsPer = kFetchUnits / kFetchWG;     // units per lane
+// ---- gather: mi_gather.h's tile body over aligned sources -------------------------------------------------------------------------
 
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 fetch_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// an ALIGNED 16-byte load from an absolute device address: the table hands out addresses, not offsets from a kernel argument,
-// so the address space is said here (a generic pointer would make it a flat load)
-static __device__ __forceinline__ u32x4 fetch_load16(u64 addr) {
-    typedef const u32x4 __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
-
-__global__ __launch_bounds__(kFetchWG)
+__global__ __launch_bounds__(kGatherWG)
 void fetch_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
                          u64 blob_bytes, u8* __restrict__ blob) {
-    __shared__ u64 s_src[kFetchUnits];
-    __shared__ u32 s_rel[kFetchUnits];               // where the entry begins in the tile
-    __shared__ u32 s_len[kFetchUnits];
-    __shared__ u64 s_k[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 tile0 = (u64)blockIdx.x * kFetchGatherTile;
-    const u64 tile1 = tile0 + kFetchGatherTile < blob_bytes ? tile0 + kFetchGatherTile : blob_bytes;
-    // the first and the last entry that reach into the tile: the last one that begins at or before the tile's first / last unit
-    if (wave < 2) {
-        const u64 k = fetch_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
-        if (lane == 0) s_k[wave] = k;
-    }
-    __syncthreads();
-    const u64 k0 = s_k[0];
-    const u64 reach = s_k[1] - k0 + 1;
-    const u32 cnt = reach < kFetchUnits ? (u32)reach : kFetchUnits;
-    for (u32 i = threadIdx.x; i < cnt; i += kFetchWG) {
-        u64 src = e_src[k0 + i], len = e_len[k0 + i];
-        const u64 dst = e_dst[k0 + i];
-        u32 rel = (u32)(dst - tile0);
-        if (dst < tile0) {                           // the first entry may begin in front of the tile (by up to 4 GiB): the tile sees
-            const u64 skip = tile0 - dst;            // what is left of it -- skip is a multiple of 16 below its length
-            src += skip;
-            len -= skip;
-            rel = 0;
-        }
-        s_src[i] = src;
-        s_len[i] = (u32)len;
-        s_rel[i] = rel;
-    }
-    __syncthreads();
-    u64 src[kFetchUnitsPer];                         // device addresses of the units' 16 bytes
-    u32 valid[kFetchUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kFetchUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kFetchWG) * 16;
-        src[j] = s_src[0];                            // a unit behind the blob's end (the last tile) loads the tile's first unit and
-        valid[j] = 0;                                 // drops it: an unconditional load, so that a lane's four are in flight together
-        if (tile0 + r >= tile1) continue;
-        u32 lo = 0, hi = cnt;                         // the entry this unit lies in: the last that begins at or before it
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (s_rel[mid] <= r) lo = mid; else hi = mid;
-        }
-        const u32 o = r - s_rel[lo], len = s_len[lo];
-        if (o < len) {                                // (always, for entries of at least one byte)
-            src[j] = s_src[lo] + o;                   // a multiple of 16 behind an aligned address
-            valid[j] = len - o;
-        }
-    }
-    u32x4 v[kFetchUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kFetchUnitsPer; ++j) v[j] = fetch_load16(src[j]);
-#pragma unroll
-    for (int j = 0; j < kFetchUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kFetchWG) * 16;
-        if (tile0 + r >= tile1) continue;
-        if (valid[j] < 16) {                          // the chunk's last unit: zero at and beyond its length, whatever the source holds there
-            u32 w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const u32 have = valid[j] > 4u * q ? valid[j] - 4u * q : 0u;
-                w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
-            }
-            v[j] = u32x4{w[0], w[1], w[2], w[3]};
-        }
-        *(u32x4*)(blob + tile0 + r) = v[j];
-    }
+    gather_tile<true>(e_src, e_len, e_dst, n_entries, blob_bytes, blob);
 }
 
 // ---- MI_SUBPACK_VERIFY: the digests of the new blob's entries against the requested ones (the rows carry them) ---------------
@@ -528,7 +386,7 @@ int mi_packset_pack(const mi_packset* set, const uint8_t* digests, const uint32_
     if (n_sel == 0 || n_sel != h[kTotFirst] || blob_bytes < 16 * n_sel)
         return fail(c, MI_ERR_HIP, "%s: the plan counted %llu entries in %llu bytes among %llu distinct digests", who, (unsigned long long)n_sel,
                     (unsigned long long)blob_bytes, (unsigned long long)h[kTotFirst]);
-    const u64 n_tiles = (blob_bytes + kFetchGatherTile - 1) / kFetchGatherTile;
+    const u64 n_tiles = (blob_bytes + kGatherTile - 1) / kGatherTile;
     if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
     void* d_blob = nullptr;
     mi_pack_entry* h_rows = nullptr;
@@ -544,7 +402,7 @@ int mi_packset_pack(const mi_packset* set, const uint8_t* digests, const uint32_
                        q.src.as<u64>(), q.len64.as<u64>(), q.dig.as<u8>(), n, q.block_cnt, q.block_bytes, e_src.as<u64>(), e_len.as<u64>(),
                        e_dst.as<u64>(), d_rows.as<u64>());
     HIPCHK(c, hipEventRecord(q.ev[1], s));
-    hipLaunchKernelGGL(fetch_gather_kernel, dim3((u32)n_tiles), dim3(kFetchWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel,
+    hipLaunchKernelGGL(fetch_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel,
                        blob_bytes, (u8*)d_blob);
     HIPCHK(c, hipEventRecord(q.ev[2], s));
     if (flags & MI_SUBPACK_VERIFY) {

@@ -49,26 +49,13 @@
 // [0, n), mark [0, cap) at a slot of the walk, two totals.  sweep READS state, digests, mark at [0, n_items), WRITES out at
 // [0, 32 limit) (the cursor is checked), two totals.  flags READS src [0, n), WRITES flags [0, n).
 #include "mi_internal.h"
+#include "mi_wave.h"
 
 #include <string.h>
 
 using namespace mi;
 
-typedef u32 u32x4 __attribute__((ext_vector_type(4)));
-
 namespace {
-
-__device__ __forceinline__ bool digest_eq32(const u8* a, const u8* b) {
-    const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
-    const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
-    const u32x4 d0 = a0 ^ b0, d1 = a1 ^ b1;
-    return (d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0;
-}
-
-__device__ __forceinline__ u64 tag_of(const u8* d) {
-    const u64 t = *(const u64*)d;
-    return t ? t : 1ull;
-}
 
 // Row states while an insert is in progress.
 enum : u8 { kRowDone = 0, kRowVerify = 1, kRowProbe = 2 };
@@ -81,7 +68,7 @@ void index_begin_kernel(const u8* __restrict__ digests, const i64* __restrict__ 
     if (i >= n) return;
     const bool probe = !(dup_of && dup_of[i] >= 0);
     row_state[i] = probe ? kRowProbe : kRowDone;
-    row_slot[i] = tag_of(digests + 32 * i) & mask;
+    row_slot[i] = tag_of(*(const u64*)(digests + 32 * i)) & mask;
 }
 
 // known[i] = 0 if the row's digest was inserted now (known may be nullptr)
@@ -96,7 +83,7 @@ void index_probe_kernel(const u8* __restrict__ digests, u64 n, u64* __restrict__
     for (u64 i = (u64)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (u64)gridDim.x * blockDim.x) {
         if (row_state[i] != kRowProbe) continue;
         const u8* d = digests + 32 * i;
-        const u64 tag = tag_of(d);
+        const u64 tag = tag_of(*(const u64*)d);
         u64 slot = row_slot[i];
         for (;;) {
             const u64 old = atomicCAS((unsigned long long*)&tags[slot], 0ull, (unsigned long long)tag);
@@ -172,7 +159,7 @@ void index_lookup_kernel(const u8* __restrict__ digests, u64 n, const u64* __res
     bool found = false;
     if (in) {
         const u8* d = digests + 32 * r;
-        const u64 tag = tag_of(d);
+        const u64 tag = tag_of(*(const u64*)d);
         u64 slot = tag & mask;
         for (u64 walked = 0; walked <= mask; ++walked) {     // (the table is at most half full: an empty slot ends every walk)
             const u64 t = tags[slot];

@@ -6,8 +6,6 @@
 
 #define MI_LOCAL __attribute__((visibility("hidden")))
 
-namespace mi { struct DevBuf; }                   // mi_internal.h
-
 extern "C" {
 // mi_api.hip (what reads staged bytes back -- _read_file_landed, _read_stats, _chunk_sum, the windows, _explain_chunk: mi_readback.hip)
 MI_LOCAL void        mi_set_error(mi_batch* b, const char* msg);     // b NULL: the message mi_last_error(NULL) returns
@@ -118,15 +116,6 @@ MI_LOCAL void mi_zpack_set_encode_ms(mi_zpack* z, double ms_encode);
 MI_LOCAL int  mi_zset_ctx(const mi_zset* s, const char* who, mi_ctx** ctx);
 MI_LOCAL int  mi_zset_lookup_enqueue(const mi_zset* s, const uint8_t* d_digests, const uint32_t* d_lengths, uint64_t n, uint64_t* d_src,
                                      uint64_t* d_word, uint64_t* d_len64, uint64_t* d_first_bad);
-// mi_zset.hip, for mi_zprune.hip (struct mi_zset itself: mi_zset_local.h): the table's two helpers as mi_zset.hip's own adds
-// use them.  _table_alloc: tags and slots (mi::DevBuf) hold cap slots, the tags' memset ENQUEUED on the ctx stream -- buffers that are
-// large enough already are kept.  _table_insert: n records (device, six words each) into the table (tags, slots, cap) through the
-// probe-then-verify rounds, ONE synchronisation of the ctx stream a round (one round unless 64-bit tags collide); sums[0] of
-// them were not held, with sums[1] stored bytes and sums[2] chunk bytes; *conflict: the smallest row whose digest is held with
-// another length (~0: none).  Its row scratch is the set's (row_state, row_slot, counter)
-MI_LOCAL int  mi_zset_table_alloc(mi_ctx* ctx, mi::DevBuf* tags, mi::DevBuf* slots, uint64_t cap);
-MI_LOCAL int  mi_zset_table_insert(mi_zset* s, uint64_t* tags, uint64_t* slots, uint64_t cap, const uint64_t* d_recs, uint64_t n,
-                                   uint64_t sums[3], uint64_t* conflict);
 // mi_api.hip, for mi_restore.hip: room in the batch's arena up to offset `end` (arena_reserve, as mi_batch_add_synthetic asks for
 // it: what the arena holds stays, whichever kind it is)
 MI_LOCAL int  mi_batch_arena_reserve(mi_batch* b, uint64_t end);

@@ -19,12 +19,12 @@
 
 #include "mi_common.h"
 #include "mi_lz4_wave.h"
+#include "mi_wave.h"
 
 namespace mi {
 
-__host__ __device__ static inline u64 z_round16(u64 v) { return (v + 15) & ~15ull; }
 // what one chunk of n bytes takes in scratch: the LZ4 bound for a block of literals, on the 16-byte grid
-__host__ __device__ static inline u64 z_worst_span(u64 n) { return z_round16(n + n / 255 + 16); }
+__host__ __device__ static inline u64 z_worst_span(u64 n) { return round16(n + n / 255 + 16); }
 
 typedef u32 u32_unaligned __attribute__((aligned(1)));
 

@@ -19,7 +19,7 @@
 // chunk (len = 1 mod 16), inside the arena's 4 KiB slack.  The hashing of the verify pass reads up to 67 bytes behind the blob's
 // last entry: the blob is allocated with the 256 bytes every DevBuf has behind it.
 #include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_wave.h"
 #include "host_blake2s.h"
 #include "host_sha256.h"
 
@@ -33,48 +33,12 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kNoRow = ~0ull;
-__host__ __device__ static inline u64 round16(u64 v) { return (v + 15) & ~15ull; }
-
 // ---- plan ------------------------------------------------------------------------------------------------------------
 constexpr int kPlanBlock = 256;
 constexpr int kPlanPer   = 8;                       // rows per thread
 constexpr int kPlanTile  = kPlanBlock * kPlanPer;   // 2048 rows per block
 constexpr int kEntryWords = sizeof(mi_pack_entry) / 8;
 static_assert(sizeof(mi_pack_entry) == 56 && kEntryWords == 7, "mi_pack_entry is seven 8-byte words");
-
-// the block scan of tables.hip: inclusive scan per wave with shuffles, then across the 4 waves through LDS
-static __device__ __forceinline__ u64 plan_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kPlanBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-// a wave's sum, in every lane
-static __device__ __forceinline__ u64 wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
 
 // per block of kPlanTile rows: how many are selected, and their rounded-up bytes; totals[2] += their bytes as they are.
 // Three sums, nothing else: a reduction per wave, the four waves' results through LDS, one barrier.
@@ -118,8 +82,8 @@ void pack_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ bl
         const u64 i = b0 + threadIdx.x;
         const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
         u64 tc, tb;
-        const u64 ec = plan_exclusive_scan(vc, &tc, lds);
-        const u64 eb = plan_exclusive_scan(vb, &tb, lds);
+        const u64 ec = block_exclusive_scan_u64<kPlanBlock>(vc, &tc, lds);
+        const u64 eb = block_exclusive_scan_u64<kPlanBlock>(vb, &tb, lds);
         if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
         carry_c += tc;
         carry_b += tb;
@@ -145,8 +109,8 @@ void pack_compact_kernel(const u8* __restrict__ select, const u64* __restrict__ 
         if (sel) { ++cnt; bytes += round16(len[k]); }
     }
     u64 t;
-    u64 at = plan_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = plan_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kPlanBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kPlanBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kPlanPer; ++k) {
         if (len[k] == kNoRow) continue;
@@ -170,20 +134,6 @@ constexpr int kPackWG = 256;
 constexpr u32 kPackTile = 16384;                     // bytes of the blob a workgroup writes
 constexpr u32 kPackUnits = kPackTile / 16;           // ... in 16-byte units: an entry takes at least one, so at most as many entries
 constexpr int kPackPer = kPackUnits / kPackWG;       // units per lane
-
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round
-static __device__ __forceinline__ u64 wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
 
 __global__ __launch_bounds__(kPackWG)
 void pack_gather_kernel(const u8* __restrict__ arena, const u64* __restrict__ e_src, const u64* __restrict__ e_len,
@@ -239,15 +189,7 @@ void pack_gather_kernel(const u8* __restrict__ arena, const u64* __restrict__ e_
     for (int j = 0; j < kPackPer; ++j) {
         const u32 r = ((u32)threadIdx.x + (u32)j * kPackWG) * 16;
         if (tile0 + r >= tile1) continue;
-        if (valid[j] < 16) {                          // the chunk's last unit: zero at and beyond its length
-            u32 w[4] = {v[j].x, v[j].y, v[j].z, v[j].w};
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const u32 have = valid[j] > 4u * q ? valid[j] - 4u * q : 0u;
-                w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
-            }
-            v[j] = u32x4{w[0], w[1], w[2], w[3]};
-        }
+        if (valid[j] < 16) v[j] = keep_first_bytes(v[j], valid[j]);   // the chunk's last unit: zero at and beyond its length
         *(u32x4*)(blob + tile0 + r) = v[j];
     }
 }

@@ -3,12 +3,13 @@
 // the inverse of pack_gather_kernel plus a digest-addressed lookup.  What feeds a batch from packs instead of from disk.
 //
 //   set       every added pack's blob lies in device memory of its own (exactly its bytes + DevBuf's 256 bytes of slack).  Its
-//             entries go into ONE open-addressing table in the manner of mi_index.hip: tag = the digest's first 8 bytes (0 is
-//             stored as 1, 0 = empty), slot = {digest 32 | the chunk's ABSOLUTE device address 8 | its length 4 | 4}.  The
-//             insert runs in probe-then-verify rounds across a kernel boundary (no thread compares digest bytes another thread
-//             of the same launch may still be writing); a digest met again is kept once; the same digest with another length
-//             is reported and makes the set unusable (the table is not rolled back).  Rebuilt at twice the size when it passes
-//             half full: the new table is filled before the old one goes, so a failed growth leaves the set as it was;
+//             entries go into ONE open-addressing table (mi_slot_table.h, the one mi_zset.hip holds too): tag = the digest's
+//             first 8 bytes (0 is stored as 1, 0 = empty), slot = {digest 32 | the chunk's ABSOLUTE device address 8 | its
+//             length 4 | 4}.  The insert runs in probe-then-verify rounds across a kernel boundary (no thread compares digest
+//             bytes another thread of the same launch may still be writing); a digest met again is kept once; the same digest
+//             with another length is reported and makes the set unusable (the table is not rolled back).  Rebuilt at twice the
+//             size when it passes half full: the new table is filled before the old one goes, so a failed growth leaves the
+//             set as it was;
 //   upload    mi_packset_add_blob: after the structural check on the host (no lying entry reaches a kernel) the blob goes up
 //             through two pinned windows, filling one while the other's copy runs -- PackReader's mirror image;
 //   verify    MI_PACKSET_VERIFY: the blob's entries through the ctx's own hashing launcher (pass kShaBlobs) as MI_PACK_VERIFY
@@ -37,8 +38,7 @@
 // structural check (offset + round16(length) <= blob_bytes, always, on the host) is what makes the entry's address a bound.
 // The hashing of the set's verify pass reads up to 67 bytes behind the blob's last entry (the same slack), that of the recipes'
 // up to 67 bytes behind the last restored file (the arena's 4 KiB).
-#include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_slot_table.h"
 
 #include <string.h>
 
@@ -52,20 +52,9 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kNone = ~0ull;
-__host__ __device__ static inline u64 restore_round16(u64 v) { return (v + 15) & ~15ull; }
 
 constexpr int kEntryWords = sizeof(mi_pack_entry) / 8;      // digest 4 | offset | chunk_index | length, reserved
-constexpr int kSlotWords = 6;                               // digest 4 | device address | length
 static_assert(sizeof(mi_pack_entry) == 56 && kEntryWords == 7, "mi_pack_entry is seven 8-byte words");
-
-static __device__ __forceinline__ bool digest_eq32(const u8* a, const u8* b) {
-    const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
-    const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
-    const u32x4 d0 = a0 ^ b0, d1 = a1 ^ b1;
-    return (d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0;
-}
-
-static __device__ __forceinline__ u64 tag_of(u64 first8) { return first8 ? first8 : 1ull; }
 
 // ---- the set: entries -> table records, the verification, the table ------------------------------------------------------
 // entries as they were uploaded -> what the table takes (digest | base + offset | length) and what the hashing launcher takes
@@ -93,86 +82,8 @@ void packset_check_kernel(const u8* __restrict__ got, const u64* __restrict__ en
     const u64* e = entries + kEntryWords * k;
     bool ok = g[0] == e[0] && g[1] == e[1] && g[2] == e[2] && g[3] == e[3];
     const u64 len = e[6] & 0xFFFFFFFFull;
-    for (u64 i = e[4] + len; i < e[4] + restore_round16(len); ++i) ok = ok && blob[i] == 0;
+    for (u64 i = e[4] + len; i < e[4] + round16(len); ++i) ok = ok && blob[i] == 0;
     if (!ok) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
-}
-
-enum : u8 { kRowDone = 0, kRowVerify = 1, kRowProbe = 2 };
-
-__global__ __launch_bounds__(256)
-void packset_begin_kernel(const u64* __restrict__ recs, u64 n, u64 mask, u8* __restrict__ row_state, u64* __restrict__ row_slot) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    row_state[i] = kRowProbe;
-    row_slot[i] = tag_of(recs[kSlotWords * i]) & mask;
-}
-
-// walks from the row's slot comparing TAGS only: an empty slot is claimed and the record stored, a slot with an equal tag is
-// remembered for the verify kernel, anything else is walked past.  counters[0] += records stored
-__global__ __launch_bounds__(256)
-void packset_probe_kernel(const u64* __restrict__ recs, u64 n, u64* __restrict__ tags, u64* __restrict__ slots, u64 mask,
-                          u8* __restrict__ row_state, u64* __restrict__ row_slot, u64* __restrict__ counters) {
-    __shared__ u32 wg_new;
-    if (threadIdx.x == 0) wg_new = 0;
-    __syncthreads();
-    u32 mine_new = 0;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
-        if (row_state[i] != kRowProbe) continue;
-        const u64* r = recs + kSlotWords * i;
-        const u64 tag = tag_of(r[0]);
-        u64 slot = row_slot[i];
-        for (;;) {
-            const u64 old = atomicCAS((unsigned long long*)&tags[slot], 0ull, (unsigned long long)tag);
-            if (old == 0ull) {                               // empty: mine now
-                u64* s = slots + kSlotWords * slot;
-                s[0] = r[0]; s[1] = r[1]; s[2] = r[2]; s[3] = r[3]; s[4] = r[4]; s[5] = r[5];
-                row_state[i] = kRowDone;
-                ++mine_new;
-                break;
-            }
-            if (old == tag) {                                // full compare after the kernel boundary
-                row_slot[i] = slot;
-                row_state[i] = kRowVerify;
-                break;
-            }
-            slot = (slot + 1) & mask;
-        }
-    }
-    if (mine_new) atomicAdd(&wg_new, mine_new);
-    __syncthreads();
-    if (threadIdx.x == 0 && wg_new) atomicAdd((unsigned long long*)counters, (unsigned long long)wg_new);
-}
-
-// equal digests: the chunk is held already (kept once) -- with another length: counters[2] = the smallest such row.
-// Equal tags, different digests: the row goes on probing behind the slot (counters[1] += 1)
-__global__ __launch_bounds__(256)
-void packset_verify_kernel(const u64* __restrict__ recs, u64 n, const u64* __restrict__ slots, u64 mask,
-                           u8* __restrict__ row_state, u64* __restrict__ row_slot, u64* __restrict__ counters) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || row_state[i] != kRowVerify) return;
-    const u64 slot = row_slot[i];
-    const u64* r = recs + kSlotWords * i;
-    const u64* s = slots + kSlotWords * slot;
-    if (s[0] == r[0] && s[1] == r[1] && s[2] == r[2] && s[3] == r[3]) {
-        if (s[5] != r[5]) atomicMin((unsigned long long*)&counters[2], (unsigned long long)i);
-        row_state[i] = kRowDone;
-    } else {
-        row_slot[i] = (slot + 1) & mask;
-        row_state[i] = kRowProbe;
-        atomicAdd((unsigned long long*)&counters[1], 1ull);
-    }
-}
-
-// every occupied slot's record to out[0, limit); the cursor counts them all
-__global__ __launch_bounds__(256)
-void packset_export_kernel(const u64* __restrict__ tags, const u64* __restrict__ slots, u64 cap, u64* __restrict__ out, u64 limit,
-                           u64* __restrict__ cursor) {
-    const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= cap || tags[s] == 0ull) return;
-    const u64 at = atomicAdd((unsigned long long*)cursor, 1ull);
-    if (at >= limit) return;
-#pragma unroll
-    for (int w = 0; w < kSlotWords; ++w) out[kSlotWords * at + w] = slots[kSlotWords * s + w];
 }
 
 // ---- resolve: every recipe row's source address ---------------------------------------------------------------------------
@@ -188,17 +99,10 @@ void restore_lookup_kernel(const u8* __restrict__ digests, const u32* __restrict
     u64 at = 0;
     u32 held = 0;
     if (len) {
-        const u64 tag = tag_of(*(const u64*)d);
-        u64 slot = tag & mask;
-        for (u64 walked = 0; walked <= mask; ++walked) {     // (the table is under half full: an empty slot ends every walk)
-            const u64 t = tags[slot];
-            if (t == 0ull) break;
-            if (t == tag && digest_eq32((const u8*)(slots + kSlotWords * slot), d)) {
-                held = (u32)slots[kSlotWords * slot + 5];
-                if (held == len) at = slots[kSlotWords * slot + 4];
-                break;
-            }
-            slot = (slot + 1) & mask;
+        const u64 slot = slot_table_find(tags, slots, mask, d);
+        if (slot != kSlotNone) {
+            held = (u32)slots[kSlotWords * slot + 5];
+            if (held == len) at = slots[kSlotWords * slot + 4];
         }
     }
     src[r] = at;
@@ -212,27 +116,6 @@ constexpr int kRestoreWG = 256;
 constexpr u32 kRestoreTile = 16384;                  // bytes of the destination a workgroup writes
 constexpr int kRestorePer = kRestoreTile / 16 / kRestoreWG;   // units per lane
 constexpr u32 kRestoreRows = 1024;                   // rows of a tile that LDS holds (a tile of rows of 16 bytes and more has no more)
-
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 restore_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// a 16-byte load at any alignment from an ABSOLUTE device address: the table hands out addresses, not offsets from a kernel
-// argument, so the address space is said here (a generic pointer would make it a flat load)
-static __device__ __forceinline__ u32x4 load16_global(u64 addr) {
-    typedef const u32x4_unaligned __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
 
 // masks of the first n bytes (n < 16) of a 16-byte unit held as (lo, hi).  Plain values on purpose: written with references to
 // lo and hi the compiler turns the choice between them into an indexed access to a two-element array in scratch
@@ -273,7 +156,7 @@ static __device__ __forceinline__ u32 restore_tile(u8* __restrict__ arena, const
 #pragma unroll
     for (int j = 0; j < kRestorePer; ++j) {
         v[j] = u32x4{0, 0, 0, 0};
-        if (valid[j]) v[j] = load16_global(ld[j]);
+        if (valid[j]) v[j] = load16_global_unaligned(ld[j]);
     }
     u32 joined = 0;
 #pragma unroll
@@ -289,7 +172,7 @@ static __device__ __forceinline__ u32 restore_tile(u8* __restrict__ arena, const
             const u32 q = (u32)(d - u);               // 1..15: where the row begins in the unit
             const u32 len = row_len(nx);
             const u32 m = len < 16 - q ? len : 16 - q;
-            const u32x4 w = load16_global(row_src(nx));      // from the row's first byte: never in front of it
+            const u32x4 w = load16_global_unaligned(row_src(nx));      // from the row's first byte: never in front of it
             const u64 wl = (((u64)w.y << 32) | w.x) & keep_lo(m), wh = (((u64)w.w << 32) | w.z) & keep_hi(m);
             // ... moved up by q bytes (q >= 8: the low half lands in the high one; a shift by 64 is never formed)
             lo |= q >= 8 ? 0ull : wl << (8 * q);
@@ -325,7 +208,7 @@ void restore_assemble_kernel(u8* __restrict__ arena, const u64* __restrict__ r_d
     if (threadIdx.x == 0) s_joined = 0;
     // the first and the last row that reach into the tile: the last one that begins at or before the tile's first / last byte
     if (wave < 2) {
-        const u64 k = restore_wave_last_le(r_dst, n_rows, wave == 0 ? tile0 : tile1 - 1, lane);
+        const u64 k = wave_last_le(r_dst, n_rows, wave == 0 ? tile0 : tile1 - 1, lane);
         if (lane == 0) s_k[wave] = k;
     }
     __syncthreads();
@@ -403,10 +286,8 @@ struct mi_packset {
     mi_ctx* ctx = nullptr;
     mi_packset_info info = {};
     std::vector<DevBuf> blobs;                   // every added pack's bytes, each in memory of its own: the table points into them
-    DevBuf tags, slots;                          // the table: cap tags, cap slots of kSlotWords words
-    DevBuf counter, row_state, row_slot;
-    u64 cap = 0;                                 // slots, a power of two
-    u64 count = 0;                               // distinct digests held
+    SlotTable table;                             // digest -> the chunk's device address and length (mi_slot_table.h)
+    DevBuf bad_cell;                             // MI_PACKSET_VERIFY's answer
     std::string broken;                          // sticky: the first message of an add that left the table in doubt
     SetUploader up;
 };
@@ -437,7 +318,7 @@ int check_structure(mi_ctx* c, const char* who, u64 blob_bytes, const mi_pack_en
     u64 end = 0;                                       // where the previous entry's unit(s) end
     for (u64 k = 0; k < n; ++k) {
         const mi_pack_entry& en = entries[k];
-        const u64 span = restore_round16(en.length);
+        const u64 span = round16(en.length);
         if (en.offset % 16 == 0 && en.offset >= end && en.offset <= blob_bytes && span <= blob_bytes - en.offset) {
             end = en.offset + span;
             continue;
@@ -446,82 +327,6 @@ int check_structure(mi_ctx* c, const char* who, u64 blob_bytes, const mi_pack_en
         return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes) is off the 16-byte grid, overlaps the entry before it or leaves "
                     "the blob of %llu bytes", who, (unsigned long long)k, (unsigned long long)en.offset, en.length, (unsigned long long)blob_bytes);
     }
-    return MI_OK;
-}
-
-int table_alloc(mi_ctx* c, DevBuf* tags, DevBuf* slots, u64 cap) {
-    HIPCHK(c, tags->ensure(cap * 8));
-    HIPCHK(c, slots->ensure(cap * kSlotWords * 8));
-    HIPCHK(c, hipMemsetAsync(tags->p, 0, cap * 8, c->stream));
-    return MI_OK;
-}
-
-// n records (device) into the table (tags, slots, cap): *n_new of them were not held, *conflict = the smallest row whose digest
-// is held with another length (kNone: none).  Rounds as in mi_index.hip: of k new digests that share their first 8 bytes one
-// claims a slot per round
-int table_insert(mi_packset* s, u64* tags, u64* slots, u64 cap, const u64* d_recs, u64 n, u64* n_new, u64* conflict) {
-    mi_ctx* c = s->ctx;
-    *n_new = 0;
-    *conflict = kNone;
-    if (n == 0) return MI_OK;
-    HIPCHK(c, s->row_state.ensure(n + 16));
-    HIPCHK(c, s->row_slot.ensure(n * 8 + 16));
-    HIPCHK(c, s->counter.ensure(32));
-    u64* d_cnt = s->counter.as<u64>();                  // [0] stored, [1] rows to probe again, [2] smallest conflicting row
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 16, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cnt + 2, 0xFF, 8, c->stream));
-    const u32 per_row = (u32)((n + 255) / 256);
-    const u32 grid = per_row < 2048u ? per_row : 2048u;
-    hipLaunchKernelGGL(packset_begin_kernel, dim3(per_row), dim3(256), 0, c->stream, d_recs, n, cap - 1, s->row_state.as<u8>(),
-                       s->row_slot.as<u64>());
-    u64* h = c->h_word.as<u64>();
-    for (u64 round = 0;; ++round) {
-        hipLaunchKernelGGL(packset_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_recs, n, tags, slots, cap - 1,
-                           s->row_state.as<u8>(), s->row_slot.as<u64>(), d_cnt);
-        hipLaunchKernelGGL(packset_verify_kernel, dim3(per_row), dim3(256), 0, c->stream, d_recs, n, slots, cap - 1,
-                           s->row_state.as<u8>(), s->row_slot.as<u64>(), d_cnt);
-        HIPCHK(c, hipMemcpyAsync(h, d_cnt, 24, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipGetLastError());
-        *n_new = h[0];
-        *conflict = h[2];
-        if (h[1] == 0) return MI_OK;                                      // no 64-bit tag collisions (the normal case)
-        if (round >= cap) return fail(c, MI_ERR_HIP, "pack set: probing does not converge");
-        HIPCHK(c, hipMemsetAsync(d_cnt + 1, 0, 8, c->stream));
-    }
-}
-
-// room for n_more digests under half full.  The new table is complete before the old one goes: a failure leaves the set as it was
-int table_make_room(mi_packset* s, u64 n_more) {
-    mi_ctx* c = s->ctx;
-    const u64 need = (s->count + n_more) * 2;
-    if (need <= s->cap) return MI_OK;
-    u64 cap = s->cap ? s->cap : 1024;
-    while (cap < need) cap <<= 1;
-    DevBuf tags, slots, old;
-    int rc = table_alloc(c, &tags, &slots, cap);
-    if (rc) return rc;
-    if (s->count) {
-        HIPCHK(c, old.ensure(s->count * kSlotWords * 8));
-        HIPCHK(c, s->counter.ensure(32));
-        HIPCHK(c, hipMemsetAsync(s->counter.p, 0, 8, c->stream));
-        hipLaunchKernelGGL(packset_export_kernel, dim3((u32)((s->cap + 255) / 256)), dim3(256), 0, c->stream, s->tags.as<u64>(),
-                           s->slots.as<u64>(), s->cap, old.as<u64>(), s->count, s->counter.as<u64>());
-        HIPCHK(c, hipMemcpyAsync(c->h_word.p, s->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const u64 have = c->h_word.as<u64>()[0];
-        if (have != s->count)
-            return fail(c, MI_ERR_STATE, "pack set holds %llu digests, counted %llu", (unsigned long long)have, (unsigned long long)s->count);
-        u64 n_new = 0, conflict = kNone;
-        rc = table_insert(s, tags.as<u64>(), slots.as<u64>(), cap, old.as<u64>(), s->count, &n_new, &conflict);
-        if (rc) return rc;
-        if (n_new != s->count)
-            return fail(c, MI_ERR_HIP, "pack set rebuild lost entries (%llu of %llu)", (unsigned long long)n_new, (unsigned long long)s->count);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    s->tags = std::move(tags);                          // (DevBuf's move swaps: the old table goes with the locals)
-    s->slots = std::move(slots);
-    s->cap = cap;
     return MI_OK;
 }
 
@@ -543,7 +348,6 @@ int set_add(mi_packset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const
     HIPCHK(c, d_recs.ensure(n * kSlotWords * 8));
     HIPCHK(c, d_off.ensure(n * 8));
     HIPCHK(c, d_len.ensure(n * 8));
-    HIPCHK(c, s->counter.ensure(32));
     HIPCHK(c, hipMemcpyAsync(d_ent.p, entries, n * sizeof(mi_pack_entry), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(packset_unpack_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_ent.as<u64>(), n, (u64)(size_t)mine.p,
                        d_recs.as<u64>(), d_off.as<u64>(), d_len.as<u64>());
@@ -551,7 +355,8 @@ int set_add(mi_packset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const
     if (flags & MI_PACKSET_VERIFY) {
         const auto t0 = std::chrono::steady_clock::now();
         HIPCHK(c, d_got.ensure(n * 32));
-        u64* d_bad = s->counter.as<u64>() + 3;
+        HIPCHK(c, s->bad_cell.ensure(8));
+        u64* d_bad = s->bad_cell.as<u64>();
         HIPCHK(c, hipMemsetAsync(d_bad, 0xFF, 8, st));
         const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
         hash_items(kShaBlobs, mine.as<u8>(), d_off.as<u64>(), d_len.as<u64>(), nullptr, (u32)n, nullptr, c->heads.as<u32>(), nullptr, true,
@@ -571,12 +376,12 @@ int set_add(mi_packset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const
         }
     }
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = table_make_room(s, n);
+    int rc = s->table.make_room(c, n, "pack set");
     if (rc) return rc;
-    u64 n_new = 0, conflict = kNone;
-    rc = table_insert(s, s->tags.as<u64>(), s->slots.as<u64>(), s->cap, d_recs.as<u64>(), n, &n_new, &conflict);
-    s->count += n_new;
-    s->info.n_digests = s->count;
+    u64 sums[3], conflict = kNone;                     // (a plain record has no stored size: only sums[0] says anything)
+    rc = s->table.insert(c, d_recs.as<u64>(), n, sums, &conflict, "pack set");
+    s->table.count += sums[0];
+    s->info.n_digests = s->table.count;
     s->blobs.push_back(std::move(mine));               // the table may point into it by now
     if (rc == MI_OK && conflict != kNone) {
         if (first_bad) *first_bad = conflict;
@@ -618,10 +423,9 @@ int mi_packset_create(mi_ctx* c, uint64_t entries_hint, mi_packset** out) {
     s->info.alg = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? MI_DIGEST_BLAKE2S : MI_DIGEST_SHA256;
     u64 cap = 1024;
     while (cap < entries_hint * 2) cap <<= 1;
-    int rc = table_alloc(c, &s->tags, &s->slots, cap);
+    int rc = s->table.alloc(c, cap);
     if (rc == MI_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, MI_ERR_HIP, "mi_packset_create: the table's memset failed");
     if (rc) { mi_packset_free(s); return rc; }
-    s->cap = cap;
     *out = s;
     return MI_OK;
 }
@@ -695,9 +499,9 @@ int mi_packset_table(const mi_packset* s, const char* who, mi_ctx** ctx, const u
     *ctx = s->ctx;
     const int rc = set_state(s, who);
     if (rc) return rc;
-    *tags = s->tags.as<u64>();
-    *slots = s->slots.as<u64>();
-    *cap = s->cap;
+    *tags = s->table.tags.as<u64>();
+    *slots = s->table.slots.as<u64>();
+    *cap = s->table.cap;
     return MI_OK;
 }
 
@@ -803,7 +607,7 @@ int mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t n_files, c
         HIPCHK(c, hipMemsetAsync(cell + 1, 0, 8, s));
         const u32 row_blocks = (u32)((n_rows + 255) / 256);
         hipLaunchKernelGGL(restore_lookup_kernel, dim3(row_blocks), dim3(256), 0, s, d_dig.as<u8>(), d_len32.as<u32>(), n_rows,
-                           set->tags.as<u64>(), set->slots.as<u64>(), set->cap - 1, d_src.as<u64>(), d_len64.as<u64>(), d_found.as<u32>(), cell);
+                           set->table.tags.as<u64>(), set->table.slots.as<u64>(), set->table.cap - 1, d_src.as<u64>(), d_len64.as<u64>(), d_found.as<u32>(), cell);
         HIPCHK(c, hipMemcpyAsync(h, cell, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(ev[1], s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -839,7 +643,7 @@ int mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t n_files, c
         }
         // assemble: [the first file's offset, the last file's end rounded up to 16).  Files without rows in front lie where the
         // first file with rows lies (an empty file takes no room), so the range begins at the first row
-        const u64 d0 = h_dst[0], d1 = restore_round16(end);
+        const u64 d0 = h_dst[0], d1 = round16(end);
         const u64 n_tiles = (d1 - d0 + kRestoreTile - 1) / kRestoreTile;
         if (n_tiles >> 31)
             return fail(c, MI_ERR_INVALID, "mi_batch_add_recipes: %llu bytes are more than one launch covers", (unsigned long long)(d1 - d0));

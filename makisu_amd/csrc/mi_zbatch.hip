@@ -31,7 +31,7 @@
 // scratch, inside the entry's worst-case span.  The hashing of the verify pass reads up to 67 bytes behind the last scratch
 // span: the 256 bytes it is allocated with.  The want list's kernels index [0, n) of arrays of n elements.
 #include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_gather.h"
 #include "mi_lz4_wave.h"
 #include "mi_lz4_wave_enc.h"
 
@@ -56,45 +56,13 @@ enum : int { kBTotEntries = 0, kBTotSpan = 1, kBTotChunk = 2, kBTotBlob = 3, kBT
 // ... and of mi_zset_missing (kMTotLookup: where zset_lookup_kernel notes the rows the set lacks -- not read)
 enum : int { kMTotWant = 0, kMTotWantBytes = 2, kMTotFirst = 3, kMTotHeld = 4, kMTotHeldBytes = 5, kMTotBad = 6, kMTotLookup = 7 };
 
-static __device__ __forceinline__ u64 zbatch_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kBBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-static __device__ __forceinline__ u64 zbatch_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-
 // the block's sums of Q values a thread: the four waves' results through LDS, in thread 0 (one barrier)
 template <int Q>
 static __device__ __forceinline__ void zbatch_block_sum(u64 (&v)[Q], u64 (*lds)[kBBlock / 64]) {
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
     for (int q = 0; q < Q; ++q) {
-        v[q] = zbatch_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -140,11 +108,11 @@ void zbatch_block_offsets_kernel(u64* __restrict__ block_a, u64* __restrict__ bl
     for (u64 b0 = 0; b0 < n_blocks; b0 += kBBlock) {
         const u64 i = b0 + threadIdx.x;
         u64 t;
-        const u64 ea = zbatch_exclusive_scan(i < n_blocks ? block_a[i] : 0, &t, lds);
+        const u64 ea = block_exclusive_scan_u64<kBBlock>(i < n_blocks ? block_a[i] : 0, &t, lds);
         if (i < n_blocks) block_a[i] = carry_a + ea;
         carry_a += t;
         if (block_b) {
-            const u64 eb = zbatch_exclusive_scan(i < n_blocks ? block_b[i] : 0, &t, lds);
+            const u64 eb = block_exclusive_scan_u64<kBBlock>(i < n_blocks ? block_b[i] : 0, &t, lds);
             if (i < n_blocks) block_b[i] = carry_b + eb;
             carry_b += t;
         }
@@ -173,8 +141,8 @@ void zbatch_compact_kernel(const u8* __restrict__ select, const u64* __restrict_
         if (sel) { ++cnt; span += z_worst_span(len[k]); }
     }
     u64 t;
-    u64 at = zbatch_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 w = zbatch_exclusive_scan(span, &t, lds) + block_span[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kBBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 w = block_exclusive_scan_u64<kBBlock>(span, &t, lds) + block_span[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kBPer; ++k) {
         if (len[k] == kBNone) continue;
@@ -220,7 +188,7 @@ void zbatch_layout_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restr
         if (base + k >= n) continue;
         const u64 w = rows[kBEntryWords * (base + k) + 6];
         const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
-        v[0] += z_round16(stored);
+        v[0] += round16(stored);
         v[1] += stored;
         v[2] += stored == len ? 1 : 0;
     }
@@ -246,10 +214,10 @@ void zbatch_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, 
         const u64 w = base + k < n ? rows[kBEntryWords * (base + k) + 6] : 0;
         len[k] = w & 0xFFFFFFFFull;
         stored[k] = w >> 32;
-        bytes += z_round16(stored[k]);
+        bytes += round16(stored[k]);
     }
     u64 t;
-    u64 dst = zbatch_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kBBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kBPer; ++k) {
         const u64 row = base + k;
@@ -259,110 +227,16 @@ void zbatch_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, 
         e_len[row] = stored[k];
         e_dst[row] = dst;
         r[4] = dst;
-        dst += z_round16(stored[k]);
+        dst += round16(stored[k]);
     }
 }
 
-// ---- gather: 16 KiB tiles of the blob, sources of either kind at any alignment -----------------------------------------------------
-constexpr int kBWG = 256;
-constexpr u32 kBGatherTile = 16384;                   // bytes of the blob a workgroup writes
-constexpr u32 kBUnits = kBGatherTile / 16;            // ... in 16-byte units: an entry takes at least one, so at most as many entries
-constexpr int kBUnitsPer = kBUnits / kBWG;            // units per lane
+// ---- gather: mi_gather.h's tile body, sources of either kind at any alignment ------------------------------------------------------
 
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 zbatch_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// a 16-byte load at ANY alignment from an absolute device address: one global_load_dwordx4 (the address space is said here: a
-// generic pointer would make it flat) -- mi_pack.hip's unit load
-static __device__ __forceinline__ u32x4 zbatch_load16(u64 addr) {
-    typedef const u32x4_unaligned __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
-
-// the first `valid` (< 16) bytes of a unit, the rest zero
-static __device__ __forceinline__ u32x4 zbatch_keep(u32x4 v, u32 valid) {
-    u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32 have = valid > 4u * q ? valid - 4u * q : 0u;
-        w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
-__global__ __launch_bounds__(kBWG)
+__global__ __launch_bounds__(kGatherWG)
 void zbatch_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
                           u64 blob_bytes, u8* __restrict__ blob) {
-    __shared__ u64 s_src[kBUnits];
-    __shared__ u32 s_rel[kBUnits];                   // where the entry begins in the tile
-    __shared__ u32 s_len[kBUnits];
-    __shared__ u64 s_k[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 tile0 = (u64)blockIdx.x * kBGatherTile;
-    const u64 tile1 = tile0 + kBGatherTile < blob_bytes ? tile0 + kBGatherTile : blob_bytes;
-    if (wave < 2) {
-        const u64 k = zbatch_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
-        if (lane == 0) s_k[wave] = k;
-    }
-    __syncthreads();
-    const u64 k0 = s_k[0];
-    const u64 reach = s_k[1] - k0 + 1;
-    const u32 cnt = reach < kBUnits ? (u32)reach : kBUnits;
-    for (u32 i = threadIdx.x; i < cnt; i += kBWG) {
-        u64 src = e_src[k0 + i], len = e_len[k0 + i];
-        const u64 dst = e_dst[k0 + i];
-        u32 rel = (u32)(dst - tile0);
-        if (dst < tile0) {                           // the first entry may begin in front of the tile: the tile sees what is left
-            const u64 skip = tile0 - dst;            // of it -- skip is a multiple of 16 below its stored size
-            src += skip;
-            len -= skip;
-            rel = 0;
-        }
-        s_src[i] = src;
-        s_len[i] = (u32)len;
-        s_rel[i] = rel;
-    }
-    __syncthreads();
-    u64 src[kBUnitsPer];
-    u32 valid[kBUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kBUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kBWG) * 16;
-        src[j] = s_src[0];                            // a unit behind the blob's end (the last tile) loads the tile's first unit and
-        valid[j] = 0;                                 // drops it: a lane's four loads are in flight together
-        if (tile0 + r >= tile1) continue;
-        u32 lo = 0, hi = cnt;                         // the entry this unit lies in: the last that begins at or before it
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (s_rel[mid] <= r) lo = mid; else hi = mid;
-        }
-        const u32 o = r - s_rel[lo], len = s_len[lo];
-        if (o < len) {                                // (always, for entries of at least one byte)
-            src[j] = s_src[lo] + o;                   // a multiple of 16 behind the entry's first byte, whatever alignment that has
-            valid[j] = len - o;
-        }
-    }
-    u32x4 v[kBUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kBUnitsPer; ++j) v[j] = zbatch_load16(src[j]);
-#pragma unroll
-    for (int j = 0; j < kBUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kBWG) * 16;
-        if (tile0 + r >= tile1) continue;
-        if (valid[j] < 16) v[j] = zbatch_keep(v[j], valid[j]);   // the entry's last unit: zero at and beyond its stored bytes
-        *(u32x4*)(blob + tile0 + r) = v[j];
-    }
+    gather_tile<false>(e_src, e_len, e_dst, n_entries, blob_bytes, blob);
 }
 
 // ---- MI_ZPACK_VERIFY: the digests of the decoded chunks against the batch's own table at chunk_index ------------------------------
@@ -430,7 +304,7 @@ void zbatch_want_rows_kernel(const i64* __restrict__ dup_of, const u8* __restric
     for (int k = 0; k < kBPer; ++k)
         if (base + k < n && dup_of[base + k] < 0 && !held[base + k]) { sel |= 1u << k; ++cnt; }
     u64 t;
-    u64 at = zbatch_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kBBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kBPer; ++k)
         if (sel & (1u << k)) want_rows[at++] = base + k;
@@ -552,7 +426,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     if (blob_bytes < 16 * n_sel || stored_bytes > chunk_bytes || stored_bytes > blob_bytes || n_raw > n_sel)
         return fail(c, MI_ERR_HIP, "%s: the layout counted %llu stored bytes (%llu raw entries) in a blob of %llu for %llu chunk bytes", who,
                     (unsigned long long)stored_bytes, (unsigned long long)n_raw, (unsigned long long)blob_bytes, (unsigned long long)chunk_bytes);
-    const u64 n_tiles = (blob_bytes + kBGatherTile - 1) / kBGatherTile;
+    const u64 n_tiles = (blob_bytes + kGatherTile - 1) / kGatherTile;
     if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
     // the blob: device memory of its own.  Does not fit: MI_ERR_NOMEM naming both sizes, nothing has changed
     if ((rc = mi_zpack_alloc(c, who, n_sel, blob_bytes, &mine.z, &d_blob, &h_rows))) return rc;
@@ -566,7 +440,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     HIPCHK(c, hipEventRecord(ev[6], s));
     hipLaunchKernelGGL(zbatch_place_kernel, dim3((u32)nb_sel), dim3(kBBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n_sel, block_bytes,
                        (u64)(size_t)b->arena.p, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
-    hipLaunchKernelGGL(zbatch_gather_kernel, dim3((u32)n_tiles), dim3(kBWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel, blob_bytes,
+    hipLaunchKernelGGL(zbatch_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel, blob_bytes,
                        (u8*)d_blob);
     HIPCHK(c, hipEventRecord(ev[7], s));
     if (verify) {

@@ -36,7 +36,7 @@
 // it -- none does -- is stored raw).  The gather reads aligned units inside [src, src + round16(stored)) of the input pack or of
 // a scratch span.  The hashing of the verify pass reads up to 67 bytes behind the last scratch span: DevBuf's 256 bytes.
 #include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_gather.h"
 #include "mi_lz4_wave.h"
 #include "mi_lz4_wave_enc.h"
 #include "host_blake2s.h"
@@ -54,7 +54,7 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kZNone = ~0ull;
-// z_round16, z_worst_span (what one chunk of n bytes takes in scratch): csrc/mi_lz4_wave_enc.h
+// z_worst_span (what one chunk of n bytes takes in scratch): csrc/mi_lz4_wave_enc.h
 
 constexpr int kZEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
 static_assert(sizeof(mi_zpack_entry) == 56 && kZEntryWords == 7 && sizeof(mi_pack_entry) == 56, "mi_zpack_entry is seven 8-byte words");
@@ -80,38 +80,6 @@ constexpr int kZPer   = 8;                            // rows per thread
 constexpr int kZTile  = kZBlock * kZPer;              // 2048 rows per block
 enum : int { kZTotBlob = 0, kZTotStored = 1, kZTotRaw = 2, kZTotChunk = 3, kZTotBad = 4 };
 
-static __device__ __forceinline__ u64 z_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kZBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-static __device__ __forceinline__ u64 z_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-
 // per block of kZTile rows: the rounded-up stored bytes; into the totals: stored bytes, raw entries, chunk bytes
 __global__ __launch_bounds__(kZBlock)
 void zpack_block_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restrict__ block_bytes, u64* __restrict__ totals) {
@@ -124,14 +92,14 @@ void zpack_block_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restric
         if (base + k >= n) continue;
         const u64 w = rows[kZEntryWords * (base + k) + 6];
         const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
-        v[0] += z_round16(stored);
+        v[0] += round16(stored);
         v[1] += stored;
         v[2] += stored == len ? 1 : 0;
         v[3] += len;
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        v[q] = z_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -159,7 +127,7 @@ void zpack_block_offsets_kernel(u64* __restrict__ block_bytes, u64 n_blocks, u64
         const u64 i = b0 + threadIdx.x;
         const u64 v = i < n_blocks ? block_bytes[i] : 0;
         u64 t;
-        const u64 e = z_exclusive_scan(v, &t, lds);
+        const u64 e = block_exclusive_scan_u64<kZBlock>(v, &t, lds);
         if (i < n_blocks) block_bytes[i] = carry + e;
         carry += t;
     }
@@ -180,10 +148,10 @@ void zpack_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, u
         const u64 w = base + k < n ? rows[kZEntryWords * (base + k) + 6] : 0;
         len[k] = w & 0xFFFFFFFFull;
         stored[k] = w >> 32;
-        bytes += z_round16(stored[k]);
+        bytes += round16(stored[k]);
     }
     u64 t;
-    u64 dst = z_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kZBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kZPer; ++k) {
         const u64 row = base + k;
@@ -193,109 +161,16 @@ void zpack_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, u
         e_len[row] = stored[k];
         e_dst[row] = dst;
         r[4] = dst;
-        dst += z_round16(stored[k]);
+        dst += round16(stored[k]);
     }
 }
 
-// ---- gather: mi_fetch.hip's, restated -----------------------------------------------------------------------------------------
-constexpr int kZWG = 256;
-constexpr u32 kZGatherTile = 16384;                   // bytes of the blob a workgroup writes
-constexpr u32 kZUnits = kZGatherTile / 16;            // ... in 16-byte units: an entry takes at least one, so at most as many entries
-constexpr int kZUnitsPer = kZUnits / kZWG;            // units per lane
+// ---- gather: mi_gather.h's tile body over aligned sources (a raw chunk in the input pack, a coded one in scratch) -------------
 
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 z_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// an ALIGNED 16-byte load from an absolute device address (the address space is said here: a generic pointer would make it flat)
-static __device__ __forceinline__ u32x4 z_load16(u64 addr) {
-    typedef const u32x4 __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
-
-// the first `valid` (< 16) bytes of a unit, the rest zero
-static __device__ __forceinline__ u32x4 z_keep(u32x4 v, u32 valid) {
-    u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32 have = valid > 4u * q ? valid - 4u * q : 0u;
-        w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
-__global__ __launch_bounds__(kZWG)
+__global__ __launch_bounds__(kGatherWG)
 void zpack_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
                          u64 blob_bytes, u8* __restrict__ blob) {
-    __shared__ u64 s_src[kZUnits];
-    __shared__ u32 s_rel[kZUnits];                   // where the entry begins in the tile
-    __shared__ u32 s_len[kZUnits];
-    __shared__ u64 s_k[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 tile0 = (u64)blockIdx.x * kZGatherTile;
-    const u64 tile1 = tile0 + kZGatherTile < blob_bytes ? tile0 + kZGatherTile : blob_bytes;
-    if (wave < 2) {
-        const u64 k = z_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
-        if (lane == 0) s_k[wave] = k;
-    }
-    __syncthreads();
-    const u64 k0 = s_k[0];
-    const u64 reach = s_k[1] - k0 + 1;
-    const u32 cnt = reach < kZUnits ? (u32)reach : kZUnits;
-    for (u32 i = threadIdx.x; i < cnt; i += kZWG) {
-        u64 src = e_src[k0 + i], len = e_len[k0 + i];
-        const u64 dst = e_dst[k0 + i];
-        u32 rel = (u32)(dst - tile0);
-        if (dst < tile0) {                           // the first entry may begin in front of the tile: the tile sees what is left
-            const u64 skip = tile0 - dst;            // of it -- skip is a multiple of 16 below its length
-            src += skip;
-            len -= skip;
-            rel = 0;
-        }
-        s_src[i] = src;
-        s_len[i] = (u32)len;
-        s_rel[i] = rel;
-    }
-    __syncthreads();
-    u64 src[kZUnitsPer];
-    u32 valid[kZUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kZUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kZWG) * 16;
-        src[j] = s_src[0];                            // a unit behind the blob's end (the last tile) loads the tile's first unit and
-        valid[j] = 0;                                 // drops it: a lane's four loads are in flight together
-        if (tile0 + r >= tile1) continue;
-        u32 lo = 0, hi = cnt;                         // the entry this unit lies in: the last that begins at or before it
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (s_rel[mid] <= r) lo = mid; else hi = mid;
-        }
-        const u32 o = r - s_rel[lo], len = s_len[lo];
-        if (o < len) {                                // (always, for entries of at least one byte)
-            src[j] = s_src[lo] + o;                   // a multiple of 16 behind an aligned address
-            valid[j] = len - o;
-        }
-    }
-    u32x4 v[kZUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kZUnitsPer; ++j) v[j] = z_load16(src[j]);
-#pragma unroll
-    for (int j = 0; j < kZUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kZWG) * 16;
-        if (tile0 + r >= tile1) continue;
-        if (valid[j] < 16) v[j] = z_keep(v[j], valid[j]);   // the entry's last unit: zero at and beyond its stored bytes
-        *(u32x4*)(blob + tile0 + r) = v[j];
-    }
+    gather_tile<true>(e_src, e_len, e_dst, n_entries, blob_bytes, blob);
 }
 
 // ---- decode ---------------------------------------------------------------------------------------------------------------------
@@ -314,14 +189,14 @@ void zpack_decode_kernel(const u8* __restrict__ zblob, const u64* __restrict__ r
         if (stored == len) {                          // raw: aligned units, the bytes at and beyond the length zeroed in registers
             for (u64 u = (u64)lane * 16; u < len; u += 64 * 16) {
                 u32x4 v = *(const u32x4*)(src + u);
-                if (len - u < 16) v = z_keep(v, (u32)(len - u));
+                if (len - u < 16) v = keep_first_bytes(v, (u32)(len - u));
                 *(u32x4*)(dst + u) = v;
             }
         } else {
             rule = z_decode_block(src, stored, dst, len, lane);
-            if (len + lane < z_round16(len)) dst[len + lane] = 0;
+            if (len + lane < round16(len)) dst[len + lane] = 0;
         }
-        const bool pad_set = stored + lane < z_round16(stored) && src[stored + lane] != 0;
+        const bool pad_set = stored + lane < round16(stored) && src[stored + lane] != 0;
         if (__ballot(pad_set) != 0 && rule == 0) rule = mi_host::kLz4PadNotZero;
         if (lane == 0) {
             rule_out[k] = rule;
@@ -477,7 +352,7 @@ bool structure_ok(u64 blob_bytes, const mi_zpack_entry* entries, u64 n, u64* fir
     u64 end = 0;                                       // where the previous entry's unit(s) end
     for (u64 k = 0; k < n; ++k) {
         const mi_zpack_entry& en = entries[k];
-        const u64 span = z_round16(en.stored);
+        const u64 span = round16(en.stored);
         if (en.stored != 0 && en.stored <= en.length && en.offset % 16 == 0 && en.offset >= end && en.offset <= blob_bytes &&
             span <= blob_bytes - en.offset) {
             end = en.offset + span;
@@ -534,7 +409,7 @@ int mi_zpack_decode_plain(mi_ctx* c, const char* who, const void* d_zblob, const
         plain[k].chunk_index = entries[k].chunk_index;
         plain[k].length = entries[k].length;
         plain[k].reserved = 0;
-        plain_bytes += z_round16(entries[k].length);
+        plain_bytes += round16(entries[k].length);
     }
     *plain_bytes_out = plain_bytes;
     *bad_out = kZNone;
@@ -668,7 +543,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     u64 scratch_bytes = 0;
     for (u64 k = 0; k < n; ++k) {
         const u64 len = rows[k].length;
-        if (len == 0 || rows[k].offset % 16 || rows[k].offset > pack_bytes || z_round16(len) > pack_bytes - rows[k].offset)
+        if (len == 0 || rows[k].offset % 16 || rows[k].offset > pack_bytes || round16(len) > pack_bytes - rows[k].offset)
             return fail(c, MI_ERR_INVALID, "%s: entry %llu of the pack (offset %llu, %u bytes) has no bytes or leaves its blob of %llu bytes", who,
                         (unsigned long long)k, (unsigned long long)rows[k].offset, rows[k].length, (unsigned long long)pack_bytes);
         w_off[k] = scratch_bytes;
@@ -713,7 +588,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
         return fail(c, MI_ERR_HIP, "%s: the plan counted %llu stored bytes in a blob of %llu for %llu chunk bytes (the pack states %llu)", who,
                     (unsigned long long)zi.stored_bytes, (unsigned long long)blob_bytes, (unsigned long long)zi.chunk_bytes,
                     (unsigned long long)pi.chunk_bytes);
-    const u64 n_tiles = (blob_bytes + kZGatherTile - 1) / kZGatherTile;
+    const u64 n_tiles = (blob_bytes + kGatherTile - 1) / kGatherTile;
     if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
     if ((e = alloc_exact(&mine.z->blob, blob_bytes)) != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
     HIPCHK(c, e_src.ensure(n * 8));
@@ -726,7 +601,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     HIPCHK(c, hipEventRecord(ev[3], s));
     hipLaunchKernelGGL(zpack_place_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n, block_bytes,
                        (u64)(size_t)d_pack, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
-    hipLaunchKernelGGL(zpack_gather_kernel, dim3((u32)n_tiles), dim3(kZWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n, blob_bytes,
+    hipLaunchKernelGGL(zpack_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n, blob_bytes,
                        mine.z->blob.as<u8>());
     HIPCHK(c, hipEventRecord(ev[4], s));
     if (flags & MI_ZPACK_VERIFY) {
@@ -878,7 +753,7 @@ int mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* 
             ok = mi_host::lz4_block_decode(src, en.stored, plain.data(), en.length) == mi_host::kLz4Ok;
             chunk = plain.data();
         }
-        for (u64 i = en.stored; i < z_round16(en.stored); ++i) ok = ok && src[i] == 0;
+        for (u64 i = en.stored; i < round16(en.stored); ++i) ok = ok && src[i] == 0;
         if (!ok) {                                     // the smallest entry that does not decode: nothing behind it matters
             if (first_bad) *first_bad = k;
             return MI_ERR_INVALID;

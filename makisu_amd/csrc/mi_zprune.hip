@@ -3,7 +3,7 @@
 // is touched (mi_zset_prune); and what is resident (mi_zset_get_usage).  For the digests still held the set answers every call
 // as before: the stored form, the length | stored word and which form is held never change, only a moved span's address.
 //
-//   mark      one thread a request row: zset_lookup_kernel's walk (the tag first, then all 32 bytes); the slot found gets a
+//   mark      one thread a request row: slot_table_find's walk (the tag first, then all 32 bytes); the slot found gets a
 //             byte in a per-slot mark array, misses are counted (one atomic a wave);
 //   sweep     over the slots, grid-stride: survivor or victim by mark and mode.  A survivor's blob is found by binary search
 //             of its span address in the sorted blob bases and remembered per slot; per-blob live bytes (round16(stored)) go
@@ -18,7 +18,7 @@
 //             offsets, every lane's units loaded before the first is stored.  Whole units, the pad as it was;
 //   repoint   the moved spans' new addresses into a per-slot array: THE OLD TABLE IS NEVER WRITTEN;
 //   rebuild   the survivors' records, with the repointed addresses, exported into a record array and inserted into a fresh
-//             table sized for them through mi_zset.hip's own table_insert (one synchronisation a probing round: one, unless
+//             table sized for them -- a SlotTable of this call's (mi_slot_table.h: one synchronisation a probing round: one, unless
 //             64-bit tags collide).  Open addressing with linear probing cannot delete in place; a rebuild is the simple
 //             correct form, and it shrinks the table.  Synchronisation 3 behind it; then the table is swapped, the dead and
 //             the compacted blobs are freed and the new blob joins the set.
@@ -35,7 +35,6 @@
 // ends on the blob's last unit -- and WRITES aligned units inside [0, moved_bytes) of the new blob.  repoint WRITES new_addr at
 // slots the plan listed (< cap).  export READS slot_blob, slots, new_addr [0, cap), WRITES records [0, limit) (the cursor is checked).
 #include "mi_zset_local.h"
-#include "mi_item_loads.h"
 
 using namespace mi;
 
@@ -43,55 +42,13 @@ namespace mi {
 
 constexpr u64 kPNone = ~0ull;
 constexpr u32 kPNoBlob = 0xFFFFFFFFu;                 // slot_blob: an empty slot, or a victim
-constexpr int kPSlotWords = 6;                        // digest 4 | device address | length, stored (mi_zset.hip's slot)
 enum : u8 { kPStay = 0, kPCompact = 1, kPDead = 2 };  // a blob's fate
 enum : int { kPTotUnknown = 0, kPTotSurvive = 1, kPTotDropped = 2, kPTotDropStored = 3, kPTotDropChunk = 4, kPTotCursor = 6 };
-
-__host__ __device__ static inline u64 zprune_round16(u64 v) { return (v + 15) & ~15ull; }
-
-static __device__ __forceinline__ bool zprune_digest_eq32(const u8* a, const u8* b) {
-    const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
-    const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
-    const u32x4 d0 = a0 ^ b0, d1 = a1 ^ b1;
-    return (d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0;
-}
 
 constexpr int kPBlock = 256;
 constexpr int kPPer   = 8;                            // slots per thread
 constexpr int kPTile  = kPBlock * kPPer;              // 2048 slots per block
 constexpr int kPBins  = 256;                          // blobs with a bin in LDS
-
-static __device__ __forceinline__ u64 zprune_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kPBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-static __device__ __forceinline__ u64 zprune_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
 
 // ---- mark ---------------------------------------------------------------------------------------------------------------------
 // mark[slot] = 1 for the slot that holds row r's digest; totals[kPTotUnknown] += rows whose digest the set does not hold
@@ -101,21 +58,9 @@ void zprune_mark_kernel(const u8* __restrict__ digests, u64 n, const u64* __rest
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     bool miss = false;
     if (r < n) {
-        const u8* d = digests + 32 * r;
-        const u64 first8 = *(const u64*)d;
-        const u64 tag = first8 ? first8 : 1ull;
-        u64 slot = tag & mask;
-        miss = true;
-        for (u64 walked = 0; walked <= mask; ++walked) {     // (the table is at most half full: an empty slot ends every walk)
-            const u64 t = tags[slot];
-            if (t == 0ull) break;
-            if (t == tag && zprune_digest_eq32((const u8*)(slots + kPSlotWords * slot), d)) {
-                mark[slot] = 1;                                // (rows that repeat a digest store the same byte)
-                miss = false;
-                break;
-            }
-            slot = (slot + 1) & mask;
-        }
+        const u64 slot = slot_table_find(tags, slots, mask, digests + 32 * r);
+        miss = slot == kSlotNone;
+        if (!miss) mark[slot] = 1;                             // (rows that repeat a digest store the same byte)
     }
     const u64 misses = (u64)__popcll(__ballot(miss));
     if ((threadIdx.x & 63) == 0 && misses) atomicAdd((unsigned long long*)&totals[kPTotUnknown], (unsigned long long)misses);
@@ -137,11 +82,11 @@ void zprune_sweep_kernel(const u64* __restrict__ tags, const u64* __restrict__ s
     for (u64 s = (u64)blockIdx.x * kPBlock + threadIdx.x; s < cap; s += (u64)gridDim.x * kPBlock) {
         u32 b = kPNoBlob;
         if (tags[s] != 0ull) {
-            const u64 word = slots[kPSlotWords * s + 5];
+            const u64 word = slots[kSlotWords * s + 5];
             const u64 len = word & 0xFFFFFFFFull, stored = word >> 32;
             const bool survives = (mark[s] != 0) == (keep != 0);
             if (survives && n_blobs) {
-                const u64 addr = slots[kPSlotWords * s + 4];
+                const u64 addr = slots[kSlotWords * s + 4];
                 u32 lo = 0, hi = n_blobs;             // the last base at or below the span's address
                 while (hi - lo > 1) {
                     const u32 mid = lo + ((hi - lo) >> 1);
@@ -149,8 +94,8 @@ void zprune_sweep_kernel(const u64* __restrict__ tags, const u64* __restrict__ s
                 }
                 b = lo;
                 ++v[0];
-                if (b < (u32)kPBins) atomicAdd(&bins[b], (unsigned long long)zprune_round16(stored));
-                else atomicAdd((unsigned long long*)&live[b], (unsigned long long)zprune_round16(stored));
+                if (b < (u32)kPBins) atomicAdd(&bins[b], (unsigned long long)round16(stored));
+                else atomicAdd((unsigned long long*)&live[b], (unsigned long long)round16(stored));
             } else {
                 ++v[1];
                 v[2] += stored;
@@ -161,7 +106,7 @@ void zprune_sweep_kernel(const u64* __restrict__ tags, const u64* __restrict__ s
     }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        v[q] = zprune_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -194,11 +139,11 @@ void zprune_block_sums_kernel(const u32* __restrict__ slot_blob, const u8* __res
     for (int k = 0; k < kPPer; ++k) {
         if (!zprune_moves(slot_blob, cls, base + k, cap)) continue;
         ++v[0];
-        v[1] += zprune_round16(slots[kPSlotWords * (base + k) + 5] >> 32);
+        v[1] += round16(slots[kSlotWords * (base + k) + 5] >> 32);
     }
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
-        v[q] = zprune_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -219,8 +164,8 @@ void zprune_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ 
         const u64 i = b0 + threadIdx.x;
         const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
         u64 tc, tb;
-        const u64 ec = zprune_exclusive_scan(vc, &tc, lds);
-        const u64 eb = zprune_exclusive_scan(vb, &tb, lds);
+        const u64 ec = block_exclusive_scan_u64<kPBlock>(vc, &tc, lds);
+        const u64 eb = block_exclusive_scan_u64<kPBlock>(vb, &tb, lds);
         if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
         carry_c += tc;
         carry_b += tb;
@@ -241,16 +186,16 @@ void zprune_compact_kernel(const u32* __restrict__ slot_blob, const u8* __restri
 #pragma unroll
     for (int k = 0; k < kPPer; ++k) {
         const bool m = zprune_moves(slot_blob, cls, base + k, cap);
-        len[k] = m ? zprune_round16(slots[kPSlotWords * (base + k) + 5] >> 32) : 0;
+        len[k] = m ? round16(slots[kSlotWords * (base + k) + 5] >> 32) : 0;
         if (m) { sel |= 1u << k; ++cnt; bytes += len[k]; }
     }
     u64 t;
-    u64 at = zprune_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = zprune_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kPBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kPBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kPPer; ++k) {
         if (!(sel & (1u << k))) continue;
-        e_src[at] = slots[kPSlotWords * (base + k) + 4];
+        e_src[at] = slots[kSlotWords * (base + k) + 4];
         e_len[at] = len[k];
         e_dst[at] = dst;
         e_slot[at] = base + k;
@@ -259,31 +204,11 @@ void zprune_compact_kernel(const u32* __restrict__ slot_blob, const u8* __restri
     }
 }
 
-// ---- move: zset_gather_kernel, restated without the masking -------------------------------------------------------------------
+// ---- move: the gather of mi_gather.h WITHOUT the masking, the lengths clamped to the tile: a kernel of its own ----------------
 constexpr int kPWG = 256;
 constexpr u32 kPGatherTile = 16384;                   // bytes of the blob a workgroup writes
 constexpr u32 kPUnits = kPGatherTile / 16;            // ... in 16-byte units: a span takes at least one, so at most as many spans
 constexpr int kPUnitsPer = kPUnits / kPWG;            // units per lane
-
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 zprune_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// an ALIGNED 16-byte load from an absolute device address (the address space is said here: a generic pointer would make it flat)
-static __device__ __forceinline__ u32x4 zprune_load16(u64 addr) {
-    typedef const u32x4 __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
 
 __global__ __launch_bounds__(kPWG)
 void zprune_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
@@ -296,7 +221,7 @@ void zprune_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__
     const u64 tile0 = (u64)blockIdx.x * kPGatherTile;
     const u64 tile1 = tile0 + kPGatherTile < blob_bytes ? tile0 + kPGatherTile : blob_bytes;
     if (wave < 2) {
-        const u64 k = zprune_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
+        const u64 k = wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
         if (lane == 0) s_k[wave] = k;
     }
     __syncthreads();
@@ -339,7 +264,7 @@ void zprune_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__
     }
     u32x4 v[kPUnitsPer];
 #pragma unroll
-    for (int j = 0; j < kPUnitsPer; ++j) v[j] = zprune_load16(src[j]);
+    for (int j = 0; j < kPUnitsPer; ++j) v[j] = load16_global(src[j]);
 #pragma unroll
     for (int j = 0; j < kPUnitsPer; ++j) {
         const u32 r = ((u32)threadIdx.x + (u32)j * kPWG) * 16;
@@ -365,7 +290,7 @@ void zprune_export_kernel(const u32* __restrict__ slot_blob, const u64* __restri
     if (at >= limit) return;
     const u64 moved = new_addr ? new_addr[s] : 0ull;
 #pragma unroll
-    for (int w = 0; w < kPSlotWords; ++w) out[kPSlotWords * at + w] = w == 4 && moved ? moved : slots[kPSlotWords * s + w];
+    for (int w = 0; w < kSlotWords; ++w) out[kSlotWords * at + w] = w == 4 && moved ? moved : slots[kSlotWords * s + w];
 }
 
 // ---- usage: the sum of round16(stored) over the occupied slots --------------------------------------------------------------------
@@ -375,8 +300,8 @@ void zprune_live_kernel(const u64* __restrict__ tags, const u64* __restrict__ sl
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u64 v = 0;
     for (u64 s = (u64)blockIdx.x * kPBlock + threadIdx.x; s < cap; s += (u64)gridDim.x * kPBlock)
-        if (tags[s] != 0ull) v += zprune_round16(slots[kPSlotWords * s + 5] >> 32);
-    v = zprune_wave_sum(v);
+        if (tags[s] != 0ull) v += round16(slots[kSlotWords * s + 5] >> 32);
+    v = wave_sum(v);
     if (lane == 0) lds[wave] = v;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -431,13 +356,15 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     if (n >> 32) return fail(c, MI_ERR_INVALID, "%s: %llu rows, a request holds fewer than 2^32", who, (unsigned long long)n);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
-    const u64 cap = s->cap, n_blobs = s->blobs.size();
+    const u64 cap = s->table.cap, n_blobs = s->blobs.size();
     mi_prune_info pi = {};
     pi.n_rows = n;
     u64 extra = 0;                                             // what this call allocates, from the sizes
 
-    DevBuf d_dig, d_mark, d_slot_blob, d_bases, d_live, d_tot, d_cls, d_scan, d_list, d_new_addr, d_recs, row_state, row_slot, counter;
-    DevBuf new_blob, tags, slots;
+    DevBuf d_dig, d_mark, d_slot_blob, d_bases, d_live, d_tot, d_cls, d_scan, d_list, d_new_addr, d_recs;
+    DevBuf new_blob;
+    SlotTable fresh;                                           // the table the survivors go into: this call's, scratch and all
+    fresh.sum_bytes = true;                                    // (as the set's own inserts run)
     Event ev[8];
     struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
@@ -465,10 +392,10 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     if (n_blobs) HIPCHK(c, hipMemsetAsync(d_live.p, 0, n_blobs * 8, st));
     HIPCHK(c, hipMemsetAsync(tot, 0, 64, st));
     if (n)
-        hipLaunchKernelGGL(zprune_mark_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_dig.as<u8>(), n, s->tags.as<u64>(),
-                           s->slots.as<u64>(), cap - 1, d_mark.as<u8>(), tot);
+        hipLaunchKernelGGL(zprune_mark_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_dig.as<u8>(), n, s->table.tags.as<u64>(),
+                           s->table.slots.as<u64>(), cap - 1, d_mark.as<u8>(), tot);
     const u32 sweep_grid = (u32)std::min<u64>((cap + kPBlock - 1) / kPBlock, 2048);
-    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPBlock), 0, st, s->tags.as<u64>(), s->slots.as<u64>(), cap, d_mark.as<u8>(),
+    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPBlock), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, d_mark.as<u8>(),
                        flags == MI_ZSET_PRUNE_KEEP ? 1u : 0u, d_bases.as<u64>(), (u32)n_blobs, d_slot_blob.as<u32>(), d_live.as<u64>(), tot);
     HIPCHK(c, hipEventRecord(ev[1], st));
     HIPCHK(c, hipMemcpyAsync(h, tot, 40, hipMemcpyDeviceToHost, st));
@@ -483,9 +410,9 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     pi.n_dropped = h[kPTotDropped];
     pi.dropped_stored_bytes = h[kPTotDropStored];
     pi.dropped_chunk_bytes = h[kPTotDropChunk];
-    if (n_survive + pi.n_dropped != s->count || pi.dropped_stored_bytes > s->info.stored_bytes || pi.dropped_chunk_bytes > s->info.chunk_bytes)
+    if (n_survive + pi.n_dropped != s->table.count || pi.dropped_stored_bytes > s->info.stored_bytes || pi.dropped_chunk_bytes > s->info.chunk_bytes)
         return fail(c, MI_ERR_STATE, "%s: the set holds %llu digests, the sweep counted %llu that stay and %llu that go", who,
-                    (unsigned long long)s->count, (unsigned long long)n_survive, (unsigned long long)pi.n_dropped);
+                    (unsigned long long)s->table.count, (unsigned long long)n_survive, (unsigned long long)pi.n_dropped);
     if (pi.n_dropped == 0) {                                   // nothing to drop: the set is untouched
         pi.peak_extra_bytes = extra;
         if (info) *info = pi;
@@ -516,7 +443,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         u64* totals = block_bytes + nb;
         HIPCHK(c, hipEventRecord(ev[2], st));
         HIPCHK(c, hipMemcpyAsync(d_cls.p, cls.data(), n_blobs, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->slots.as<u64>(),
+        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(),
                            cap, block_cnt, block_bytes);
         hipLaunchKernelGGL(zprune_block_offsets_kernel, dim3(1), dim3(kPBlock), 0, st, block_cnt, block_bytes, nb, totals);
         HIPCHK(c, hipEventRecord(ev[3], st));
@@ -551,12 +478,12 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         PRUNE_ALLOC(d_list, 4 * n_move * 8, "the move list");
         PRUNE_ALLOC(d_new_addr, cap * 8, "the per-slot address array");
     }
-    PRUNE_ALLOC(tags, new_cap * 8, "the new table's tags");
-    PRUNE_ALLOC(slots, new_cap * kPSlotWords * 8, "the new table's slots");
-    PRUNE_ALLOC(d_recs, n_survive * kPSlotWords * 8, "the survivors' records");
-    PRUNE_ALLOC(row_state, n_survive + 16, "the insert's row states");
-    PRUNE_ALLOC(row_slot, n_survive * 8 + 16, "the insert's row slots");
-    PRUNE_ALLOC(counter, 64, "the insert's counters");
+    PRUNE_ALLOC(fresh.tags, new_cap * 8, "the new table's tags");
+    PRUNE_ALLOC(fresh.slots, new_cap * kSlotWords * 8, "the new table's slots");
+    PRUNE_ALLOC(d_recs, n_survive * kSlotWords * 8, "the survivors' records");
+    PRUNE_ALLOC(fresh.row_state, n_survive + 16, "the insert's row states");
+    PRUNE_ALLOC(fresh.row_slot, n_survive * 8 + 16, "the insert's row slots");
+    PRUNE_ALLOC(fresh.counter, 64, "the insert's counters");
     pi.peak_extra_bytes = extra;
 
     // ---- move, repoint ----------------------------------------------------------------------------------------------------------
@@ -569,7 +496,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         const u64 n_tiles = (moved_bytes + kPGatherTile - 1) / kPGatherTile;
         HIPCHK(c, hipEventRecord(ev[4], st));
         HIPCHK(c, hipMemsetAsync(d_new_addr.p, 0, cap * 8, st));
-        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->slots.as<u64>(), cap,
+        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(), cap,
                            block_cnt, block_bytes, e_src, e_len, e_dst, e_slot);
         hipLaunchKernelGGL(zprune_gather_kernel, dim3((u32)n_tiles), dim3(kPWG), 0, st, e_src, e_len, e_dst, n_move, moved_bytes, new_blob.as<u8>());
         hipLaunchKernelGGL(zprune_repoint_kernel, dim3((u32)((n_move + 255) / 256)), dim3(256), 0, st, e_slot, e_dst, n_move,
@@ -579,19 +506,13 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
 
     // ---- rebuild: the new table is complete before the old one goes ----------------------------------------------------------------
     HIPCHK(c, hipEventRecord(ev[6], st));
-    rc = mi_zset_table_alloc(c, &tags, &slots, new_cap);       // (both are large enough: only the tags' memset is enqueued)
+    rc = fresh.alloc(c, new_cap);                              // (both are large enough: only the tags' memset is enqueued)
     if (rc) return rc;
     if (n_survive) {
-        hipLaunchKernelGGL(zprune_export_kernel, dim3((u32)((cap + 255) / 256)), dim3(256), 0, st, d_slot_blob.as<u32>(), s->slots.as<u64>(), cap,
+        hipLaunchKernelGGL(zprune_export_kernel, dim3((u32)((cap + 255) / 256)), dim3(256), 0, st, d_slot_blob.as<u32>(), s->table.slots.as<u64>(), cap,
                            n_move ? d_new_addr.as<u64>() : (const u64*)nullptr, d_recs.as<u64>(), n_survive, tot + kPTotCursor);
         u64 sums[3], conflict = kPNone;
-        std::swap(s->row_state, row_state);                    // the insert's scratch is this call's: the set keeps no allocation of it
-        std::swap(s->row_slot, row_slot);
-        std::swap(s->counter, counter);
-        rc = mi_zset_table_insert(s, tags.as<u64>(), slots.as<u64>(), new_cap, d_recs.as<u64>(), n_survive, sums, &conflict);
-        std::swap(s->row_state, row_state);
-        std::swap(s->row_slot, row_slot);
-        std::swap(s->counter, counter);
+        rc = fresh.insert(c, d_recs.as<u64>(), n_survive, sums, &conflict, "compressed pack set");
         if (rc) return rc;
         if (sums[0] != n_survive || conflict != kPNone)
             return fail(c, MI_ERR_HIP, "%s: the rebuild took %llu of %llu records", who, (unsigned long long)sums[0], (unsigned long long)n_survive);
@@ -608,10 +529,10 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     pi.ms_rebuild = ms;
 
     // ---- the set changes: nothing below can fail -------------------------------------------------------------------------------
-    std::swap(s->tags, tags);                                  // (the old table goes with the locals)
-    std::swap(s->slots, slots);
-    s->cap = new_cap;
-    s->count = n_survive;
+    std::swap(s->table.tags, fresh.tags);                      // (the old table goes with the locals, and the insert's scratch)
+    std::swap(s->table.slots, fresh.slots);
+    s->table.cap = new_cap;
+    s->table.count = n_survive;
     std::vector<u8> fate(n_blobs);
     for (u64 i = 0; i < n_blobs; ++i) fate[order[i]] = cls[i];
     std::vector<ZsetBlob> kept;
@@ -646,16 +567,16 @@ int mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out) {
     struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffer above after it)
     HIPCHK(c, d_total.ensure(8));
     HIPCHK(c, hipMemsetAsync(d_total.p, 0, 8, st));
-    const u32 grid = (u32)std::min<u64>((s->cap + kPBlock - 1) / kPBlock, 2048);
-    hipLaunchKernelGGL(zprune_live_kernel, dim3(grid), dim3(kPBlock), 0, st, s->tags.as<u64>(), s->slots.as<u64>(), s->cap, d_total.as<u64>());
+    const u32 grid = (u32)std::min<u64>((s->table.cap + kPBlock - 1) / kPBlock, 2048);
+    hipLaunchKernelGGL(zprune_live_kernel, dim3(grid), dim3(kPBlock), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), s->table.cap, d_total.as<u64>());
     HIPCHK(c, hipMemcpyAsync(c->h_word.p, d_total.p, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     out->n_blobs = s->blobs.size();
     for (const ZsetBlob& b : s->blobs) out->resident_bytes += b.mem.bytes;
     out->live_bytes = c->h_word.as<u64>()[0];
-    out->table_slots = s->cap;
-    out->table_bytes = s->tags.bytes + s->slots.bytes;
+    out->table_slots = s->table.cap;
+    out->table_bytes = s->table.tags.bytes + s->table.slots.bytes;
     return MI_OK;
 }
 

@@ -3,15 +3,15 @@
 // set by decoding every recipe row straight to its place in the arena (mi_batch_add_zrecipes).  A chunk's stored form is a
 // pure function of its bytes, so moving stored spans gives byte for byte what mi_packset_pack + mi_pack_compress gives.
 //
-//   set       mi_restore.hip's table, restated for a slot that carries `stored`: tag = the digest's first 8 bytes (0 is stored
-//             as 1, 0 = empty), slot = {digest 32 | the stored span's ABSOLUTE device address 8 | length | stored << 32}.  Insert
-//             in probe-then-verify rounds across a kernel boundary; a digest met again is kept once (the first form wins); the
-//             same digest with another LENGTH makes the set unusable.  Rebuilt at twice the size when it passes half full;
+//   set       the pack sets' table (mi_slot_table.h) with a slot that carries `stored`: tag = the digest's first 8 bytes (0 is
+//             stored as 1, 0 = empty), slot = {digest 32 | the stored span's ABSOLUTE device address 8 | length | stored << 32}.
+//             Insert in probe-then-verify rounds across a kernel boundary; a digest met again is kept once (the first form
+//             wins); the same digest with another LENGTH makes the set unusable.  Rebuilt at twice the size when it passes half full;
 //   verify    MI_ZSET_VERIFY / MI_ZPACK_VERIFY: the blob decoded by mi_zpack.hip's decode kernel into a scratch laid out as a
 //             plain pack (mi_zpack_decode_plain), hashed by the ctx's launcher (pass kShaBlobs), held against the entries;
-//   cut       mi_fetch.hip's plan, restated: lookup (tag first, then all 32 bytes), first occurrences by the engine's dedup
+//   cut       mi_fetch.hip's plan: lookup (slot_table_find: tag first, then all 32 bytes), first occurrences by the engine's dedup
 //             marking, three launches of a scan over round16(stored) that carries the totals (entries, stored bytes, raw
-//             entries, chunk bytes), the entries' compaction, and zpack_gather_kernel's 16 KiB-tile gather from absolute
+//             entries, chunk bytes), the entries' compaction, and the 16 KiB-tile gather (mi_gather.h) from absolute
 //             16-byte-aligned sources, the bytes at and beyond `stored` zeroed in registers.  One synchronisation: the totals,
 //             before the blob is allocated.  Every offset is 64-bit;
 //   restore   zset_restore_kernel: ONE WAVE A RECIPE ROW (the workgroup is the wave, grid-stride, at most 65 536 waves).  A coded
@@ -27,8 +27,7 @@
 // every add (offset + round16(stored) <= blob_bytes, always, on the host) keeps a stored span inside its blob.  The cut READS
 // aligned 16-byte units inside [src, src + round16(stored)) and WRITES aligned units inside the new blob.  The hashing of a
 // verify pass reads up to 67 bytes behind the last string: a scratch's 256 bytes of slack, the arena's 4 KiB.
-#include "mi_internal.h"
-#include "mi_item_loads.h"
+#include "mi_gather.h"
 #include "mi_lz4_wave.h"
 #include "mi_zset_local.h"
 
@@ -44,123 +43,23 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kQNone = ~0ull;
-__host__ __device__ static inline u64 zset_round16(u64 v) { return (v + 15) & ~15ull; }
 
 constexpr int kQEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
-constexpr int kQSlotWords = 6;                                // digest 4 | device address | length, stored
 static_assert(sizeof(mi_zpack_entry) == 56 && kQEntryWords == 7, "mi_zpack_entry is seven 8-byte words");
 
-static __device__ __forceinline__ bool zset_digest_eq32(const u8* a, const u8* b) {
-    const u32x4 a0 = ((const u32x4*)a)[0], a1 = ((const u32x4*)a)[1];
-    const u32x4 b0 = ((const u32x4*)b)[0], b1 = ((const u32x4*)b)[1];
-    const u32x4 d0 = a0 ^ b0, d1 = a1 ^ b1;
-    return (d0.x | d0.y | d0.z | d0.w | d1.x | d1.y | d1.z | d1.w) == 0;
-}
-
-static __device__ __forceinline__ u64 zset_tag_of(u64 first8) { return first8 ? first8 : 1ull; }
-
-// ---- the set: entries -> table records, the table (mi_restore.hip's packset_* kernels, restated) ---------------------------
+// ---- the set: entries -> the table's records (the table itself: mi_slot_table.hip) -------------------------------------------
 __global__ __launch_bounds__(256)
 void zset_unpack_kernel(const u64* __restrict__ entries, u64 n, u64 base, u64* __restrict__ recs) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
     const u64* e = entries + kQEntryWords * k;
-    u64* r = recs + kQSlotWords * k;
+    u64* r = recs + kSlotWords * k;
     r[0] = e[0]; r[1] = e[1]; r[2] = e[2]; r[3] = e[3];
     r[4] = base + e[4];
     r[5] = e[6];
 }
 
-enum : u8 { kQRowDone = 0, kQRowVerify = 1, kQRowProbe = 2 };
-
-__global__ __launch_bounds__(256)
-void zset_begin_kernel(const u64* __restrict__ recs, u64 n, u64 mask, u8* __restrict__ row_state, u64* __restrict__ row_slot) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    row_state[i] = kQRowProbe;
-    row_slot[i] = zset_tag_of(recs[kQSlotWords * i]) & mask;
-}
-
-// walks from the row's slot comparing TAGS only: an empty slot is claimed and the record stored, a slot with an equal tag is
-// remembered for the verify kernel, anything else is walked past.  counters[0] += records stored, [3] += their stored bytes,
-// [4] += their lengths
-__global__ __launch_bounds__(256)
-void zset_probe_kernel(const u64* __restrict__ recs, u64 n, u64* __restrict__ tags, u64* __restrict__ slots, u64 mask,
-                       u8* __restrict__ row_state, u64* __restrict__ row_slot, u64* __restrict__ counters) {
-    __shared__ unsigned long long wg[3];
-    if (threadIdx.x < 3) wg[threadIdx.x] = 0;
-    __syncthreads();
-    u64 mine_new = 0, mine_stored = 0, mine_len = 0;
-    for (u64 i = (u64)blockIdx.x * 256 + threadIdx.x; i < n; i += (u64)gridDim.x * 256) {
-        if (row_state[i] != kQRowProbe) continue;
-        const u64* r = recs + kQSlotWords * i;
-        const u64 tag = zset_tag_of(r[0]);
-        u64 slot = row_slot[i];
-        for (;;) {
-            const u64 old = atomicCAS((unsigned long long*)&tags[slot], 0ull, (unsigned long long)tag);
-            if (old == 0ull) {                               // empty: mine now
-                u64* s = slots + kQSlotWords * slot;
-                s[0] = r[0]; s[1] = r[1]; s[2] = r[2]; s[3] = r[3]; s[4] = r[4]; s[5] = r[5];
-                row_state[i] = kQRowDone;
-                ++mine_new;
-                mine_stored += r[5] >> 32;
-                mine_len += r[5] & 0xFFFFFFFFull;
-                break;
-            }
-            if (old == tag) {                                // full compare after the kernel boundary
-                row_slot[i] = slot;
-                row_state[i] = kQRowVerify;
-                break;
-            }
-            slot = (slot + 1) & mask;
-        }
-    }
-    if (mine_new) {
-        atomicAdd(&wg[0], (unsigned long long)mine_new);
-        atomicAdd(&wg[1], (unsigned long long)mine_stored);
-        atomicAdd(&wg[2], (unsigned long long)mine_len);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0 && wg[0]) {
-        atomicAdd((unsigned long long*)&counters[0], wg[0]);
-        atomicAdd((unsigned long long*)&counters[3], wg[1]);
-        atomicAdd((unsigned long long*)&counters[4], wg[2]);
-    }
-}
-
-// equal digests: the chunk is held already (kept once, the first form wins) -- with another LENGTH: counters[2] = the smallest
-// such row.  Equal tags, different digests: the row goes on probing behind the slot (counters[1] += 1)
-__global__ __launch_bounds__(256)
-void zset_verify_kernel(const u64* __restrict__ recs, u64 n, const u64* __restrict__ slots, u64 mask, u8* __restrict__ row_state,
-                        u64* __restrict__ row_slot, u64* __restrict__ counters) {
-    const u64 i = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n || row_state[i] != kQRowVerify) return;
-    const u64 slot = row_slot[i];
-    const u64* r = recs + kQSlotWords * i;
-    const u64* s = slots + kQSlotWords * slot;
-    if (s[0] == r[0] && s[1] == r[1] && s[2] == r[2] && s[3] == r[3]) {
-        if ((u32)s[5] != (u32)r[5]) atomicMin((unsigned long long*)&counters[2], (unsigned long long)i);
-        row_state[i] = kQRowDone;
-    } else {
-        row_slot[i] = (slot + 1) & mask;
-        row_state[i] = kQRowProbe;
-        atomicAdd((unsigned long long*)&counters[1], 1ull);
-    }
-}
-
-// every occupied slot's record to out[0, limit); the cursor counts them all
-__global__ __launch_bounds__(256)
-void zset_export_kernel(const u64* __restrict__ tags, const u64* __restrict__ slots, u64 cap, u64* __restrict__ out, u64 limit,
-                        u64* __restrict__ cursor) {
-    const u64 s = (u64)blockIdx.x * 256 + threadIdx.x;
-    if (s >= cap || tags[s] == 0ull) return;
-    const u64 at = atomicAdd((unsigned long long*)cursor, 1ull);
-    if (at >= limit) return;
-#pragma unroll
-    for (int w = 0; w < kQSlotWords; ++w) out[kQSlotWords * at + w] = slots[kQSlotWords * s + w];
-}
-
-// ---- resolve (mi_fetch.hip's fetch_lookup_kernel, restated) ---------------------------------------------------------------
+// ---- resolve (as mi_fetch.hip's fetch_lookup_kernel does) ----------------------------------------------------------------------
 // src[r], word[r]: where the set holds row r's stored span and its length | stored << 32 (0, 0: it does not hold the digest);
 // len64[r]: the SET'S length.  A bad row: a digest the set lacks; with lengths, a stated length of 0 or another one than the set's
 __global__ __launch_bounds__(256)
@@ -170,18 +69,11 @@ void zset_lookup_kernel(const u8* __restrict__ digests, const u32* __restrict__ 
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
     const u8* d = digests + 32 * r;
-    const u64 tag = zset_tag_of(*(const u64*)d);
     u64 at = 0, w = 0;
-    u64 slot = tag & mask;
-    for (u64 walked = 0; walked <= mask; ++walked) {         // (the table is under half full: an empty slot ends every walk)
-        const u64 t = tags[slot];
-        if (t == 0ull) break;
-        if (t == tag && zset_digest_eq32((const u8*)(slots + kQSlotWords * slot), d)) {
-            at = slots[kQSlotWords * slot + 4];
-            w = slots[kQSlotWords * slot + 5];
-            break;
-        }
-        slot = (slot + 1) & mask;
+    const u64 slot = slot_table_find(tags, slots, mask, d);
+    if (slot != kSlotNone) {
+        at = slots[kSlotWords * slot + 4];
+        w = slots[kSlotWords * slot + 5];
     }
     src[r] = at;
     word[r] = w;
@@ -200,38 +92,6 @@ constexpr int kQPer   = 8;                            // rows per thread
 constexpr int kQTile  = kQBlock * kQPer;              // 2048 rows per block
 enum : int { kQTotEntries = 0, kQTotBlob = 1, kQTotStored = 2, kQTotRaw = 3, kQTotChunk = 4, kQTotBad = 6, kQTotDiffer = 7 };
 
-static __device__ __forceinline__ u64 zset_exclusive_scan(u64 v, u64* total, u64* lds /*>=4*/) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    u64 x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const u32 lo = __shfl_up((u32)x, d), hi = __shfl_up((u32)(x >> 32), d);
-        const u64 y = ((u64)hi << 32) | lo;
-        if (lane >= d) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    u64 wave_off = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < kQBlock / 64; ++w) {
-        const u64 s = lds[w];
-        if (w < wave) wave_off += s;
-        tot += s;
-    }
-    __syncthreads();
-    *total = tot;
-    return wave_off + x - v;
-}
-
-static __device__ __forceinline__ u64 zset_wave_sum(u64 v) {
-#pragma unroll
-    for (int d = 32; d; d >>= 1) {
-        const u32 lo = __shfl_xor((u32)v, d), hi = __shfl_xor((u32)(v >> 32), d);
-        v += ((u64)hi << 32) | lo;
-    }
-    return v;
-}
-
 // per block of kQTile rows: the first occurrences and their rounded-up stored bytes; into the totals: stored bytes, raw
 // entries, chunk bytes
 __global__ __launch_bounds__(kQBlock)
@@ -248,14 +108,14 @@ void zset_block_sums_kernel(const i64* __restrict__ dup_of, const u64* __restric
         const u64 w = word[row];
         const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
         ++v[0];
-        v[1] += zset_round16(stored);
+        v[1] += round16(stored);
         v[2] += stored;
         v[3] += stored == len ? 1 : 0;
         v[4] += len;
     }
 #pragma unroll
     for (int q = 0; q < 5; ++q) {
-        v[q] = zset_wave_sum(v[q]);
+        v[q] = wave_sum(v[q]);
         if (lane == 0) lds[q][wave] = v[q];
     }
     __syncthreads();
@@ -284,8 +144,8 @@ void zset_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ bl
         const u64 i = b0 + threadIdx.x;
         const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
         u64 tc, tb;
-        const u64 ec = zset_exclusive_scan(vc, &tc, lds);
-        const u64 eb = zset_exclusive_scan(vb, &tb, lds);
+        const u64 ec = block_exclusive_scan_u64<kQBlock>(vc, &tc, lds);
+        const u64 eb = block_exclusive_scan_u64<kQBlock>(vb, &tb, lds);
         if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
         carry_c += tc;
         carry_b += tb;
@@ -309,11 +169,11 @@ void zset_compact_entries_kernel(const i64* __restrict__ dup_of, const u64* __re
     for (int k = 0; k < kQPer; ++k) {
         const bool s = base + k < n && dup_of[base + k] < 0;
         w[k] = s ? word[base + k] : 0;
-        if (s) { sel |= 1u << k; ++cnt; bytes += zset_round16(w[k] >> 32); }
+        if (s) { sel |= 1u << k; ++cnt; bytes += round16(w[k] >> 32); }
     }
     u64 t;
-    u64 at = zset_exclusive_scan(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = zset_exclusive_scan(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = block_exclusive_scan_u64<kQBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
+    u64 dst = block_exclusive_scan_u64<kQBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
 #pragma unroll
     for (int k = 0; k < kQPer; ++k) {
         if (!(sel & (1u << k))) continue;
@@ -329,115 +189,16 @@ void zset_compact_entries_kernel(const i64* __restrict__ dup_of, const u64* __re
         r[5] = row;
         r[6] = w[k];
         ++at;
-        dst += zset_round16(stored);
+        dst += round16(stored);
     }
 }
 
-// ---- gather: zpack_gather_kernel, restated ------------------------------------------------------------------------------------
-constexpr int kQWG = 256;
-constexpr u32 kQGatherTile = 16384;                   // bytes of the blob a workgroup writes
-constexpr u32 kQUnits = kQGatherTile / 16;            // ... in 16-byte units: an entry takes at least one, so at most as many entries
-constexpr int kQUnitsPer = kQUnits / kQWG;            // units per lane
+// ---- gather: mi_gather.h's tile body over aligned sources -----------------------------------------------------------------------
 
-// the largest k in [0, n) with a[k] <= x (a ascending, a[0] <= x), by one wave: 64 probes a round (mi_pack.hip's scheme)
-static __device__ __forceinline__ u64 zset_wave_last_le(const u64* __restrict__ a, u64 n, u64 x, int lane) {
-    u64 lo = 0, hi = n;
-    while (hi - lo > 1) {
-        const u64 step = (hi - lo + 63) >> 6;
-        const u64 p = lo + (u64)lane * step;
-        const bool ok = p < hi && a[p] <= x;
-        const u64 c = (u64)__popcll(__ballot(ok));   // the probes that hold are a prefix of the lanes; lane 0 probes lo: c >= 1
-        hi = lo + c * step < hi ? lo + c * step : hi;
-        lo = lo + (c - 1) * step;
-    }
-    return lo;
-}
-
-// an ALIGNED 16-byte load from an absolute device address (the address space is said here: a generic pointer would make it flat)
-static __device__ __forceinline__ u32x4 zset_load16(u64 addr) {
-    typedef const u32x4 __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
-
-// a 16-byte load at ANY alignment from an absolute device address (mi_restore.hip's load16_global)
-static __device__ __forceinline__ u32x4 zset_load16_unaligned(u64 addr) {
-    typedef const u32x4_unaligned __attribute__((address_space(1))) * global_ptr;
-    return *(global_ptr)addr;
-}
-
-// the first `valid` (< 16) bytes of a unit, the rest zero
-static __device__ __forceinline__ u32x4 zset_keep(u32x4 v, u32 valid) {
-    u32 w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        const u32 have = valid > 4u * q ? valid - 4u * q : 0u;
-        w[q] = have >= 4 ? w[q] : have ? (w[q] & ((1u << (8 * have)) - 1u)) : 0u;
-    }
-    return u32x4{w[0], w[1], w[2], w[3]};
-}
-
-__global__ __launch_bounds__(kQWG)
+__global__ __launch_bounds__(kGatherWG)
 void zset_gather_kernel(const u64* __restrict__ e_src, const u64* __restrict__ e_len, const u64* __restrict__ e_dst, u64 n_entries,
                         u64 blob_bytes, u8* __restrict__ blob) {
-    __shared__ u64 s_src[kQUnits];
-    __shared__ u32 s_rel[kQUnits];                   // where the entry begins in the tile
-    __shared__ u32 s_len[kQUnits];
-    __shared__ u64 s_k[2];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 tile0 = (u64)blockIdx.x * kQGatherTile;
-    const u64 tile1 = tile0 + kQGatherTile < blob_bytes ? tile0 + kQGatherTile : blob_bytes;
-    if (wave < 2) {
-        const u64 k = zset_wave_last_le(e_dst, n_entries, wave == 0 ? tile0 : tile1 - 16, lane);
-        if (lane == 0) s_k[wave] = k;
-    }
-    __syncthreads();
-    const u64 k0 = s_k[0];
-    const u64 reach = s_k[1] - k0 + 1;
-    const u32 cnt = reach < kQUnits ? (u32)reach : kQUnits;
-    for (u32 i = threadIdx.x; i < cnt; i += kQWG) {
-        u64 src = e_src[k0 + i], len = e_len[k0 + i];
-        const u64 dst = e_dst[k0 + i];
-        u32 rel = (u32)(dst - tile0);
-        if (dst < tile0) {                           // the first entry may begin in front of the tile: the tile sees what is left
-            const u64 skip = tile0 - dst;            // of it -- skip is a multiple of 16 below its length
-            src += skip;
-            len -= skip;
-            rel = 0;
-        }
-        s_src[i] = src;
-        s_len[i] = (u32)len;
-        s_rel[i] = rel;
-    }
-    __syncthreads();
-    u64 src[kQUnitsPer];
-    u32 valid[kQUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kQUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kQWG) * 16;
-        src[j] = s_src[0];                            // a unit behind the blob's end (the last tile) loads the tile's first unit and
-        valid[j] = 0;                                 // drops it: a lane's four loads are in flight together
-        if (tile0 + r >= tile1) continue;
-        u32 lo = 0, hi = cnt;                         // the entry this unit lies in: the last that begins at or before it
-        while (hi - lo > 1) {
-            const u32 mid = (lo + hi) >> 1;
-            if (s_rel[mid] <= r) lo = mid; else hi = mid;
-        }
-        const u32 o = r - s_rel[lo], len = s_len[lo];
-        if (o < len) {                                // (always, for entries of at least one byte)
-            src[j] = s_src[lo] + o;                   // a multiple of 16 behind an aligned address
-            valid[j] = len - o;
-        }
-    }
-    u32x4 v[kQUnitsPer];
-#pragma unroll
-    for (int j = 0; j < kQUnitsPer; ++j) v[j] = zset_load16(src[j]);
-#pragma unroll
-    for (int j = 0; j < kQUnitsPer; ++j) {
-        const u32 r = ((u32)threadIdx.x + (u32)j * kQWG) * 16;
-        if (tile0 + r >= tile1) continue;
-        if (valid[j] < 16) v[j] = zset_keep(v[j], valid[j]);   // the entry's last unit: zero at and beyond its stored bytes
-        *(u32x4*)(blob + tile0 + r) = v[j];
-    }
+    gather_tile<true>(e_src, e_len, e_dst, n_entries, blob_bytes, blob);
 }
 
 // ---- the fused restore: one wave a recipe row, decoded (or copied) straight to its place in the arena -----------------------
@@ -462,12 +223,12 @@ void zset_restore_kernel(u8* arena, const u64* __restrict__ r_dst, const u64* __
             const u64 units = (len - head) >> 4;
             const u64 tail = head + (units << 4);
             if ((u64)lane < head) dst[lane] = src[lane];
-            for (u64 u = lane; u < units; u += 64) *(u32x4*)(dst + head + (u << 4)) = zset_load16_unaligned(s_addr + head + (u << 4));
+            for (u64 u = lane; u < units; u += 64) *(u32x4*)(dst + head + (u << 4)) = load16_global_unaligned(s_addr + head + (u << 4));
             if (tail + lane < len) dst[tail + lane] = src[tail + lane];
         } else {
             rule = z_decode_block(src, stored, dst, len, lane);
         }
-        const bool pad_set = stored + lane < zset_round16(stored) && src[stored + lane] != 0;
+        const bool pad_set = stored + lane < round16(stored) && src[stored + lane] != 0;
         if (__ballot(pad_set) != 0 && rule == 0) rule = mi_host::kLz4PadNotZero;
         if (lane == 0) {
             rule_out[k] = rule;
@@ -526,83 +287,6 @@ int set_state(const mi_zset* s, const char* who) {
     return fail(s->ctx, MI_ERR_STATE, "%s: the compressed pack set is unusable since: %s", who, s->broken.c_str());
 }
 
-int table_alloc(mi_ctx* c, DevBuf* tags, DevBuf* slots, u64 cap) {
-    HIPCHK(c, tags->ensure(cap * 8));
-    HIPCHK(c, slots->ensure(cap * kQSlotWords * 8));
-    HIPCHK(c, hipMemsetAsync(tags->p, 0, cap * 8, c->stream));
-    return MI_OK;
-}
-
-// n records (device) into the table (tags, slots, cap): sums[0] of them were not held, with sums[1] stored bytes and sums[2]
-// chunk bytes; *conflict = the smallest row whose digest is held with another length (kQNone: none)
-int table_insert(mi_zset* s, u64* tags, u64* slots, u64 cap, const u64* d_recs, u64 n, u64 sums[3], u64* conflict) {
-    mi_ctx* c = s->ctx;
-    sums[0] = sums[1] = sums[2] = 0;
-    *conflict = kQNone;
-    if (n == 0) return MI_OK;
-    HIPCHK(c, s->row_state.ensure(n + 16));
-    HIPCHK(c, s->row_slot.ensure(n * 8 + 16));
-    HIPCHK(c, s->counter.ensure(64));
-    u64* d_cnt = s->counter.as<u64>();                  // [0] stored, [1] rows to probe again, [2] smallest conflicting row, [3] [4] bytes
-    HIPCHK(c, hipMemsetAsync(d_cnt, 0, 40, c->stream));
-    HIPCHK(c, hipMemsetAsync(d_cnt + 2, 0xFF, 8, c->stream));
-    const u32 per_row = (u32)((n + 255) / 256);
-    const u32 grid = per_row < 2048u ? per_row : 2048u;
-    hipLaunchKernelGGL(zset_begin_kernel, dim3(per_row), dim3(256), 0, c->stream, d_recs, n, cap - 1, s->row_state.as<u8>(),
-                       s->row_slot.as<u64>());
-    u64* h = c->h_word.as<u64>();
-    for (u64 round = 0;; ++round) {
-        hipLaunchKernelGGL(zset_probe_kernel, dim3(grid), dim3(256), 0, c->stream, d_recs, n, tags, slots, cap - 1, s->row_state.as<u8>(),
-                           s->row_slot.as<u64>(), d_cnt);
-        hipLaunchKernelGGL(zset_verify_kernel, dim3(per_row), dim3(256), 0, c->stream, d_recs, n, slots, cap - 1, s->row_state.as<u8>(),
-                           s->row_slot.as<u64>(), d_cnt);
-        HIPCHK(c, hipMemcpyAsync(h, d_cnt, 40, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipGetLastError());
-        sums[0] = h[0];
-        sums[1] = h[3];
-        sums[2] = h[4];
-        *conflict = h[2];
-        if (h[1] == 0) return MI_OK;                                      // no 64-bit tag collisions (the normal case)
-        if (round >= cap) return fail(c, MI_ERR_HIP, "compressed pack set: probing does not converge");
-        HIPCHK(c, hipMemsetAsync(d_cnt + 1, 0, 8, c->stream));
-    }
-}
-
-// room for n_more digests under half full.  The new table is complete before the old one goes: a failure leaves the set as it was
-int table_make_room(mi_zset* s, u64 n_more) {
-    mi_ctx* c = s->ctx;
-    const u64 need = (s->count + n_more) * 2;
-    if (need <= s->cap) return MI_OK;
-    u64 cap = s->cap ? s->cap : 1024;
-    while (cap < need) cap <<= 1;
-    DevBuf tags, slots, old;
-    int rc = table_alloc(c, &tags, &slots, cap);
-    if (rc) return rc;
-    if (s->count) {
-        HIPCHK(c, old.ensure(s->count * kQSlotWords * 8));
-        HIPCHK(c, s->counter.ensure(64));
-        HIPCHK(c, hipMemsetAsync(s->counter.p, 0, 8, c->stream));
-        hipLaunchKernelGGL(zset_export_kernel, dim3((u32)((s->cap + 255) / 256)), dim3(256), 0, c->stream, s->tags.as<u64>(),
-                           s->slots.as<u64>(), s->cap, old.as<u64>(), s->count, s->counter.as<u64>());
-        HIPCHK(c, hipMemcpyAsync(c->h_word.p, s->counter.p, 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        const u64 have = c->h_word.as<u64>()[0];
-        if (have != s->count)
-            return fail(c, MI_ERR_STATE, "compressed pack set holds %llu digests, counted %llu", (unsigned long long)have, (unsigned long long)s->count);
-        u64 sums[3], conflict = kQNone;
-        rc = table_insert(s, tags.as<u64>(), slots.as<u64>(), cap, old.as<u64>(), s->count, sums, &conflict);
-        if (rc) return rc;
-        if (sums[0] != s->count)
-            return fail(c, MI_ERR_HIP, "compressed pack set rebuild lost entries (%llu of %llu)", (unsigned long long)sums[0], (unsigned long long)s->count);
-    }
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    s->tags = std::move(tags);                          // (DevBuf's move swaps: the old table goes with the locals)
-    s->slots = std::move(slots);
-    s->cap = cap;
-    return MI_OK;
-}
-
 // MI_ZSET_VERIFY / MI_ZPACK_VERIFY: a compressed blob on the device, its entries on the host (structurally sound) and on the
 // device (d_rows: what the digests are held against), n > 0.  Decoded into a scratch laid out as a plain pack, hashed there.
 // *bad = the smallest entry that does not decode (then *rule says why) or, if all decode, that does not hash (*rule = 0);
@@ -651,7 +335,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
         return MI_OK;
     }
     HIPCHK(c, d_ent.ensure(n * sizeof(mi_zpack_entry)));
-    HIPCHK(c, d_recs.ensure(n * kQSlotWords * 8));
+    HIPCHK(c, d_recs.ensure(n * kSlotWords * 8));
     HIPCHK(c, hipMemcpyAsync(d_ent.p, entries, n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(zset_unpack_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_ent.as<u64>(), n, (u64)(size_t)mine.p,
                        d_recs.as<u64>());
@@ -673,12 +357,12 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
         }
     }
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = table_make_room(s, n);
+    int rc = s->table.make_room(c, n, "compressed pack set");
     if (rc) return rc;
     u64 sums[3], conflict = kQNone;
-    rc = table_insert(s, s->tags.as<u64>(), s->slots.as<u64>(), s->cap, d_recs.as<u64>(), n, sums, &conflict);
-    s->count += sums[0];
-    s->info.n_digests = s->count;
+    rc = s->table.insert(c, d_recs.as<u64>(), n, sums, &conflict, "compressed pack set");
+    s->table.count += sums[0];
+    s->info.n_digests = s->table.count;
     s->info.stored_bytes += sums[1];
     s->info.chunk_bytes += sums[2];
     s->blobs.push_back(ZsetBlob{std::move(mine), blob_bytes});   // the table may point into it by now
@@ -694,7 +378,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
     s->info.ms_insert = ms_since(t0);
     ++s->info.n_packs;
     s->info.n_entries += n;
-    for (u64 k = 0; k < n; ++k) s->info.blob_bytes += zset_round16(entries[k].stored);
+    for (u64 k = 0; k < n; ++k) s->info.blob_bytes += round16(entries[k].stored);
     return MI_OK;
 }
 
@@ -713,10 +397,10 @@ int mi_zset_create(mi_ctx* c, uint64_t entries_hint, mi_zset** out) {
     s->info.alg = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? MI_DIGEST_BLAKE2S : MI_DIGEST_SHA256;
     u64 cap = 1024;
     while (cap < entries_hint * 2) cap <<= 1;
-    int rc = table_alloc(c, &s->tags, &s->slots, cap);
+    s->table.sum_bytes = true;                          // (mi_zset_info's stored_bytes and chunk_bytes)
+    int rc = s->table.alloc(c, cap);
     if (rc == MI_OK && hipStreamSynchronize(c->stream) != hipSuccess) rc = fail(c, MI_ERR_HIP, "mi_zset_create: the table's memset failed");
     if (rc) { mi_zset_free(s); return rc; }
-    s->cap = cap;
     *out = s;
     return MI_OK;
 }
@@ -787,17 +471,9 @@ int mi_zset_ctx(const mi_zset* s, const char* who, mi_ctx** ctx) {
 int mi_zset_lookup_enqueue(const mi_zset* s, const uint8_t* d_digests, const uint32_t* d_lengths, uint64_t n, uint64_t* d_src, uint64_t* d_word,
                            uint64_t* d_len64, uint64_t* d_first_bad) {
     if (!s || !d_digests || !n || !d_src || !d_word || !d_len64 || !d_first_bad) return MI_ERR_INVALID;
-    hipLaunchKernelGGL(zset_lookup_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s->ctx->stream, d_digests, d_lengths, n, s->tags.as<u64>(),
-                       s->slots.as<u64>(), s->cap - 1, d_src, d_word, d_len64, d_first_bad);
+    hipLaunchKernelGGL(zset_lookup_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s->ctx->stream, d_digests, d_lengths, n,
+                       s->table.tags.as<u64>(), s->table.slots.as<u64>(), s->table.cap - 1, d_src, d_word, d_len64, d_first_bad);
     return MI_OK;
-}
-
-// (hidden: mi_local.h) for mi_zprune.hip: the table's helpers above, as they are
-int mi_zset_table_alloc(mi_ctx* c, mi::DevBuf* tags, mi::DevBuf* slots, uint64_t cap) { return table_alloc(c, tags, slots, cap); }
-
-int mi_zset_table_insert(mi_zset* s, uint64_t* tags, uint64_t* slots, uint64_t cap, const uint64_t* d_recs, uint64_t n, uint64_t sums[3],
-                         uint64_t* conflict) {
-    return table_insert(s, tags, slots, cap, d_recs, n, sums, conflict);
 }
 
 int mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint32_t* stored, uint64_t cap, uint64_t* n) {
@@ -806,29 +482,28 @@ int mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint3
     mi_ctx* c = s->ctx;
     const int rc = set_state(s, who);
     if (rc) return rc;
-    *n = s->count;
-    if (cap == 0 || s->count == 0) return MI_OK;                       // the sizing call; a set of nothing
-    if (cap < s->count)
-        return fail(c, MI_ERR_INVALID, "%s: room for %llu entries, the set holds %llu", who, (unsigned long long)cap, (unsigned long long)s->count);
+    *n = s->table.count;
+    if (cap == 0 || s->table.count == 0) return MI_OK;                       // the sizing call; a set of nothing
+    if (cap < s->table.count)
+        return fail(c, MI_ERR_INVALID, "%s: room for %llu entries, the set holds %llu", who, (unsigned long long)cap, (unsigned long long)s->table.count);
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf d_recs, d_cursor;
     struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
-    std::vector<u64> recs(s->count * kQSlotWords);
-    HIPCHK(c, d_recs.ensure(s->count * kQSlotWords * 8));
+    std::vector<u64> recs(s->table.count * kSlotWords);
+    HIPCHK(c, d_recs.ensure(s->table.count * kSlotWords * 8));
     HIPCHK(c, d_cursor.ensure(8));
     HIPCHK(c, hipMemsetAsync(d_cursor.p, 0, 8, st));
-    hipLaunchKernelGGL(zset_export_kernel, dim3((u32)((s->cap + 255) / 256)), dim3(256), 0, st, s->tags.as<u64>(), s->slots.as<u64>(), s->cap,
-                       d_recs.as<u64>(), s->count, d_cursor.as<u64>());
+    s->table.export_records(c, d_recs.as<u64>(), s->table.count, d_cursor.as<u64>());
     HIPCHK(c, hipMemcpyAsync(c->h_word.p, d_cursor.p, 8, hipMemcpyDeviceToHost, st));
-    HIPCHK(c, hipMemcpyAsync(recs.data(), d_recs.p, s->count * kQSlotWords * 8, hipMemcpyDeviceToHost, st));
+    HIPCHK(c, hipMemcpyAsync(recs.data(), d_recs.p, s->table.count * kSlotWords * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     const u64 have = c->h_word.as<u64>()[0];
-    if (have != s->count)
-        return fail(c, MI_ERR_STATE, "%s: the set holds %llu digests, counted %llu", who, (unsigned long long)have, (unsigned long long)s->count);
-    for (u64 k = 0; k < s->count; ++k) {
-        const u64* r = recs.data() + kQSlotWords * k;
+    if (have != s->table.count)
+        return fail(c, MI_ERR_STATE, "%s: the set holds %llu digests, counted %llu", who, (unsigned long long)have, (unsigned long long)s->table.count);
+    for (u64 k = 0; k < s->table.count; ++k) {
+        const u64* r = recs.data() + kSlotWords * k;
         if (digests) memcpy(digests + 32 * k, r, 32);
         if (lengths) lengths[k] = (u32)r[5];
         if (stored) stored[k] = (u32)(r[5] >> 32);
@@ -904,7 +579,7 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
     HIPCHK(c, hipMemsetAsync(totals, 0, 6 * 8, s));
     HIPCHK(c, hipMemsetAsync(totals + kQTotBad, 0xFF, 2 * 8, s));
     hipLaunchKernelGGL(zset_lookup_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, s, d_dig.as<u8>(),
-                       lengths ? d_len32.as<u32>() : (const u32*)nullptr, n, set->tags.as<u64>(), set->slots.as<u64>(), set->cap - 1,
+                       lengths ? d_len32.as<u32>() : (const u32*)nullptr, n, set->table.tags.as<u64>(), set->table.slots.as<u64>(), set->table.cap - 1,
                        d_src.as<u64>(), d_word.as<u64>(), d_len64.as<u64>(), totals + kQTotBad);
     launch_dedup_mark(d_dig.as<u8>(), n, nullptr, c->dd_table.as<u32>(), c->dd_slot.as<u32>(), dd_cap, d_dup.as<i64>(), c->dd_nuniq.as<u64>(),
                       true, s);
@@ -933,7 +608,7 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
     if (n_sel == 0 || n_sel > n || blob_bytes < 16 * n_sel || stored_bytes > chunk_bytes || stored_bytes > blob_bytes)
         return fail(c, MI_ERR_HIP, "%s: the plan counted %llu entries with %llu stored bytes in a blob of %llu for %llu chunk bytes", who,
                     (unsigned long long)n_sel, (unsigned long long)stored_bytes, (unsigned long long)blob_bytes, (unsigned long long)chunk_bytes);
-    const u64 n_tiles = (blob_bytes + kQGatherTile - 1) / kQGatherTile;
+    const u64 n_tiles = (blob_bytes + kGatherTile - 1) / kGatherTile;
     if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
     rc = mi_zpack_alloc(c, who, n_sel, blob_bytes, &mine.z, &d_blob, &h_rows);      // does not fit: MI_ERR_NOMEM, nothing has changed
     if (rc) return rc;
@@ -944,7 +619,7 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
     HIPCHK(c, hipEventRecord(ev[2], s));
     hipLaunchKernelGGL(zset_compact_entries_kernel, dim3((u32)nb), dim3(kQBlock), 0, s, d_dup.as<i64>(), d_src.as<u64>(), d_word.as<u64>(),
                        d_dig.as<u8>(), n, block_cnt, block_bytes, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), d_rows.as<u64>());
-    hipLaunchKernelGGL(zset_gather_kernel, dim3((u32)n_tiles), dim3(kQWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel,
+    hipLaunchKernelGGL(zset_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel,
                        blob_bytes, (u8*)d_blob);
     HIPCHK(c, hipEventRecord(ev[3], s));
     // the entries to the host with the same synchronisation: mi_zpack_entries only reads from then on
@@ -1054,7 +729,7 @@ int mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, con
         HIPCHK(c, hipMemsetAsync(cell, 0xFF, 16, s));
         const u32 row_blocks = (u32)((n_rows + 255) / 256);
         hipLaunchKernelGGL(zset_lookup_kernel, dim3(row_blocks), dim3(256), 0, s, d_dig.as<u8>(), d_len32.as<u32>(), n_rows,
-                           set->tags.as<u64>(), set->slots.as<u64>(), set->cap - 1, d_src.as<u64>(), d_word.as<u64>(), d_len64.as<u64>(), cell);
+                           set->table.tags.as<u64>(), set->table.slots.as<u64>(), set->table.cap - 1, d_src.as<u64>(), d_word.as<u64>(), d_len64.as<u64>(), cell);
         HIPCHK(c, hipMemcpyAsync(h, cell, 8, hipMemcpyDeviceToHost, s));
         HIPCHK(c, hipEventRecord(ev[1], s));
         HIPCHK(c, hipStreamSynchronize(s));
@@ -1091,7 +766,7 @@ int mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, con
         if (flags & MI_RECIPE_VERIFY) {
             const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
             hash_items(kShaBlobs, b->arena.as<u8>(), d_dst.as<u64>(), d_len64.as<u64>(), nullptr, (u32)n_rows, nullptr, c->heads.as<u32>(),
-                       nullptr, true, d_got.as<u8>(), c->sha, c->prop.multiProcessorCount, zset_round16(end), s);
+                       nullptr, true, d_got.as<u8>(), c->sha, c->prop.multiProcessorCount, round16(end), s);
             hipLaunchKernelGGL(zset_compare_kernel, dim3(row_blocks), dim3(256), 0, s, d_got.as<u8>(), d_dig.as<u64>(), 4u, n_rows, cell + 1);
         }
         HIPCHK(c, hipEventRecord(ev[3], s));

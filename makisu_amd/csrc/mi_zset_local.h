@@ -1,8 +1,8 @@
 // mi_zset_local.h -- what a compressed pack set IS, for the two translation units that work on one: mi_zset.hip (create, add,
 // cut, restore) and mi_zprune.hip (prune in place, usage).  Host types only: no kernel lives here, and mi_zset.hip's device
-// code does not depend on it.  The table's helpers of mi_zset.hip that mi_zprune.hip reuses are declared in mi_local.h.
+// code does not depend on it.  The table both work on is a mi::SlotTable (mi_slot_table.h).
 #pragma once
-#include "mi_internal.h"
+#include "mi_slot_table.h"
 
 #include <string.h>
 
@@ -68,10 +68,7 @@ struct mi_zset {
     mi_ctx* ctx = nullptr;
     mi_zset_info info = {};
     std::vector<mi::ZsetBlob> blobs;             // every blob that is resident: the table points into them
-    mi::DevBuf tags, slots;                      // the table: cap tags, cap slots of kQSlotWords words
-    mi::DevBuf counter, row_state, row_slot;
-    mi::u64 cap = 0;                             // slots, a power of two
-    mi::u64 count = 0;                           // distinct digests held
+    mi::SlotTable table;                         // digest -> the stored span's device address, length | stored << 32 (mi_slot_table.h)
     std::string broken;                          // sticky: the first message of an add that left the table in doubt
     mi::ZsetUploader up;
 };

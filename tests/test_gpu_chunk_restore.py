@@ -345,6 +345,41 @@ def test_what_is_refused_leaves_batch_and_set_as_they_were():
             s.info
 
 
+# ---- 6b. the table itself: a conflict inside one add, growth through export and re-insert -----------------------------------------
+def test_one_digest_with_two_lengths_in_one_add_is_a_conflict():
+    """Two entries of 16 and 17 bytes under one digest, into a fresh set, verify off (digests are opaque).  Both rows probe in
+    one launch: one claims the slot, the other meets its own tag there and is the conflict the verify kernel reports -- which of
+    the two compare-and-swaps comes first is the hardware's, so the row named is either, with its own length."""
+    entries, blob = pc.model_pack([(0, 0, 16), (0, 16, 17)], [bytes(range(33))])
+    entries = entries.copy()
+    entries["digest"][1] = entries["digest"][0]
+    with M.Engine() as e, e.packset() as s:
+        err = _raises(-1, lambda: s.add_blob(blob, entries), "another length", "unusable from here on")
+        assert err.first_bad in (0, 1) and "entry %d (%d bytes)" % (err.first_bad, 16 + err.first_bad) in str(err), str(err)
+        _raises(-6, lambda: s.add_blob(blob, entries), "unusable since", "another length")
+        with pytest.raises(M.MiError):
+            s.info
+
+
+def test_a_set_grows_through_export_and_re_insert():
+    """A fresh set has 1 024 slots and stays under half full: 513 entries grow it empty, 513 more grow it through the export of
+    what it holds and their re-insert.  Every digest is found afterwards, by the want list and by a restore."""
+    data = np.random.default_rng(48).integers(0, 256, 1026 * 16, dtype=np.uint8).tobytes()
+    halves = [pc.model_pack([(0, 16 * i, 16) for i in range(k, k + 513)], [data]) for k in (0, 513)]
+    dig = np.ascontiguousarray(np.concatenate([en["digest"] for en, _ in halves]))
+    assert len({bytes(d) for d in dig}) == 1026
+    with M.Engine() as e, e.packset() as s, e.batch() as b:
+        for en, bl in halves:
+            s.add_blob(bl, en)
+        assert (s.info.n_digests, s.info.n_entries, s.info.n_packs) == (1026, 1026, 2)
+        held, want, info = s.missing(dig)
+        assert held.all() and len(want) == 0 and info.n_want == 0
+        pick = [0, 512, 1025]                                    # the first, the 513th and the last
+        b.add_recipes(s, [(dig[pick], np.full(3, 16, dtype=np.uint32))], verify=True)
+        b.run()
+        assert b.read_file(0, 0, 48) == b"".join(data[16 * k:16 * k + 16] for k in pick)
+
+
 # ---- 7. the flags are what catches damage -----------------------------------------------------------------------------------
 def test_only_the_flags_catch_a_damaged_blob():
     rng = np.random.default_rng(48)

@@ -395,6 +395,54 @@ def test_what_is_refused_leaves_set_and_batch_as_they_were(planted):
         keep.close()
 
 
+# ---- 7b. the table itself: a conflict inside one add, two stored forms of one chunk, growth through export and re-insert -------------
+def test_one_digest_with_two_lengths_in_one_add_is_a_conflict_and_with_two_stored_forms_is_not():
+    """Two entries of 16 and 17 bytes under one digest, into a fresh set, verify off (digests are opaque).  Both rows probe in
+    one launch: one claims the slot, the other meets its own tag there and is the conflict the verify kernel reports -- which of
+    the two compare-and-swaps comes first is the hardware's, so the row named is either, with its own length.  One digest and
+    one length stored raw and then coded is no conflict: the set keeps the form it had."""
+    _, _, ze, zb = qc.zpack_of([bytes(range(16)), bytes(range(17))])
+    ze = ze.copy()
+    ze["digest"][1] = ze["digest"][0]
+    twice = bytes([9]) * 40
+    coded = zc.compress_chunk(twice)
+    assert len(coded) < 40
+    raw_form, coded_form = zc.build_zpack([zc._entry(twice, 40, twice)]), zc.build_zpack([zc._entry(coded, 40, twice)])
+    with M.Engine() as e:
+        with e.zset() as zs:
+            err = _raises(-1, lambda: zs.add_zblob(zb, ze), "another length", "unusable from here on")
+            assert err.first_bad in (0, 1) and "entry %d (%d bytes)" % (err.first_bad, 16 + err.first_bad) in str(err), str(err)
+            _raises(-6, lambda: zs.info, "unusable since", "another length")
+        with e.zset() as zs, e.batch() as b:
+            for en, bl in (raw_form, coded_form):
+                zs.add_zblob(bl, en)
+            d, ln, st = zs.entries()
+            assert (len(d), int(ln[0]), int(st[0])) == (1, 40, 40) and zs.info.n_packs == 2
+            b.add_zrecipes(zs, [qc.recipe([twice], [0])], verify=True)
+            b.run()
+            assert b.read_file(0, 0, 40) == twice
+
+
+def test_a_zset_grows_through_export_and_re_insert():
+    """A fresh set has 1 024 slots and stays under half full: 513 entries grow it empty, 513 more grow it through the export of
+    what it holds and their re-insert.  Every digest is found afterwards, by the want list and by a restore."""
+    data = np.random.default_rng(110).integers(0, 256, 1026 * 16, dtype=np.uint8).tobytes()
+    chunks = [data[16 * i:16 * i + 16] for i in range(1026)]
+    dig = qc.digests_of(chunks)
+    assert len({bytes(d) for d in dig}) == 1026
+    with M.Engine() as e, e.zset() as zs, e.batch() as b:
+        for k in (0, 513):
+            _, _, ze, zb = qc.zpack_of(chunks[k:k + 513])
+            zs.add_zblob(zb, ze)
+        assert (zs.info.n_digests, zs.info.n_entries, zs.info.n_packs) == (1026, 1026, 2)
+        held, want, info = zs.missing(dig)
+        assert held.all() and len(want) == 0 and info.n_want == 0
+        pick = [0, 512, 1025]                                    # the first, the 513th and the last
+        b.add_zrecipes(zs, [qc.recipe(chunks, pick, dig=dig)], verify=True)
+        b.run()
+        assert b.read_file(0, 0, 48) == b"".join(chunks[k] for k in pick)
+
+
 # ---- 8. keys that collide ---------------------------------------------------------------------------------------------------------------
 def test_digests_that_share_their_first_eight_bytes_resolve_to_their_own_chunks():
     rng = np.random.default_rng(108)

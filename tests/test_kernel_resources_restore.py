@@ -8,8 +8,7 @@ from test_kernel_resources import HIPCC, _usage
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 
-KERNELS = ["mi::packset_begin_kernel", "mi::packset_check_kernel", "mi::packset_export_kernel", "mi::packset_probe_kernel",
-           "mi::packset_unpack_kernel", "mi::packset_verify_kernel", "mi::restore_assemble_kernel", "mi::restore_compare_kernel",
+KERNELS = ["mi::packset_check_kernel", "mi::packset_unpack_kernel", "mi::restore_assemble_kernel", "mi::restore_compare_kernel",
            "mi::restore_lookup_kernel"]
 
 
@@ -34,5 +33,5 @@ def test_the_assemble_kernel_keeps_the_figures_the_design_states(usage):
     assert g["VGPRs"] <= 72 and g["Occupancy [waves/SIMD]"] == 7, g
     for name in KERNELS:
         if name != "mi::restore_assemble_kernel":
-            # the table's and the compare kernels: a counter word in LDS at the most
+            # the set's, the lookup and the compare kernels: a counter word in LDS at the most
             assert usage[name]["VGPRs"] <= 64 and usage[name]["Occupancy [waves/SIMD]"] == 8 and usage[name]["LDS Size [bytes/block]"] <= 16, (name, usage[name])

@@ -8,9 +8,8 @@ from test_kernel_resources import HIPCC, _usage
 
 pytestmark = pytest.mark.skipif(not os.path.exists(HIPCC), reason="needs hipcc")
 
-KERNELS = ["mi::zset_begin_kernel", "mi::zset_block_offsets_kernel", "mi::zset_block_sums_kernel", "mi::zset_compact_entries_kernel",
-           "mi::zset_compare_kernel", "mi::zset_export_kernel", "mi::zset_gather_kernel", "mi::zset_lookup_kernel", "mi::zset_probe_kernel",
-           "mi::zset_restore_kernel", "mi::zset_unpack_kernel", "mi::zset_verify_kernel"]
+KERNELS = ["mi::zset_block_offsets_kernel", "mi::zset_block_sums_kernel", "mi::zset_compact_entries_kernel", "mi::zset_compare_kernel",
+           "mi::zset_gather_kernel", "mi::zset_lookup_kernel", "mi::zset_restore_kernel", "mi::zset_unpack_kernel"]
 
 
 @pytest.fixture(scope="module")
