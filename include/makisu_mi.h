@@ -917,6 +917,10 @@ MI_CORE int  mi_memfs_commit_stats(const mi_memfs* fs, mi_commit_stats* out);
  * is MI_ERR_INVALID from mi_memfs_set_options: mi_pack_compress, or a decode, makes the other form; the commit does not do the
  * work twice.                                                                                                              */
 #define MI_MEMFS_CHUNK_ZPACK 0x4u
+/* MI_MEMFS_ZPACK_LEVEL2: beside MI_MEMFS_CHUNK_ZPACK (alone it changes nothing), the commit's zpack is coded at level 2
+ * (mi_batch_zpack_chunks with MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2): mi_memfs_take_zpack is then byte for byte what
+ * mi_memfs_take_pack followed by mi_pack_compress(MI_ZPACK_LEVEL2) gives.  The layer, the recipes and the index are the same. */
+#define MI_MEMFS_ZPACK_LEVEL2 0x10u
 MI_CORE int  mi_memfs_set_options(mi_memfs* fs, uint32_t options);
 /* From now on every content-aware commit of this handle adds its batch to `index` (NULL: stop).  The index must belong
  * to the ctx the commits run on and outlive them; the handle does not own it.                                          */
@@ -1174,7 +1178,14 @@ MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const
  * literals, a 2-byte little-endian offset in 1..65535, match-length extension bytes; the last sequence is literals only, the
  * last 5 bytes are literals, no match starts within the last 12 bytes) that any LZ4 library expands.  The coder keeps the block
  * only when it is smaller than length - (length >> 4); chunks under 13 bytes are always raw.  Blob and entries are a pure
- * function of the input pack: no timing, no hardware write order, no device shows in them.
+ * function of the input pack and the LEVEL: no timing, no hardware write order, no device shows in them.
+ * LEVELS.  The coder has two parses for the one format.  Level 1 (flags without MI_ZPACK_LEVEL2): the minimal parse, every byte
+ * as before there were levels.  MI_ZPACK_LEVEL2: a denser parse (two hash tables, the longest of the step's matches, backward
+ * extension, every position of a match remembered) that stores fewer bytes over a corpus -- NOT for every chunk: a single
+ * chunk may store a few bytes more at level 2 than at level 1 -- and takes twice the LDS per wave.  The flag is taken by the calls
+ * that CODE: mi_pack_compress and mi_batch_zpack_chunks, alone or with MI_ZPACK_VERIFY.  Nothing that reads, moves or decodes a
+ * stored form takes it or needs it: mi_zpack_check, mi_packset_add_z*, mi_zset_add_z*, mi_zset_zpack, mi_zset_missing,
+ * mi_zset_prune and mi_batch_add_zrecipes treat a block of either level alike.
  *   mi_pack_compress      any pack (mi_batch_pack_chunks, mi_memfs_take_pack, mi_packset_pack), which stays the caller's and is
  *                         not changed.  Blocking, on the ctx stream.  The zpack is a child of the pack's ctx (mi_ctx_destroy
  *                         refuses while one lives).  0 entries: a zpack of 0 entries.  The coder's scratch (worst-case spans)
@@ -1201,6 +1212,7 @@ MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const
  *                         the same input (structure first, then the first entry that does not decode, then the first that
  *                         does not hash).                                                                                */
 #define MI_ZPACK_VERIFY 0x1u
+#define MI_ZPACK_LEVEL2 0x4u   /* mi_pack_compress, mi_batch_zpack_chunks: the denser parse (LEVELS above) */
 typedef struct mi_zpack mi_zpack;
 typedef struct {               /* 56 bytes: mi_pack_entry's layout */
     uint8_t  digest[32];       /* of the chunk's PLAIN bytes (the ctx's algorithm) */
@@ -1230,9 +1242,12 @@ MI_BLOCK int  mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpa
                              uint32_t alg, uint64_t* first_bad);
 
 /* ---- compressed pack sets: zpacks resident AS STORED, cut by digest and restored without recoding ------------------ *
- * A chunk's stored form is a pure function of its bytes (every chunk is coded on its own), so a store server answers a want
- * list by MOVING stored spans -- no decode, no parse -- and the result is byte for byte what mi_packset_pack followed by
- * mi_pack_compress gives; a puller decodes every recipe row straight to its place in the arena, no plain blob in between.
+ * A chunk's stored form is a pure function of its bytes and the level (every chunk is coded on its own), so a store server
+ * answers a want list by MOVING stored spans -- no decode, no parse -- and the result is byte for byte what mi_packset_pack
+ * followed by mi_pack_compress AT THE LEVEL THE SPANS WERE CODED AT gives; a puller decodes every recipe row straight to its
+ * place in the arena, no plain blob in between.  A set that meets the same digest at two levels keeps the first form, under the
+ * rule below; mi_zset_zpack, mi_zset_missing, mi_zset_prune and mi_batch_add_zrecipes take no level flag: they move or decode
+ * stored forms, whoever coded them.
  *   mi_zset_create        a COMPRESSED PACK SET: a device hash table as mi_packset_create makes one (open addressing, the tag a
  *                         digest's first 8 bytes, entries_hint sizes it, rebuilt at twice the size when it passes half full); a
  *                         slot holds the digest, the device address of the stored span and length | stored << 32.  A child of
@@ -1305,7 +1320,8 @@ MI_BLOCK int  mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_
  *                         on the ctx stream; the batch is not changed.  The call needs the coder's scratch (the sum of the
  *                         worst-case spans: the selected bytes + 0.4 % + up to 31 bytes a chunk) and the blob; if either does
  *                         not fit: MI_ERR_NOMEM naming the size and what the device has free, nothing has changed, the caller
- *                         splits the selection.  MI_ZPACK_VERIFY (the only flag): the new blob is decoded again on the device
+ *                         splits the selection.  MI_ZPACK_LEVEL2: the denser parse, and then what mi_pack_compress gives
+ *                         WITH THAT FLAG.  MI_ZPACK_VERIFY (the only other flag): the new blob is decoded again on the device
  *                         into the scratch, hashed by the ctx's own hashing kernel and held against THE BATCH'S digest table at
  *                         chunk_index -- one decode and one hashing pass vouch for both hops, arena -> stored form -> plain
  *                         again; an entry that differs or does not decode is MI_ERR_IO naming the entry, the chunk row, the

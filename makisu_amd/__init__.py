@@ -21,7 +21,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
-           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK",
+           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK", "ZPACK_LEVEL2", "MEMFS_ZPACK_LEVEL2",
            "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP",
            "IndexPruneInfo", "INDEX_PRUNE_KEEP", "INDEX_PRUNE_DROP"]
 
@@ -112,6 +112,7 @@ LAYER_MODE_WITH_TYPE = 0x1
 MEMFS_TRUST_CTIME = 0x1
 MEMFS_CHUNK_PACK = 0x2                   # a commit also packs the chunks its index did not know (MemFS.take_pack) and keeps the recipes
 MEMFS_CHUNK_ZPACK = 0x4                  # ... codes them straight from the arena into a compressed pack instead (MemFS.take_zpack)
+MEMFS_ZPACK_LEVEL2 = 0x10                # ... at level 2 (beside MEMFS_CHUNK_ZPACK)
 PACK_VERIFY = 0x1                        # mi_batch_pack_chunks: hash the blob again on the device
 
 
@@ -166,6 +167,7 @@ class WantInfo(C.Structure):
 
 
 ZPACK_VERIFY = 0x1                       # mi_pack_compress: the new blob decoded and hashed again on the device
+ZPACK_LEVEL2 = 0x4                       # mi_pack_compress, mi_batch_zpack_chunks: the denser parse, the same block format
 
 
 class ZPackEntry(C.Structure):
@@ -243,6 +245,13 @@ GZIP_OFF, GZIP_DEFAULT = -2, -1
 # tario.SetCompressionLevel's names (lib/tario/gzip.go:28-43; the `--compression` flag of bin/makisu/cmd/build.go) -> the
 # gzip_level of mi_layer_config: "no" is a gzip member of stored blocks (pgzip.NoCompression), not MI_GZIP_OFF
 COMPRESSION_LEVELS = {"no": 0, "speed": 1, "size": 9, "default": GZIP_DEFAULT}
+
+
+def _zpack_level_flag(level):
+    """the zpack coder's level (1: every byte as ever, 2: MI_ZPACK_LEVEL2) as a flag of the calls that code"""
+    if level not in (1, 2):
+        raise ValueError("a zpack is coded at level 1 or 2, not %r" % (level,))
+    return ZPACK_LEVEL2 if level == 2 else 0
 
 
 def compression_level(name):
@@ -949,14 +958,16 @@ class MemFS:
         engine._children.add(self)
         self._check(self._lib.mi_memfs_reserve_device(self._h, engine._h, files, nbytes), "mi_memfs_reserve_device")
 
-    def set_options(self, trust_ctime=False, chunk_pack=False, chunk_zpack=False):
+    def set_options(self, trust_ctime=False, chunk_pack=False, chunk_zpack=False, zpack_level=1):
         """MI_MEMFS_TRUST_CTIME: scan commits do not read files again whose inode is what it was when they were hashed.
         MI_MEMFS_CHUNK_PACK: a commit (one Engine, an index set) also packs the chunks the index did not know -- take_pack() --
         and its layer's regular files carry "chunks": [(digest, length), ...], their recipes.
         MI_MEMFS_CHUNK_ZPACK: the same with the chunks coded straight from the arena into a compressed pack -- take_zpack();
-        both at once are refused (MI_ERR_INVALID)"""
+        both at once are refused (MI_ERR_INVALID); zpack_level=2 (MI_MEMFS_ZPACK_LEVEL2): that zpack is coded at level 2"""
+        _zpack_level_flag(zpack_level)
         self._check(self._lib.mi_memfs_set_options(self._h, (MEMFS_TRUST_CTIME if trust_ctime else 0) | (MEMFS_CHUNK_PACK if chunk_pack else 0) |
-                                                   (MEMFS_CHUNK_ZPACK if chunk_zpack else 0)), "mi_memfs_set_options")
+                                                   (MEMFS_CHUNK_ZPACK if chunk_zpack else 0) | (MEMFS_ZPACK_LEVEL2 if zpack_level == 2 else 0)),
+                    "mi_memfs_set_options")
         self._chunk_pack, self._chunk_zpack = bool(chunk_pack), bool(chunk_zpack)
 
     def take_pack(self):
@@ -1267,11 +1278,11 @@ class Pack:
         self._eng._check(self._lib.mi_pack_device(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def compress(self, verify=False):
+    def compress(self, verify=False, level=1):
         """mi_pack_compress: every chunk coded on its own as one LZ4 block (or kept raw) on the device -> ZPack; this pack
-        is not changed"""
+        is not changed.  level=2 (MI_ZPACK_LEVEL2): the denser parse, the same block format"""
         h = C.c_void_p()
-        self._eng._check(self._lib.mi_pack_compress(self._h, ZPACK_VERIFY if verify else 0, C.byref(h)))
+        self._eng._check(self._lib.mi_pack_compress(self._h, (ZPACK_VERIFY if verify else 0) | _zpack_level_flag(level), C.byref(h)))
         return ZPack(self._eng, h)
 
     def close(self):
@@ -1951,13 +1962,17 @@ class Batch:
     def zpack(self, select=None, verify=False):
         """mi_batch_zpack_chunks: pack(select).compress() without the plain pack -- the selected rows coded where they lie in
         the arena, byte for byte the same ZPack; verify: decoded again and held against the batch's own digests"""
+        return self.zpack_at(1, select, verify)
+
+    def zpack_at(self, level, select=None, verify=False):
+        """zpack() at a level: 2 is MI_ZPACK_LEVEL2, byte for byte pack(select).compress(level=2)"""
         h = C.c_void_p()
         ptr, n = None, 0
         if select is not None:
             sel = np.zeros(max(len(select), 1), dtype=np.uint8)      # (never NULL: NULL means every row)
             sel[:len(select)] = np.asarray(select) != 0
             ptr, n = sel.ctypes.data, len(select)
-        self._check(self._lib.mi_batch_zpack_chunks(self._h, ptr, n, ZPACK_VERIFY if verify else 0, C.byref(h)))
+        self._check(self._lib.mi_batch_zpack_chunks(self._h, ptr, n, (ZPACK_VERIFY if verify else 0) | _zpack_level_flag(level), C.byref(h)))
         return ZPack(self.engine, h)
 
     def add_recipes(self, packset, recipes, tags=None, verify=False):

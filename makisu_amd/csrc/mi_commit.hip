@@ -495,13 +495,14 @@ struct Commit {
     // MI_MEMFS_CHUNK_PACK: the rows whose bytes index_new_bytes counts as ONE blob (mi_batch_pack_chunks with MI_PACK_VERIFY: the
     // batch still holds the tree's bytes), and every layer file's ordered chunks.  A pack that cannot be built does not fail the
     // commit -- the layer is written: mi_memfs_take_pack returns the error and the message.  MI_MEMFS_CHUNK_ZPACK: the same rows
-    // coded straight from the arena (mi_batch_zpack_chunks with MI_ZPACK_VERIFY), the same recipes.
+    // coded straight from the arena (mi_batch_zpack_chunks with MI_ZPACK_VERIFY, and MI_ZPACK_LEVEL2 under MI_MEMFS_ZPACK_LEVEL2), the
+    // same recipes.
     void pack_and_recipes(mi_batch* mb, const mi_chunk_result* rows, uint64_t nc, const uint8_t* known) {
         std::vector<uint8_t> select(nc ? nc : 1);
         for (uint64_t i = 0; i < nc; ++i) select[i] = !known[i] && rows[i].dup_of < 0;
         if (m->chunk_zpack) {
             mi_zpack* z = nullptr;
-            const int zrc = mi_batch_zpack_chunks(mb, select.data(), nc, MI_ZPACK_VERIFY, &z);
+            const int zrc = mi_batch_zpack_chunks(mb, select.data(), nc, MI_ZPACK_VERIFY | (m->zpack_level2 ? MI_ZPACK_LEVEL2 : 0u), &z);
             memfs_zpack_drop(m, zrc, zrc ? std::string("chunk zpack: ") + mi_last_error(ctx) : std::string());
             m->zpack = z;
         } else {
@@ -635,7 +636,7 @@ extern "C" int mi_memfs_commit_stats(const mi_memfs* m, mi_commit_stats* out) {
     return MI_OK;
 }
 extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
-    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK | MI_MEMFS_CHUNK_ZPACK))) return MI_ERR_INVALID;
+    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK | MI_MEMFS_CHUNK_ZPACK | MI_MEMFS_ZPACK_LEVEL2))) return MI_ERR_INVALID;
     if ((options & MI_MEMFS_CHUNK_PACK) && (options & MI_MEMFS_CHUNK_ZPACK)) {    // mi_pack_compress, or a decode, makes the other form
         m->err = "mi_memfs_set_options: MI_MEMFS_CHUNK_PACK and MI_MEMFS_CHUNK_ZPACK exclude each other: the commit does not do the work twice";
         return MI_ERR_INVALID;
@@ -643,6 +644,7 @@ extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
     m->fs.trust_ctime = (options & MI_MEMFS_TRUST_CTIME) != 0;
     m->chunk_pack = (options & MI_MEMFS_CHUNK_PACK) != 0;
     m->chunk_zpack = (options & MI_MEMFS_CHUNK_ZPACK) != 0;
+    m->zpack_level2 = (options & MI_MEMFS_ZPACK_LEVEL2) != 0;            // (alone it changes nothing: there is no zpack to code)
     return MI_OK;
 }
 extern "C" int mi_memfs_take_zpack(mi_memfs* m, mi_zpack** out) {

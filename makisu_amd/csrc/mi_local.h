@@ -109,6 +109,11 @@ MI_LOCAL int  mi_zpack_device(const mi_zpack* z, mi_ctx** ctx, const void** d_bl
 MI_LOCAL int  mi_zpack_decode_enqueue(mi_ctx* ctx, const void* d_zblob, const uint64_t* d_rows, const uint64_t* d_poff, uint64_t n,
                                       void* d_out, uint32_t* d_rule, uint64_t* d_first_bad);
 MI_LOCAL void mi_zpack_set_encode_ms(mi_zpack* z, double ms_encode);
+// mi_zpack2.hip, for mi_zpack.hip and mi_zbatch.hip (MI_ZPACK_LEVEL2): the level-2 encode kernel ENQUEUED on the ctx stream in
+// place of the caller's level-1 kernel, with that kernel's arguments -- d_base: the pack's blob or the batch's arena, d_rows[k]'s
+// offset word the chunk's offset from it -- over `waves` workgroups of one wave
+MI_LOCAL int  mi_zencode_l2_enqueue(mi_ctx* ctx, const void* d_base, uint64_t* d_rows, const uint64_t* d_woff, void* d_scratch, uint64_t n,
+                                    uint32_t waves);
 // mi_zset.hip, for mi_zbatch.hip (mi_zset_missing): the set's ctx -- MI_ERR_STATE under `who` with the first message for a set in
 // its sticky failed state, MI_ERR_INVALID for NULL -- and zset_lookup_kernel ENQUEUED on the ctx stream over n digests on the
 // device: d_src[r] / d_word[r] = where the set holds row r's stored span and its length | stored << 32 (0, 0: not held),

@@ -342,7 +342,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     mi_ctx* c = b->ctx;
     *out = nullptr;
     if (b->group) return fail(c, MI_ERR_INVALID, "%s: a batch group has one arena per GPU; pack its members", who);
-    if (flags & ~(uint32_t)MI_ZPACK_VERIFY) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    if (flags & ~(uint32_t)(MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
     if (!b->ran || b->in_flight) return fail(c, MI_ERR_STATE, "%s: the batch must have run (and been waited for)", who);
     const u64 n = b->n_chunks;
     if (select && n_select != n)
@@ -411,8 +411,14 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     hipLaunchKernelGGL(zbatch_compact_kernel, dim3((u32)nb), dim3(kBBlock), 0, s, d_sel.as<u8>(), b->chunk_off.as<u64>(), b->chunk_len.as<u64>(),
                        b->digests.as<u8>(), n, block_cnt, block_span, d_rows.as<u64>(), d_woff.as<u64>(), d_aoff.as<u64>(), d_plen.as<u64>());
     HIPCHK(c, hipEventRecord(ev[3], s));
-    hipLaunchKernelGGL(zbatch_encode_kernel, dim3((u32)std::min<u64>(n_sel, kEncodeWaves)), dim3(64), 0, s, b->arena.as<u8>(), d_rows.as<u64>(),
-                       d_woff.as<u64>(), d_scratch.as<u8>(), n_sel);
+    if (flags & MI_ZPACK_LEVEL2) {                         // the denser parse (mi_zpack2.hip): the same rows, spans and scratch
+        if ((rc = mi_zencode_l2_enqueue(c, b->arena.p, d_rows.as<u64>(), d_woff.as<u64>(), d_scratch.p, n_sel,
+                                        (u32)std::min<u64>(n_sel, kEncodeWaves))))
+            return fail(c, rc, "%s: the level-2 coder was refused", who);
+    } else {
+        hipLaunchKernelGGL(zbatch_encode_kernel, dim3((u32)std::min<u64>(n_sel, kEncodeWaves)), dim3(64), 0, s, b->arena.as<u8>(), d_rows.as<u64>(),
+                           d_woff.as<u64>(), d_scratch.as<u8>(), n_sel);
+    }
     HIPCHK(c, hipEventRecord(ev[4], s));
     u64* block_bytes = block_span;
     hipLaunchKernelGGL(zbatch_layout_sums_kernel, dim3((u32)nb_sel), dim3(kBBlock), 0, s, d_rows.as<u64>(), n_sel, block_bytes, totals);

@@ -517,7 +517,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     if (!p || !out) return MI_ERR_INVALID;
     static const char* who = "mi_pack_compress";
     mi_ctx* c = mi_pack_ctx(p);
-    if (flags & ~(uint32_t)MI_ZPACK_VERIFY) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    if (flags & ~(uint32_t)(MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
     mi_pack_info pi;
     const void* d_pack = nullptr;
     u64 pack_bytes = 0;
@@ -567,8 +567,13 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     HIPCHK(c, hipMemsetAsync(totals, 0, 4 * 8, s));
     HIPCHK(c, hipMemsetAsync(totals + kZTotBad, 0xFF, 8, s));
     HIPCHK(c, hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(zpack_encode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, (const u8*)d_pack, d_rows.as<u64>(), d_woff.as<u64>(),
-                       d_scratch.as<u8>(), n);
+    if (flags & MI_ZPACK_LEVEL2) {                         // the denser parse (mi_zpack2.hip): the same rows, spans and scratch
+        if ((rc = mi_zencode_l2_enqueue(c, d_pack, d_rows.as<u64>(), d_woff.as<u64>(), d_scratch.p, n, wave_grid(n))))
+            return fail(c, rc, "%s: the level-2 coder was refused", who);
+    } else {
+        hipLaunchKernelGGL(zpack_encode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, (const u8*)d_pack, d_rows.as<u64>(), d_woff.as<u64>(),
+                           d_scratch.as<u8>(), n);
+    }
     HIPCHK(c, hipEventRecord(ev[1], s));
     hipLaunchKernelGGL(zpack_block_sums_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), n, block_bytes, totals);
     hipLaunchKernelGGL(zpack_block_offsets_kernel, dim3(1), dim3(kZBlock), 0, s, block_bytes, nb, totals);

@@ -12,7 +12,9 @@ leg's compressor: the only yardstick there is for "compressing these bytes on th
 own chunk pass.  No threshold on any time.
 Each GPU step is a process of its own under a time limit: `chunk_zpack_bench.py` starts `chunk_zpack_bench.py --step ...` with
 timeout(1) and stops at the first step that fails.
-chunk_zpack_bench.py [out = profiles/chunk_zpack.txt] [files = 20000] [runs = 10] [bytes = 2e9]   (needs an MI355X)"""
+--level 2: every leg ALSO compresses the same pack with MI_ZPACK_LEVEL2 in the same run and states ms_encode and the
+stored bytes of both levels side by side; the output then goes to profiles/chunk_zpack_l2.txt.
+chunk_zpack_bench.py [--level 1|2] [out = profiles/chunk_zpack.txt] [files = 20000] [runs = 10] [bytes = 2e9]   (needs an MI355X)"""
 import ctypes as C
 import os
 import statistics
@@ -72,7 +74,7 @@ def zlib_level1_seconds(blob, offsets, lengths):
     return time.perf_counter() - t0, out
 
 
-def leg(eng, hip, b, name, runs, say, host_yardstick):
+def leg(eng, hip, b, name, runs, say, host_yardstick, level=1):
     from chunk_pack_bench import d2d_copy_ms
     b.run()
     b.rerun()
@@ -101,6 +103,19 @@ def leg(eng, hip, b, name, runs, say, host_yardstick):
         say("    compact %.3f ms (min %.3f, max %.3f): %.2f GB/s" % (c, min(comp), max(comp), gbs(c)))
         say("    decode  %.3f ms (min %.3f, max %.3f): %.2f GB/s" % (d, min(dec), max(dec), gbs(d)))
         say("    MI_ZPACK_VERIFY (decode + hash + compare): %.3f ms; the batch's own chunk pass over every row: %.3f ms" % (v, ms_chunk_pass))
+        if level == 2:                                                            # the same pack, the same run, the denser parse
+            enc2, zi2 = [], None
+            for k in range(runs + 2):
+                with p.compress(verify=True, level=2) as z:
+                    zi2 = z.info.as_dict()
+                if k >= 2:
+                    enc2.append(zi2["ms_encode"])
+            e2 = statistics.median(enc2)
+            say("    level 2 (MI_ZPACK_LEVEL2), the same pack: encode %.3f ms (min %.3f, max %.3f): %.2f GB/s against level 1's %.3f ms = "
+                "%.2f x the time" % (e2, min(enc2), max(enc2), gbs(e2), e, e2 / e))
+            say("    level 2 stored / chunk bytes: %.4f (%d bytes, %d entries raw) against level 1's %.4f (%d bytes, %d raw): %.4f of level 1's "
+                "stored bytes; verified %d" % (zi2["stored_bytes"] / cb, zi2["stored_bytes"], zi2["n_raw"], zi["stored_bytes"] / cb,
+                                               zi["stored_bytes"], zi["n_raw"], zi2["stored_bytes"] / zi["stored_bytes"], zi2["verified"]))
         ptr, nb = p.device()
         copy = d2d_copy_ms(hip, C.c_void_p(ptr), nb, runs)
         cm = statistics.median(copy)
@@ -114,7 +129,7 @@ def leg(eng, hip, b, name, runs, say, host_yardstick):
                 (HOST_THREADS, secs, cb / secs / 1e9, out / cb, secs * 1e3 / (e + c), zi["stored_bytes"] / out))
 
 
-def step(n_files, runs, limit):
+def step(n_files, runs, limit, level=1):
     import makisu_amd as M
     from makisu_amd import workloads as W
     from chunk_pack_bench import _hip
@@ -129,7 +144,7 @@ def step(n_files, runs, limit):
         with eng.batch(sh.n_files, W.batch_bytes_hint(sh)) as b:
             W.fill_batch(b, sh)
             leg(eng, hip, b, "incompressible leg -- %d synthetic files x 64 KiB, RANDOM bytes: every chunk is stored raw, this measures the "
-                "raw path only" % sh.n_files, runs, say, False)
+                "raw path only" % sh.n_files, runs, say, False, level)
         files, total = usr_lib_files(limit)
         say("compressible leg -- %d regular files under /usr/lib, %d bytes, largest first:" % (len(files), total))
         for p, size in files[:12]:
@@ -138,18 +153,26 @@ def step(n_files, runs, limit):
             say("        ... and %d smaller ones" % (len(files) - 12))
         with eng.batch(len(files), total + 4096 * len(files)) as b:
             b.add_paths([p for p, _ in files], [s for _, s in files])
-            leg(eng, hip, b, "the files", runs, say, True)
+            leg(eng, hip, b, "the files", runs, say, True, level)
 
 
 def main():
+    level = 1
+    if "--level" in sys.argv:
+        at = sys.argv.index("--level")
+        level = int(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+        if level not in (1, 2):
+            sys.exit("--level 1 or 2")
     if sys.argv[1:2] == ["--step"]:
-        return step(int(sys.argv[2]), int(sys.argv[3]), int(float(sys.argv[4])))
-    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "chunk_zpack.txt")
+        return step(int(sys.argv[2]), int(sys.argv[3]), int(float(sys.argv[4])), level)
+    out = sys.argv[1] if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "chunk_zpack_l2.txt" if level == 2 else "chunk_zpack.txt")
     n_files = int(sys.argv[2]) if len(sys.argv) > 2 else 20000
     runs = max(10, int(sys.argv[3])) if len(sys.argv) > 3 else 10
     limit = sys.argv[4] if len(sys.argv) > 4 else "2e9"
     # the one GPU step, a fresh process under its own time limit; nothing is started after a failure
-    cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "--step", str(n_files), str(runs), limit]
+    cmd = ["timeout", "-k", "10", str(STEP_LIMIT_S), sys.executable, os.path.abspath(__file__), "--step", str(n_files), str(runs), limit,
+           "--level", str(level)]
     p = subprocess.run(cmd, capture_output=True, text=True)
     sys.stdout.write(p.stdout)
     sys.stderr.write(p.stderr[-4000:])
