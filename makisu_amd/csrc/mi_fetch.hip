@@ -9,8 +9,8 @@
 //             address, the SET'S length and the held flag; the smallest bad row by atomicMin;
 //   firsts    a row counts only if no smaller row carries its digest: the engine's marking over the uploaded digests
 //             (launch_dedup_mark, what mi_dedup_mark runs: whole digests, dup_of < 0 = a first occurrence);
-//   plan      mi_pack.hip's three launches (block sums over 2 048 rows, one block over the sums, a compacting pass) with the
-//             lengths the resolve found.  missing: first occurrence and not held -> the row numbers, the byte sums;
+//   plan      mi_plan.h's three launches with the lengths the resolve found.  missing: first occurrence and not held -> the
+//             row numbers (the want list, finished by want_list_finish for mi_zset_missing too), the byte sums;
 //             pack: first occurrence -> source address, length, blob offset and the 56-byte mi_pack_entry row per entry;
 //   gather    destination-driven like pack_gather_kernel: 16 KiB tiles, a 256-thread workgroup a tile, the tile's entries (at
 //             most 1 024) in LDS, every lane four 16-byte units 4 KiB apart, all its loads before its first store.  The
@@ -27,6 +27,7 @@
 // nothing behind its padded span is read -- not even the blob's slack.  The verify pass reads what the hashing kernels read
 // behind a string (up to 67 bytes) behind the NEW blob's last entry: inside the 256 bytes it is allocated with.
 #include "mi_gather.h"
+#include "mi_plan.h"
 #include "mi_slot_table.h"
 
 #include <string.h>
@@ -38,9 +39,6 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kFetchNone = ~0ull;
-
-constexpr int kFetchEntryWords = sizeof(mi_pack_entry) / 8;     // digest 4 | offset | chunk_index | length, reserved
-static_assert(sizeof(mi_pack_entry) == 56 && kFetchEntryWords == 7, "mi_pack_entry is seven 8-byte words");
 
 // ---- resolve ------------------------------------------------------------------------------------------------------------------
 // src[r], len64[r]: where the set holds row r's chunk and with how many bytes (0, 0: it does not); held[r]: whether it does.
@@ -71,10 +69,7 @@ void fetch_lookup_kernel(const u8* __restrict__ digests, const u32* __restrict__
     if (bad) atomicMin((unsigned long long*)first_bad, (unsigned long long)r);
 }
 
-// ---- plan: mi_pack.hip's scheme over the resolved rows -------------------------------------------------------------------------
-constexpr int kFetchBlock = 256;
-constexpr int kFetchPer   = 8;                          // rows per thread
-constexpr int kFetchTile  = kFetchBlock * kFetchPer;    // 2048 rows per block
+// ---- plan: mi_plan.h's over the resolved rows -------------------------------------------------------------------------------------
 enum : int { kTotEntries = 0, kTotBlob = 1, kTotRaw = 2, kTotFirst = 3, kTotHeld = 4, kTotHeldBytes = 5, kTotBad = 6, kTotDiffer = 7 };
 
 // the selection: a first occurrence that the set holds (want_held: the sub-pack's entries) or lacks (the want list)
@@ -82,19 +77,18 @@ static __device__ __forceinline__ bool fetch_selected(const i64* __restrict__ du
     return dup_of[row] < 0 && (held[row] != 0) == (want_held != 0);
 }
 
-// per block of kFetchTile rows: the selected rows and their rounded-up bytes (the set's lengths); into the totals: the selected
+// per block of kPlanTile rows: the selected rows and their rounded-up bytes (the set's lengths); into the totals: the selected
 // rows' bytes as they are (the set's lengths, or for the want list the STATED ones: the set knows nothing of a chunk it lacks),
 // the first occurrences, those of them the set holds, and their bytes
-__global__ __launch_bounds__(kFetchBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void fetch_block_sums_kernel(const i64* __restrict__ dup_of, const u8* __restrict__ held, const u64* __restrict__ len64,
                              const u32* __restrict__ stated, u64 n, int want_held, u64* __restrict__ block_cnt,
                              u64* __restrict__ block_bytes, u64* __restrict__ totals) {
-    __shared__ u64 lds[6][kFetchBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * kFetchTile + (u64)threadIdx.x * kFetchPer;
+    __shared__ u64 lds[6][kPlanBlock / 64];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 v[6] = {0, 0, 0, 0, 0, 0};                       // selected, their rounded-up bytes, their bytes, firsts, held firsts, their bytes
 #pragma unroll
-    for (int k = 0; k < kFetchPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const u64 row = base + k;
         if (row >= n || dup_of[row] >= 0) continue;
         const bool h = held[row] != 0;
@@ -107,98 +101,56 @@ void fetch_block_sums_kernel(const i64* __restrict__ dup_of, const u8* __restric
             v[2] += want_held ? len : stated ? (u64)stated[row] : 0ull;
         }
     }
-#pragma unroll
-    for (int q = 0; q < 6; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) lds[q][wave] = v[q];
-    }
-    __syncthreads();
+    plan_block_sum<6>(v, lds);
     if (threadIdx.x == 0) {
-        u64 t[6];
-#pragma unroll
-        for (int q = 0; q < 6; ++q) {
-            t[q] = 0;
-#pragma unroll
-            for (int w = 0; w < kFetchBlock / 64; ++w) t[q] += lds[q][w];
-        }
-        block_cnt[blockIdx.x] = t[0];
-        block_bytes[blockIdx.x] = t[1];
-        if (t[2]) atomicAdd((unsigned long long*)&totals[kTotRaw], (unsigned long long)t[2]);
-        if (t[3]) atomicAdd((unsigned long long*)&totals[kTotFirst], (unsigned long long)t[3]);
-        if (t[4]) atomicAdd((unsigned long long*)&totals[kTotHeld], (unsigned long long)t[4]);
-        if (t[5]) atomicAdd((unsigned long long*)&totals[kTotHeldBytes], (unsigned long long)t[5]);
+        block_cnt[blockIdx.x] = v[0];
+        block_bytes[blockIdx.x] = v[1];
+        if (v[2]) atomicAdd((unsigned long long*)&totals[kTotRaw], (unsigned long long)v[2]);
+        if (v[3]) atomicAdd((unsigned long long*)&totals[kTotFirst], (unsigned long long)v[3]);
+        if (v[4]) atomicAdd((unsigned long long*)&totals[kTotHeld], (unsigned long long)v[4]);
+        if (v[5]) atomicAdd((unsigned long long*)&totals[kTotHeldBytes], (unsigned long long)v[5]);
     }
 }
 
 // single block: exclusive scan of both block arrays in place; the totals: selected rows, their rounded-up bytes
-__global__ __launch_bounds__(kFetchBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void fetch_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ block_bytes, u64 n_blocks, u64* __restrict__ totals) {
-    __shared__ u64 lds[4];
-    u64 carry_c = 0, carry_b = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kFetchBlock) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
-        u64 tc, tb;
-        const u64 ec = block_exclusive_scan_u64<kFetchBlock>(vc, &tc, lds);
-        const u64 eb = block_exclusive_scan_u64<kFetchBlock>(vb, &tb, lds);
-        if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
-        carry_c += tc;
-        carry_b += tb;
-    }
-    if (threadIdx.x == 0) { totals[kTotEntries] = carry_c; totals[kTotBlob] = carry_b; }
+    plan_block_offsets<true>(block_cnt, block_bytes, n_blocks, &totals[kTotEntries], &totals[kTotBlob]);
 }
 
 // the want list: the selected rows' numbers, ascending
-__global__ __launch_bounds__(kFetchBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void fetch_compact_rows_kernel(const i64* __restrict__ dup_of, const u8* __restrict__ held, u64 n, const u64* __restrict__ block_cnt,
                                u64* __restrict__ want_rows) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kFetchTile + (u64)threadIdx.x * kFetchPer;
-    u32 sel = 0;
-    u64 cnt = 0;
-#pragma unroll
-    for (int k = 0; k < kFetchPer; ++k)
-        if (base + k < n && fetch_selected(dup_of, held, base + k, 0)) { sel |= 1u << k; ++cnt; }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kFetchBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kFetchPer; ++k)
-        if (sel & (1u << k)) want_rows[at++] = base + k;
+    want_rows_body([=](u64 row) { return fetch_selected(dup_of, held, row, 0); }, n, block_cnt, want_rows);
 }
 
 // the sub-pack's entries, in order of first occurrence: where the chunk lies, its length, where it goes in the blob, and the
 // mi_pack_entry row (digest | offset | chunk_index = the request row | length, reserved = 0)
-__global__ __launch_bounds__(kFetchBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void fetch_compact_entries_kernel(const i64* __restrict__ dup_of, const u8* __restrict__ held, const u64* __restrict__ src,
                                   const u64* __restrict__ len64, const u8* __restrict__ digests, u64 n,
                                   const u64* __restrict__ block_cnt, const u64* __restrict__ block_bytes, u64* __restrict__ e_src,
                                   u64* __restrict__ e_len, u64* __restrict__ e_dst, u64* __restrict__ rows) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kFetchTile + (u64)threadIdx.x * kFetchPer;
-    u64 len[kFetchPer];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
+    u64 len[kPlanPer];
     u64 cnt = 0, bytes = 0;
 #pragma unroll
-    for (int k = 0; k < kFetchPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const bool sel = base + k < n && fetch_selected(dup_of, held, base + k, 1);
         len[k] = sel ? len64[base + k] : kFetchNone;
         if (sel) { ++cnt; bytes += round16(len[k]); }
     }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kFetchBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = block_exclusive_scan_u64<kFetchBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = plan_first(cnt, block_cnt);
+    u64 dst = plan_first(bytes, block_bytes);
 #pragma unroll
-    for (int k = 0; k < kFetchPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         if (len[k] == kFetchNone) continue;
         const u64 row = base + k;
         e_src[at] = src[row];
         e_len[at] = len[k];
         e_dst[at] = dst;
-        const u64* d = (const u64*)(digests + 32 * row);
-        u64* r = rows + kFetchEntryWords * at;
-        r[0] = d[0]; r[1] = d[1]; r[2] = d[2]; r[3] = d[3];
-        r[4] = dst;
-        r[5] = row;
-        r[6] = len[k] & 0xFFFFFFFFull;                 // length | reserved = 0
+        put_entry_row(rows + kEntryWords * at, digests + 32 * row, dst, row, len[k] & 0xFFFFFFFFull);   // length | reserved = 0
         ++at;
         dst += round16(len[k]);
     }
@@ -217,21 +169,12 @@ __global__ __launch_bounds__(256)
 void fetch_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ rows, u64 n, u64* __restrict__ first_bad) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* g = (const u64*)(got + 32 * k);
-    const u64* w = rows + kFetchEntryWords * k;
-    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+    digest_differs_mark(got, rows + kEntryWords * k, k, first_bad);
 }
 
 }  // namespace mi
 
 namespace {
-
-std::string hex32(const uint8_t* d) {
-    static const char* dig = "0123456789abcdef";
-    std::string out(64, '0');
-    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
-    return out;
-}
 
 // what one call holds on the device until it returns
 struct Request {
@@ -250,7 +193,7 @@ int resolve_and_plan(mi_ctx* c, const uint64_t* tags, const uint64_t* slots, u64
                      u64 n, bool must_hold, Request* q) {
     hipStream_t s = c->stream;
     for (auto& e : q->ev) HIPCHK(c, e.create());
-    q->nb = (n + kFetchTile - 1) / kFetchTile;
+    q->nb = (n + kPlanTile - 1) / kPlanTile;
     u64 dd_cap = 1024;
     while (dd_cap < 2 * n) dd_cap <<= 1;
     HIPCHK(c, q->dig.ensure(n * 32));
@@ -277,11 +220,11 @@ int resolve_and_plan(mi_ctx* c, const uint64_t* tags, const uint64_t* slots, u64
                        must_hold ? 1 : 0, q->src.as<u64>(), q->len64.as<u64>(), q->held.as<u8>(), q->totals + kTotBad);
     launch_dedup_mark(q->dig.as<u8>(), n, nullptr, c->dd_table.as<u32>(), c->dd_slot.as<u32>(), dd_cap, q->dup.as<i64>(),
                       c->dd_nuniq.as<u64>(), true, s);
-    hipLaunchKernelGGL(fetch_block_sums_kernel, dim3((u32)q->nb), dim3(kFetchBlock), 0, s, q->dup.as<i64>(), q->held.as<u8>(),
+    hipLaunchKernelGGL(fetch_block_sums_kernel, dim3((u32)q->nb), dim3(kPlanBlock), 0, s, q->dup.as<i64>(), q->held.as<u8>(),
                        q->len64.as<u64>(), q->stated(), n, must_hold ? 1 : 0, q->block_cnt, q->block_bytes, q->totals);
-    hipLaunchKernelGGL(fetch_block_offsets_kernel, dim3(1), dim3(kFetchBlock), 0, s, q->block_cnt, q->block_bytes, q->nb, q->totals);
+    hipLaunchKernelGGL(fetch_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, q->block_cnt, q->block_bytes, q->nb, q->totals);
     if (!must_hold)
-        hipLaunchKernelGGL(fetch_compact_rows_kernel, dim3((u32)q->nb), dim3(kFetchBlock), 0, s, q->dup.as<i64>(), q->held.as<u8>(), n,
+        hipLaunchKernelGGL(fetch_compact_rows_kernel, dim3((u32)q->nb), dim3(kPlanBlock), 0, s, q->dup.as<i64>(), q->held.as<u8>(), n,
                            q->block_cnt, q->want.as<u64>());
     HIPCHK(c, hipEventRecord(q->ev[1], s));
     HIPCHK(c, hipMemcpyAsync(c->h_word.p, q->totals, 8 * 8, hipMemcpyDeviceToHost, s));
@@ -308,6 +251,37 @@ int refuse_row(mi_ctx* c, const char* who, const Request& q, u64 bad, const uint
 
 }  // namespace
 
+namespace mi {
+
+int want_list_finish(mi_ctx* c, const char* who, u64 n, u64 n_distinct, u64 n_held, u64 n_want, u64 held_bytes, u64 want_bytes,
+                     hipEvent_t ev0, hipEvent_t ev1, const void* d_held, const void* d_want, uint8_t* held, uint64_t* want_rows,
+                     uint64_t cap, mi_want_info* info) {
+    mi_want_info out = {};
+    out.n_rows = n;
+    out.n_distinct = n_distinct;
+    out.n_held = n_held;
+    out.n_want = n_want;
+    out.held_bytes = held_bytes;
+    out.want_bytes = want_bytes;
+    if (out.n_held + out.n_want != out.n_distinct)
+        return fail(c, MI_ERR_HIP, "%s: the plan counted %llu held and %llu missing among %llu distinct digests", who,
+                    (unsigned long long)out.n_held, (unsigned long long)out.n_want, (unsigned long long)out.n_distinct);
+    float ms = 0;
+    HIPCHK(c, hipEventElapsedTime(&ms, ev0, ev1));
+    out.ms_resolve = ms;
+    if (info) *info = out;
+    const bool fits = out.n_want <= cap;
+    if (held) HIPCHK(c, hipMemcpyAsync(held, d_held, n, hipMemcpyDeviceToHost, c->stream));
+    if (fits && out.n_want) HIPCHK(c, hipMemcpyAsync(want_rows, d_want, out.n_want * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (!fits && (cap || want_rows))
+        return fail(c, MI_ERR_CAPACITY, "%s: the want list buffer holds %llu rows, need %llu", who, (unsigned long long)cap,
+                    (unsigned long long)out.n_want);
+    return MI_OK;
+}
+
+}  // namespace mi
+
 extern "C" {
 
 int mi_packset_missing(const mi_packset* set, const uint8_t* digests, const uint32_t* lengths, uint64_t n, uint8_t* held,
@@ -325,33 +299,13 @@ int mi_packset_missing(const mi_packset* set, const uint8_t* digests, const uint
     if (n == 0) return MI_OK;
     HIPCHK(c, hipSetDevice(c->device));
     Request q;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{c->stream};   // (goes first: buffers and events after it)
+    StreamDrain drain{c->stream};   // (goes first: buffers and events after it)
     rc = resolve_and_plan(c, tags, slots, t_cap, digests, lengths, n, false, &q);
     if (rc) return rc;
     const u64* h = c->h_word.as<u64>();
     if (h[kTotBad] != kFetchNone) return refuse_row(c, who, q, h[kTotBad], digests, lengths);
-    mi_want_info out = {};
-    out.n_rows = n;
-    out.n_distinct = h[kTotFirst];
-    out.n_held = h[kTotHeld];
-    out.n_want = h[kTotEntries];
-    out.held_bytes = h[kTotHeldBytes];
-    out.want_bytes = h[kTotRaw];
-    if (out.n_held + out.n_want != out.n_distinct)
-        return fail(c, MI_ERR_HIP, "%s: the plan counted %llu held and %llu missing among %llu distinct digests", who,
-                    (unsigned long long)out.n_held, (unsigned long long)out.n_want, (unsigned long long)out.n_distinct);
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, q.ev[0], q.ev[1]));
-    out.ms_resolve = ms;
-    if (info) *info = out;
-    const bool fits = out.n_want <= cap;
-    if (held) HIPCHK(c, hipMemcpyAsync(held, q.held.p, n, hipMemcpyDeviceToHost, c->stream));
-    if (fits && out.n_want) HIPCHK(c, hipMemcpyAsync(want_rows, q.want.p, out.n_want * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (!fits && (cap || want_rows))
-        return fail(c, MI_ERR_CAPACITY, "%s: the want list buffer holds %llu rows, need %llu", who, (unsigned long long)cap,
-                    (unsigned long long)out.n_want);
-    return MI_OK;
+    return want_list_finish(c, who, n, h[kTotFirst], h[kTotHeld], h[kTotEntries], h[kTotHeldBytes], h[kTotRaw], q.ev[0], q.ev[1], q.held.p,
+                            q.want.p, held, want_rows, cap, info);
 }
 
 int mi_packset_pack(const mi_packset* set, const uint8_t* digests, const uint32_t* lengths, uint64_t n, uint32_t flags, mi_pack** out,
@@ -374,7 +328,7 @@ int mi_packset_pack(const mi_packset* set, const uint8_t* digests, const uint32_
     struct Owned { mi_pack* p = nullptr; ~Owned() { if (p) mi_pack_free(p); } } mine;   // (drains the ctx stream before the blob goes)
     Request q;
     DevBuf e_src, e_len, e_dst, d_rows, d_got;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    StreamDrain drain{s};   // (goes first: buffers and events after it)
     rc = resolve_and_plan(c, tags, slots, t_cap, digests, lengths, n, true, &q);
     if (rc) return rc;
     u64* h = c->h_word.as<u64>();
@@ -398,7 +352,7 @@ int mi_packset_pack(const mi_packset* set, const uint8_t* digests, const uint32_
     HIPCHK(c, e_dst.ensure(n_sel * 8));
     if (flags & MI_SUBPACK_VERIFY) HIPCHK(c, d_got.ensure(n_sel * 32));
     // plan, second half; the gather; the verification
-    hipLaunchKernelGGL(fetch_compact_entries_kernel, dim3((u32)q.nb), dim3(kFetchBlock), 0, s, q.dup.as<i64>(), q.held.as<u8>(),
+    hipLaunchKernelGGL(fetch_compact_entries_kernel, dim3((u32)q.nb), dim3(kPlanBlock), 0, s, q.dup.as<i64>(), q.held.as<u8>(),
                        q.src.as<u64>(), q.len64.as<u64>(), q.dig.as<u8>(), n, q.block_cnt, q.block_bytes, e_src.as<u64>(), e_len.as<u64>(),
                        e_dst.as<u64>(), d_rows.as<u64>());
     HIPCHK(c, hipEventRecord(q.ev[1], s));

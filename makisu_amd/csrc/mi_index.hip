@@ -322,15 +322,6 @@ int index_insert(mi_index* x, const u8* d_digests, const i64* d_dup_of, u64 n, u
 }
 
 // ---- query / prune / retain: the host side ------------------------------------------------------------------------------------
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_zprune.hip's alloc_exact); *tally += what was allocated
-hipError_t alloc_exact(DevBuf* b, u64 want, u64* tally) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; *tally += alloc; }
-    return e;
-}
-
 int does_not_fit(mi_ctx* c, const char* who, hipError_t e, const char* what, u64 bytes) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
@@ -341,12 +332,9 @@ int does_not_fit(mi_ctx* c, const char* who, hipError_t e, const char* what, u64
 
 #define INDEX_ALLOC(buf, want, what)                                                      \
     do {                                                                                  \
-        const hipError_t e_ = alloc_exact(&(buf), (want), &extra);                        \
+        const hipError_t e_ = (buf).alloc_exact((want), &extra);                        \
         if (e_ != hipSuccess) return does_not_fit(c, who, e_, (what), (want));            \
     } while (0)
-
-// the stream is idle before the locals declared in front of one of these go
-struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } };
 
 // held[r] for n digests on the device, by the table alone; *n_held = the rows held.  ONE synchronisation; the index is read only
 int index_lookup_rows(mi_index* x, const u8* d_digests, u64 n, u8* held_out, u64* n_held) {
@@ -358,7 +346,7 @@ int index_lookup_rows(mi_index* x, const u8* d_digests, u64 n, u8* held_out, u64
         return MI_OK;
     }
     DevBuf d_held, d_tot;
-    Drain drain{c->stream};
+    StreamDrain drain{c->stream};
     if (held_out) HIPCHK(c, d_held.ensure(n));
     HIPCHK(c, d_tot.ensure(64));
     HIPCHK(c, hipMemsetAsync(d_tot.p, 0, 64, c->stream));
@@ -393,7 +381,7 @@ int index_rebuild(mi_index* x, const char* who, const u64* state, const u8* dige
     fresh.ctx = c;
     DevBuf d_recs;
     Event ev[2];
-    Drain drain{st};
+    StreamDrain drain{st};
     for (auto& e : ev) HIPCHK(c, e.create());
     INDEX_ALLOC(fresh.state, new_cap * 8, "the new table's tags");
     INDEX_ALLOC(fresh.slots, new_cap * 32, "the new table's digests");
@@ -621,7 +609,7 @@ int mi_index_prune(mi_index* x, const uint8_t* digests, uint64_t n, uint32_t fla
     u64 extra = 0;                                           // what this call allocates, from the sizes
     DevBuf d_dig, d_mark, d_tot;
     Event ev[2];
-    Drain drain{st};
+    StreamDrain drain{st};
     for (auto& e : ev) HIPCHK(c, e.create());
     // ---- mark, count; synchronisation 1 -------------------------------------------------------------------------------------
     INDEX_ALLOC(d_dig, n * 32, "the request");
@@ -685,7 +673,7 @@ int mi_index_retain_zset(mi_index* x, const mi_zset* set, mi_index_prune_info* i
     u64 extra = 0;
     DevBuf d_exp, d_src, d_word, d_len64, d_flags, d_tot;
     Event ev[2];
-    Drain drain{st};
+    StreamDrain drain{st};
     for (auto& e : ev) HIPCHK(c, e.create());
     // ---- export, the set's lookup, the flags, count; synchronisation 1 ----------------------------------------------------------
     INDEX_ALLOC(d_exp, count * 32, "the exported digests");

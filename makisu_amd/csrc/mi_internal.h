@@ -44,9 +44,26 @@ struct DevBuf {
         if (e == hipSuccess) bytes = alloc;
         return e;
     }
+    // exactly `want` bytes rounded up to 256, plus the 256 bytes of slack -- no eighth on top: a blob or a scratch whose size
+    // is known does not grow.  What the buffer held goes only when the new memory is there; *tally += what was allocated
+    hipError_t alloc_exact(u64 want, u64* tally = nullptr) {
+        const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
+        void* q = nullptr;
+        const hipError_t e = dev_alloc(&q, alloc);
+        if (e != hipSuccess) return e;
+        release();
+        p = q;
+        bytes = alloc;
+        if (tally) *tally += alloc;
+        return e;
+    }
     void release() { if (p) (void)dev_free(p); p = nullptr; bytes = 0; }
     template <typename T> T* as() const { return (T*)p; }
 };
+
+// The stream is idle before the locals declared IN FRONT of one of these go: device buffers and events of a call that returns
+// early are not freed under work that is still queued
+struct StreamDrain { hipStream_t st; ~StreamDrain() { (void)hipStreamSynchronize(st); } };
 
 // Pinned host memory, a stream and an event with owners, under DevBuf's rule: whoever deletes the owning object has made its
 // device current and synchronised its streams.  An object that holds a stream AND events recorded on it or pinned memory it
@@ -131,6 +148,14 @@ struct PartRec {
 // sets the ctx's (or, for c == nullptr, the create-time) error message; returns code
 int fail(mi_ctx* c, int code, const char* fmt, ...);
 std::string ctx_error(mi_ctx* c);      // a copy of the ctx's message, taken under the lock every writer holds
+
+// mi_fetch.hip: what mi_packset_missing and mi_zset_missing do once the plan's totals lie on the host and no row was refused.
+// Fills mi_want_info from the six values, holds held + want against distinct, takes ms_resolve from the two events, copies the
+// held flags (d_held, n of them) and -- if they fit `cap` -- the want rows (d_want) out on the ctx stream and waits; a list
+// that does not fit is refused when the caller gave a buffer at all
+int want_list_finish(mi_ctx* c, const char* who, u64 n, u64 n_distinct, u64 n_held, u64 n_want, u64 held_bytes, u64 want_bytes,
+                     hipEvent_t ev0, hipEvent_t ev1, const void* d_held, const void* d_want, uint8_t* held, uint64_t* want_rows,
+                     uint64_t cap, mi_want_info* info);
 
 // mi_group.hip: what each mi_batch_* entry point of that name does for a GROUP HEAD (h->group set) instead
 struct Group;

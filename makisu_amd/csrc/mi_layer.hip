@@ -931,12 +931,6 @@ int mi_cache_key(const char* cache_id, char* out, uint64_t cap) {
     return MI_OK;
 }
 
-static void hex32(const uint8_t* d, char* out) {
-    static const char* x = "0123456789abcdef";
-    for (int i = 0; i < 32; ++i) { out[2 * i] = x[d[i] >> 4]; out[2 * i + 1] = x[d[i] & 15]; }
-    out[64] = 0;
-}
-
 int mi_cache_create_entry(const uint8_t* tar_sha256, const uint8_t* gzip_sha256, char* out, uint64_t cap) {
     if (!out) return MI_ERR_INVALID;
     if (!tar_sha256 && !gzip_sha256) {                          // createEntry(nil): the step made no layer
@@ -946,9 +940,7 @@ int mi_cache_create_entry(const uint8_t* tar_sha256, const uint8_t* gzip_sha256,
     }
     if (!tar_sha256 || !gzip_sha256) return MI_ERR_INVALID;
     if (cap < 130) return MI_ERR_CAPACITY;
-    hex32(tar_sha256, out);
-    out[64] = ',';
-    hex32(gzip_sha256, out + 65);
+    snprintf(out, 130, "%s,%s", mi::hex32(tar_sha256).c_str(), mi::hex32(gzip_sha256).c_str());
     return MI_OK;
 }
 

@@ -4,7 +4,19 @@
 #pragma once
 #include "../../include/makisu_mi.h"
 
+#include <string>
+
 #define MI_LOCAL __attribute__((visibility("hidden")))
+
+namespace mi {
+// 32 bytes as 64 lower-case hex digits: a digest in a message, the halves of a cache entry
+inline std::string hex32(const uint8_t* d) {
+    static const char* dig = "0123456789abcdef";
+    std::string out(64, '0');
+    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
+    return out;
+}
+}  // namespace mi
 
 extern "C" {
 // mi_api.hip (what reads staged bytes back -- _read_file_landed, _read_stats, _chunk_sum, the windows, _explain_chunk: mi_readback.hip)

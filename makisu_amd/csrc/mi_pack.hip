@@ -2,9 +2,8 @@
 // (mi_batch_pack_chunks and the mi_pack_* calls of include/makisu_mi.h).  What a chunk-addressed store takes in for a layer:
 // the bytes of the chunks no earlier layer held, every chunk on a 16-byte offset, the pad behind it zero, addressed by digest.
 //
-//   plan      the selection flags and chunk_len through an exclusive scan of the ROUNDED-UP lengths of the selected rows
-//             (the scheme of tables.hip's launch_scan_counts: block sums, one block over the sums, the final pass), the final
-//             pass compacting into per-entry arrays: source arena offset, length, blob offset, and the mi_pack_entry row;
+//   plan      mi_plan.h's three launches over the selection flags and the ROUNDED-UP lengths of the selected rows; per entry:
+//             source arena offset, length, blob offset, and the mi_pack_entry row;
 //   gather    destination-driven: the blob is cut into tiles of kPackTile bytes, a workgroup takes a tile, so the length
 //             distribution of the chunks cannot unbalance the launch (one 64 KiB chunk and 1 024 chunks of 16 bytes are the
 //             same work).  The entries that reach into a tile are found by a search over the entries' blob offsets, 64 probes
@@ -19,7 +18,7 @@
 // chunk (len = 1 mod 16), inside the arena's 4 KiB slack.  The hashing of the verify pass reads up to 67 bytes behind the blob's
 // last entry: the blob is allocated with the 256 bytes every DevBuf has behind it.
 #include "mi_internal.h"
-#include "mi_wave.h"
+#include "mi_plan.h"
 #include "host_blake2s.h"
 #include "host_sha256.h"
 
@@ -34,41 +33,26 @@ namespace mi {
 
 constexpr u64 kNoRow = ~0ull;
 // ---- plan ------------------------------------------------------------------------------------------------------------
-constexpr int kPlanBlock = 256;
-constexpr int kPlanPer   = 8;                       // rows per thread
-constexpr int kPlanTile  = kPlanBlock * kPlanPer;   // 2048 rows per block
-constexpr int kEntryWords = sizeof(mi_pack_entry) / 8;
-static_assert(sizeof(mi_pack_entry) == 56 && kEntryWords == 7, "mi_pack_entry is seven 8-byte words");
-
-// per block of kPlanTile rows: how many are selected, and their rounded-up bytes; totals[2] += their bytes as they are.
-// Three sums, nothing else: a reduction per wave, the four waves' results through LDS, one barrier.
+// per block of kPlanTile rows: how many are selected, and their rounded-up bytes; totals[2] += their bytes as they are
 __global__ __launch_bounds__(kPlanBlock)
 void pack_block_sums_kernel(const u8* __restrict__ select, const u64* __restrict__ chunk_len, u64 n,
                             u64* __restrict__ block_cnt, u64* __restrict__ block_bytes, u64* __restrict__ totals) {
     __shared__ u64 lds[3][kPlanBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
-    u64 cnt = 0, bytes = 0, raw = 0;
+    u64 v[3] = {0, 0, 0};                             // entries, their rounded-up bytes, their bytes
 #pragma unroll
     for (int k = 0; k < kPlanPer; ++k)
         if (base + k < n && (!select || select[base + k])) {
             const u64 len = chunk_len[base + k];
-            ++cnt;
-            bytes += round16(len);
-            raw += len;
+            ++v[0];
+            v[1] += round16(len);
+            v[2] += len;
         }
-    cnt = wave_sum(cnt);
-    bytes = wave_sum(bytes);
-    raw = wave_sum(raw);
-    if (lane == 0) { lds[0][wave] = cnt; lds[1][wave] = bytes; lds[2][wave] = raw; }
-    __syncthreads();
+    plan_block_sum<3>(v, lds);
     if (threadIdx.x == 0) {
-        u64 t_cnt = 0, t_bytes = 0, t_raw = 0;
-#pragma unroll
-        for (int w = 0; w < kPlanBlock / 64; ++w) { t_cnt += lds[0][w]; t_bytes += lds[1][w]; t_raw += lds[2][w]; }
-        block_cnt[blockIdx.x] = t_cnt;
-        block_bytes[blockIdx.x] = t_bytes;
-        if (t_raw) atomicAdd((unsigned long long*)&totals[2], (unsigned long long)t_raw);
+        block_cnt[blockIdx.x] = v[0];
+        block_bytes[blockIdx.x] = v[1];
+        if (v[2]) atomicAdd((unsigned long long*)&totals[2], (unsigned long long)v[2]);
     }
 }
 
@@ -76,19 +60,7 @@ void pack_block_sums_kernel(const u8* __restrict__ select, const u64* __restrict
 __global__ __launch_bounds__(kPlanBlock)
 void pack_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ block_bytes, u64 n_blocks,
                                u64* __restrict__ totals) {
-    __shared__ u64 lds[4];
-    u64 carry_c = 0, carry_b = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kPlanBlock) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
-        u64 tc, tb;
-        const u64 ec = block_exclusive_scan_u64<kPlanBlock>(vc, &tc, lds);
-        const u64 eb = block_exclusive_scan_u64<kPlanBlock>(vb, &tb, lds);
-        if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
-        carry_c += tc;
-        carry_b += tb;
-    }
-    if (threadIdx.x == 0) { totals[0] = carry_c; totals[1] = carry_b; }
+    plan_block_offsets<true>(block_cnt, block_bytes, n_blocks, &totals[0], &totals[1]);
 }
 
 // the selected rows, in row order, as entries: where the chunk lies in the arena, its length, where it goes in the blob, and
@@ -98,7 +70,6 @@ void pack_compact_kernel(const u8* __restrict__ select, const u64* __restrict__ 
                          const u8* __restrict__ digests, u64 n, const u64* __restrict__ block_cnt,
                          const u64* __restrict__ block_bytes, u64* __restrict__ e_src, u64* __restrict__ e_len,
                          u64* __restrict__ e_dst, u64* __restrict__ rows) {
-    __shared__ u64 lds[4];
     const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 len[kPlanPer];
     u64 cnt = 0, bytes = 0;
@@ -108,9 +79,8 @@ void pack_compact_kernel(const u8* __restrict__ select, const u64* __restrict__ 
         len[k] = sel ? chunk_len[base + k] : kNoRow;
         if (sel) { ++cnt; bytes += round16(len[k]); }
     }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kPlanBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = block_exclusive_scan_u64<kPlanBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = plan_first(cnt, block_cnt);
+    u64 dst = plan_first(bytes, block_bytes);
 #pragma unroll
     for (int k = 0; k < kPlanPer; ++k) {
         if (len[k] == kNoRow) continue;
@@ -118,12 +88,7 @@ void pack_compact_kernel(const u8* __restrict__ select, const u64* __restrict__ 
         e_src[at] = chunk_off[row];
         e_len[at] = len[k];
         e_dst[at] = dst;
-        const u64* d = (const u64*)(digests + 32 * row);
-        u64* r = rows + kEntryWords * at;
-        r[0] = d[0]; r[1] = d[1]; r[2] = d[2]; r[3] = d[3];
-        r[4] = dst;
-        r[5] = row;
-        r[6] = len[k] & 0xFFFFFFFFull;                 // length | reserved = 0
+        put_entry_row(rows + kEntryWords * at, digests + 32 * row, dst, row, len[k] & 0xFFFFFFFFull);   // length | reserved = 0
         ++at;
         dst += round16(len[k]);
     }
@@ -199,9 +164,7 @@ __global__ __launch_bounds__(256)
 void pack_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ rows, u64 n, u64* __restrict__ first_bad) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* g = (const u64*)(got + 32 * k);
-    const u64* w = rows + kEntryWords * k;
-    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+    digest_differs_mark(got, rows + kEntryWords * k, k, first_bad);
 }
 
 // ---- mi_pack_read: the blob through two pinned windows, the copy of one overlapping the consumption of the other (the
@@ -292,15 +255,6 @@ struct mi_pack {
 
 namespace {
 
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (no eighth on top: a blob does not grow)
-hipError_t alloc_exact(DevBuf* b, u64 want) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
-    return e;
-}
-
 void pack_delete(mi_pack* p) {
     mi_ctx* c = p->ctx;
     (void)hipSetDevice(c->device);
@@ -379,7 +333,7 @@ int mi_batch_pack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select, 
     p->info.chunk_bytes = h[2];
     const u64 blob_bytes = h[1];
     // the blob: device memory of its own.  Does not fit: MI_ERR_NOMEM, nothing else has changed
-    if ((e = alloc_exact(&p->blob, blob_bytes)) != hipSuccess) {
+    if ((e = p->blob.alloc_exact(blob_bytes)) != hipSuccess) {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
         (void)hipGetLastError();
@@ -389,7 +343,7 @@ int mi_batch_pack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select, 
         pack_delete(p);
         return rc;
     }
-    if ((e = alloc_exact(&d_rows, n_sel * sizeof(mi_pack_entry))) != hipSuccess || (e = e_src.ensure(n_sel * 8)) != hipSuccess ||
+    if ((e = d_rows.alloc_exact(n_sel * sizeof(mi_pack_entry))) != hipSuccess || (e = e_src.ensure(n_sel * 8)) != hipSuccess ||
         (e = e_len.ensure(n_sel * 8)) != hipSuccess || (e = e_dst.ensure(n_sel * 8)) != hipSuccess ||
         ((flags & MI_PACK_VERIFY) && (e = d_got.ensure(n_sel * 32)) != hipSuccess))
         return hip_failed("entry arrays");
@@ -471,7 +425,7 @@ int mi_pack_alloc(mi_ctx* c, const char* who, uint64_t n_entries, uint64_t blob_
     p->info.n_entries = n_entries;
     p->info.blob_bytes = blob_bytes;
     p->info.chunk_bytes = chunk_bytes;
-    const hipError_t e = alloc_exact(&p->blob, blob_bytes);
+    const hipError_t e = p->blob.alloc_exact(blob_bytes);
     if (e != hipSuccess) {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);

@@ -38,6 +38,7 @@
 // structural check (offset + round16(length) <= blob_bytes, always, on the host) is what makes the entry's address a bound.
 // The hashing of the set's verify pass reads up to 67 bytes behind the blob's last entry (the same slack), that of the recipes'
 // up to 67 bytes behind the last restored file (the arena's 4 KiB).
+#include "mi_plan.h"
 #include "mi_slot_table.h"
 
 #include <string.h>
@@ -52,9 +53,6 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kNone = ~0ull;
-
-constexpr int kEntryWords = sizeof(mi_pack_entry) / 8;      // digest 4 | offset | chunk_index | length, reserved
-static_assert(sizeof(mi_pack_entry) == 56 && kEntryWords == 7, "mi_pack_entry is seven 8-byte words");
 
 // ---- the set: entries -> table records, the verification, the table ------------------------------------------------------
 // entries as they were uploaded -> what the table takes (digest | base + offset | length) and what the hashing launcher takes
@@ -234,7 +232,7 @@ __global__ __launch_bounds__(256)
 void restore_compare_kernel(const u8* __restrict__ got, const u8* __restrict__ want, u64 n, u64* __restrict__ first_bad) {
     const u64 r = (u64)blockIdx.x * 256 + threadIdx.x;
     if (r >= n) return;
-    if (!digest_eq32(got + 32 * r, want + 32 * r)) atomicMin((unsigned long long*)first_bad, (unsigned long long)r);
+    digest_differs_mark(got, (const u64*)(want + 32 * r), r, first_bad);
 }
 
 // ---- mi_packset_add_blob's way up: two pinned windows, one filled by the host while the other's copy runs ------------------
@@ -298,15 +296,6 @@ double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
 
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_pack.hip's scheme: a blob does not grow)
-hipError_t alloc_exact(DevBuf* b, u64 want) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
-    return e;
-}
-
 int set_state(const mi_packset* s, const char* who) {
     if (s->broken.empty()) return MI_OK;
     return fail(s->ctx, MI_ERR_STATE, "%s: the pack set is unusable since: %s", who, s->broken.c_str());
@@ -338,7 +327,7 @@ int set_add(mi_packset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const
     hipStream_t st = c->stream;
     DevBuf mine = std::move(blob);                     // freed on every early return -- after the stream has drained
     DevBuf d_ent, d_recs, d_off, d_len, d_got;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    StreamDrain drain{st};   // (goes first: the buffers above after it)
     s->info.ms_verify = s->info.ms_insert = 0;
     if (n == 0) {                                      // a pack of nothing
         ++s->info.n_packs;
@@ -444,7 +433,7 @@ int mi_packset_add_blob(mi_packset* s, const void* blob, uint64_t blob_bytes, co
     s->info.ms_upload = 0;
     DevBuf d_blob;
     if (blob_bytes && n) {
-        const hipError_t e = alloc_exact(&d_blob, blob_bytes);
+        const hipError_t e = d_blob.alloc_exact(blob_bytes);
         if (e != hipSuccess) return blob_does_not_fit(c, "mi_packset_add_blob", e, blob_bytes, n);
         const auto t0 = std::chrono::steady_clock::now();
         rc = s->up.upload(c, d_blob.as<u8>(), blob, blob_bytes);
@@ -474,7 +463,7 @@ int mi_packset_add_pack(mi_packset* s, const mi_pack* p, uint32_t flags) {
     s->info.ms_upload = 0;
     DevBuf d_blob;
     if (blob_bytes && n) {
-        const hipError_t e = alloc_exact(&d_blob, blob_bytes);
+        const hipError_t e = d_blob.alloc_exact(blob_bytes);
         if (e != hipSuccess) return blob_does_not_fit(c, "mi_packset_add_pack", e, blob_bytes, n);
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t ce = hipMemcpyAsync(d_blob.p, src, blob_bytes, hipMemcpyDeviceToDevice, c->stream);
@@ -586,7 +575,7 @@ int mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t n_files, c
         hipStream_t s = c->stream;
         DevBuf d_dig, d_len32, d_dst, d_src, d_len64, d_found, d_cell, d_got;
         Event ev[4];
-        struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+        StreamDrain drain{s};   // (goes first: buffers and events after it)
         for (auto& e : ev) HIPCHK(c, e.create());
         HIPCHK(c, d_dig.ensure(n_rows * 32));
         HIPCHK(c, d_len32.ensure(n_rows * 4));
@@ -617,12 +606,6 @@ int mi_batch_add_recipes(mi_batch* b, const mi_packset* set, uint64_t n_files, c
             while (f + 1 < n_files && row >= first + n_chunks[f]) first += n_chunks[f++];
             *file = f;
             *in_file = row - first;
-        };
-        auto hex32 = [](const uint8_t* d) {
-            static const char* dig = "0123456789abcdef";
-            std::string out(64, '0');
-            for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
-            return out;
         };
         if (h[0] != kNone) {
             const u64 bad = h[0];

@@ -1,8 +1,9 @@
 // mi_wave.h -- the device primitives the chunk store's files share (mi_pack, mi_fetch, mi_restore, mi_zpack, mi_zset, mi_zbatch,
 // mi_zprune, mi_index): the block scan and the wave's sum of 64-bit values, the wave's search over an ascending array, the
 // digest compare and the table's tag, 16-byte loads from an absolute device address, and the masking of an entry's last unit.
-// Every one is forced inline: a kernel compiles as it did with the function in its own file.  tables.hip keeps its own scan
-// (another LDS contract), the two hashing kernels share mi_item_loads.h, whose load types these functions use.
+// Every one is forced inline: a kernel compiles as it did with the function in its own file.  Its siblings: mi_plan.h (the
+// plan's three launches over these primitives), mi_zrows.h (a coded zpack's rows), mi_gather.h (the tile gather).  tables.hip
+// keeps its own scan (another LDS contract), the two hashing kernels share mi_item_loads.h, whose load types these functions use.
 #pragma once
 
 #include "mi_common.h"

@@ -5,14 +5,13 @@
 // (mi_lz4_wave_enc.h), so the zpack is byte for byte what mi_batch_pack_chunks + mi_pack_compress gives for the same selection --
 // without the plain blob, its gather and its hashing pass.
 //
-//   plan      the selection flags go up; mi_pack.hip's three launches (block sums over 2 048 rows, one block over the sums, the
-//             compacting pass) over the WORST-CASE spans z_worst_span(length) of the selected rows: per entry the 56-byte row
-//             (digest | the chunk's ARENA OFFSET | the batch row | length), its scratch offset, its arena offset and its length;
-//   encode    one wave an entry, the workgroup is the wave, grid-stride: z_encode_block(arena + chunk_off, length, scratch +
-//             w_off, ...) -- the coder reads the chunk where it lies, at whatever byte alignment it has;
-//   layout    the same three launches over round16(stored) with the totals (stored bytes, raw entries); the placing pass gives
-//             every entry its blob offset and its gather source as an ABSOLUTE device address: a coded entry's scratch span
-//             (16-byte aligned), a raw entry's chunk in the arena (ANY alignment);
+//   plan      the selection flags go up; mi_plan.h's three launches over the WORST-CASE spans z_worst_span(length) of the
+//             selected rows: per entry the 56-byte row (digest | the chunk's ARENA OFFSET | the batch row | length), its scratch
+//             offset, its arena offset and its length;
+//   encode    mi_zrows.h's loop with the arena as its base: the coder reads the chunk where it lies, at whatever byte
+//             alignment it has;
+//   layout    mi_zrows.h's, with the totals (stored bytes, raw entries): a coded entry's gather source is its scratch span
+//             (16-byte aligned), a raw entry's its chunk in the arena (ANY alignment);
 //   gather    destination-driven, 16 KiB tiles, one wave searching the entries' offsets (mi_pack.hip's scheme).  Sources of
 //             either kind lie side by side in a tile: every lane's 16-byte unit is ONE global_load_dwordx4 at whatever alignment
 //             its source has, the bytes at and beyond `stored` are zeroed in registers, one aligned 16-byte store writes the
@@ -21,7 +20,7 @@
 //             them: same stream), hashed there by the ctx's launcher (pass kShaBlobs), held against THE BATCH'S OWN digest table at
 //             chunk_index: one decode and one hashing pass vouch for both hops, arena -> stored form -> plain again;
 //   missing   mi_fetch.hip's want list over zset_lookup_kernel's answer: held flags and the rows that state another length than
-//             the set's, first occurrences by the engine's dedup marking, the scan, the want rows ascending.
+//             the set's, first occurrences by the engine's dedup marking, the plan, want_list_finish.
 //
 // BOUNDS.  The encoder READS inside the chunk only: positions <= length - 12 read 4 bytes, match bytes lie below length - 5,
 // literals below length; it WRITES below the entry's worst-case span (checked per sequence).  The gather READS 16 bytes at
@@ -33,7 +32,7 @@
 #include "mi_internal.h"
 #include "mi_gather.h"
 #include "mi_lz4_wave.h"
-#include "mi_lz4_wave_enc.h"
+#include "mi_zrows.h"
 
 #include <string.h>
 
@@ -45,54 +44,28 @@ using namespace mi;
 namespace mi {
 
 constexpr u64 kBNone = ~0ull;
-constexpr int kBEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
-static_assert(sizeof(mi_zpack_entry) == 56 && kBEntryWords == 7, "mi_zpack_entry is seven 8-byte words");
-
-constexpr int kBBlock = 256;
-constexpr int kBPer   = 8;                            // rows per thread
-constexpr int kBTile  = kBBlock * kBPer;              // 2048 rows per block
 // the totals of mi_batch_zpack_chunks ...
 enum : int { kBTotEntries = 0, kBTotSpan = 1, kBTotChunk = 2, kBTotBlob = 3, kBTotStored = 4, kBTotRaw = 5, kBTotBad = 6, kBTotDiffer = 7 };
 // ... and of mi_zset_missing (kMTotLookup: where zset_lookup_kernel notes the rows the set lacks -- not read)
 enum : int { kMTotWant = 0, kMTotWantBytes = 2, kMTotFirst = 3, kMTotHeld = 4, kMTotHeldBytes = 5, kMTotBad = 6, kMTotLookup = 7 };
 
-// the block's sums of Q values a thread: the four waves' results through LDS, in thread 0 (one barrier)
-template <int Q>
-static __device__ __forceinline__ void zbatch_block_sum(u64 (&v)[Q], u64 (*lds)[kBBlock / 64]) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int q = 0; q < Q; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) lds[q][wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            v[q] = 0;
-#pragma unroll
-            for (int w = 0; w < kBBlock / 64; ++w) v[q] += lds[q][w];
-        }
-    }
-}
-
-// ---- plan: mi_pack.hip's scan over the worst-case spans of the selected rows ----------------------------------------------------
-// per block of kBTile rows: how many are selected and their worst-case spans; totals[kBTotChunk] += their bytes as they are
-__global__ __launch_bounds__(kBBlock)
+// ---- plan: mi_plan.h's over the worst-case spans of the selected rows -------------------------------------------------------------
+// per block of kPlanTile rows: how many are selected and their worst-case spans; totals[kBTotChunk] += their bytes as they are
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_plan_sums_kernel(const u8* __restrict__ select, const u64* __restrict__ chunk_len, u64 n, u64* __restrict__ block_cnt,
                              u64* __restrict__ block_span, u64* __restrict__ totals) {
-    __shared__ u64 lds[3][kBBlock / 64];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
+    __shared__ u64 lds[3][kPlanBlock / 64];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 v[3] = {0, 0, 0};                             // entries, worst-case spans, chunk bytes
 #pragma unroll
-    for (int k = 0; k < kBPer; ++k)
+    for (int k = 0; k < kPlanPer; ++k)
         if (base + k < n && (!select || select[base + k])) {
             const u64 len = chunk_len[base + k];
             ++v[0];
             v[1] += z_worst_span(len);
             v[2] += len;
         }
-    zbatch_block_sum<3>(v, lds);
+    plan_block_sum<3>(v, lds);
     if (threadIdx.x == 0) {
         block_cnt[blockIdx.x] = v[0];
         block_span[blockIdx.x] = v[1];
@@ -101,59 +74,36 @@ void zbatch_plan_sums_kernel(const u8* __restrict__ select, const u64* __restric
 }
 
 // single block: exclusive scan of one or two block arrays in place (block_b may be NULL); totals[ia], totals[ib] = their sums
-__global__ __launch_bounds__(kBBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_block_offsets_kernel(u64* __restrict__ block_a, u64* __restrict__ block_b, u64 n_blocks, u64* __restrict__ totals, int ia, int ib) {
-    __shared__ u64 lds[4];
-    u64 carry_a = 0, carry_b = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kBBlock) {
-        const u64 i = b0 + threadIdx.x;
-        u64 t;
-        const u64 ea = block_exclusive_scan_u64<kBBlock>(i < n_blocks ? block_a[i] : 0, &t, lds);
-        if (i < n_blocks) block_a[i] = carry_a + ea;
-        carry_a += t;
-        if (block_b) {
-            const u64 eb = block_exclusive_scan_u64<kBBlock>(i < n_blocks ? block_b[i] : 0, &t, lds);
-            if (i < n_blocks) block_b[i] = carry_b + eb;
-            carry_b += t;
-        }
-    }
-    if (threadIdx.x == 0) {
-        totals[ia] = carry_a;
-        if (block_b) totals[ib] = carry_b;
-    }
+    if (block_b) plan_block_offsets<true>(block_a, block_b, n_blocks, &totals[ia], &totals[ib]);
+    else plan_block_offsets<false>(block_a, nullptr, n_blocks, &totals[ia], nullptr);      // (ib is not read: callers pass ia again)
 }
 
 // the selected rows, in row order, as entries: the row (digest | the chunk's ARENA OFFSET | the batch row | length; the layout
 // turns the offset word into the blob's), where its worst-case span begins in the scratch, and -- for the error message and the
 // hashing launcher, which outlive the offset word -- the arena offset and the length once more
-__global__ __launch_bounds__(kBBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_compact_kernel(const u8* __restrict__ select, const u64* __restrict__ chunk_off, const u64* __restrict__ chunk_len,
                            const u8* __restrict__ digests, u64 n, const u64* __restrict__ block_cnt, const u64* __restrict__ block_span,
                            u64* __restrict__ rows, u64* __restrict__ w_off, u64* __restrict__ a_off, u64* __restrict__ p_len) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
-    u64 len[kBPer];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
+    u64 len[kPlanPer];
     u64 cnt = 0, span = 0;
 #pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const bool sel = base + k < n && (!select || select[base + k]);
         len[k] = sel ? chunk_len[base + k] : kBNone;
         if (sel) { ++cnt; span += z_worst_span(len[k]); }
     }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kBBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 w = block_exclusive_scan_u64<kBBlock>(span, &t, lds) + block_span[blockIdx.x];
+    u64 at = plan_first(cnt, block_cnt);
+    u64 w = plan_first(span, block_span);
 #pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         if (len[k] == kBNone) continue;
         const u64 row = base + k;
         const u64 off = chunk_off[row];
-        const u64* d = (const u64*)(digests + 32 * row);
-        u64* r = rows + kBEntryWords * at;
-        r[0] = d[0]; r[1] = d[1]; r[2] = d[2]; r[3] = d[3];
-        r[4] = off;
-        r[5] = row;
-        r[6] = len[k] & 0xFFFFFFFFull;                 // length | stored: the coder's
+        put_entry_row(rows + kEntryWords * at, digests + 32 * row, off, row, len[k] & 0xFFFFFFFFull);   // length | stored: the coder's
         w_off[at] = w;
         a_off[at] = off;
         p_len[at] = len[k];
@@ -163,72 +113,23 @@ void zbatch_compact_kernel(const u8* __restrict__ select, const u64* __restrict_
 }
 
 // ---- encode: zpack_encode_kernel with the arena as its input --------------------------------------------------------------------
-// rows[k]: digest | the chunk's arena offset | the batch row | length (the high half is written here: stored)
 __global__ __launch_bounds__(64)
 void zbatch_encode_kernel(const u8* __restrict__ arena, u64* __restrict__ rows, const u64* __restrict__ w_off, u8* __restrict__ scratch, u64 n) {
     __shared__ u32 table[kZTable];
-    const int lane = threadIdx.x;
-    for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
-        const u64* r = rows + kBEntryWords * k;
-        const u32 len = (u32)r[6];
-        const u32 stored = z_encode_block(arena + r[4], len, scratch + w_off[k], z_worst_span(len), table, lane);
-        if (lane == 0) rows[kBEntryWords * k + 6] = (u64)len | ((u64)stored << 32);
-    }
+    z_encode_rows<ZLevel1>(arena, rows, w_off, scratch, n, table);
 }
 
-// ---- layout: the scan over round16(stored) -----------------------------------------------------------------------------------------
-// per block of kBTile entries: the rounded-up stored bytes; into the totals: stored bytes, raw entries
-__global__ __launch_bounds__(kBBlock)
+// ---- layout: mi_zrows.h's, over round16(stored) ----------------------------------------------------------------------------------
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_layout_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restrict__ block_bytes, u64* __restrict__ totals) {
-    __shared__ u64 lds[3][kBBlock / 64];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
-    u64 v[3] = {0, 0, 0};                             // rounded-up stored bytes, stored bytes, raw entries
-#pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
-        if (base + k >= n) continue;
-        const u64 w = rows[kBEntryWords * (base + k) + 6];
-        const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
-        v[0] += round16(stored);
-        v[1] += stored;
-        v[2] += stored == len ? 1 : 0;
-    }
-    zbatch_block_sum<3>(v, lds);
-    if (threadIdx.x == 0) {
-        block_bytes[blockIdx.x] = v[0];
-        if (v[1]) atomicAdd((unsigned long long*)&totals[kBTotStored], (unsigned long long)v[1]);
-        if (v[2]) atomicAdd((unsigned long long*)&totals[kBTotRaw], (unsigned long long)v[2]);
-    }
+    z_layout_sums<false>(rows, n, block_bytes, totals, kBTotStored, kBTotRaw, 0);
 }
 
-// every entry's place in the new blob, where its stored form lies now as an absolute device address (a raw chunk: in the arena, at
-// any alignment; a coded one: in its scratch span) and the row's offset word: from here on the rows are the zpack's entries
-__global__ __launch_bounds__(kBBlock)
+// a raw chunk lies in the arena, at any alignment
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, u64 n, const u64* __restrict__ block_bytes, u64 arena_base,
                          u64 scratch_base, u64* __restrict__ e_src, u64* __restrict__ e_len, u64* __restrict__ e_dst) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
-    u64 stored[kBPer], len[kBPer];
-    u64 bytes = 0;
-#pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
-        const u64 w = base + k < n ? rows[kBEntryWords * (base + k) + 6] : 0;
-        len[k] = w & 0xFFFFFFFFull;
-        stored[k] = w >> 32;
-        bytes += round16(stored[k]);
-    }
-    u64 t;
-    u64 dst = block_exclusive_scan_u64<kBBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
-        const u64 row = base + k;
-        if (row >= n) continue;
-        u64* r = rows + kBEntryWords * row;
-        e_src[row] = stored[k] == len[k] ? arena_base + r[4] : scratch_base + w_off[row];
-        e_len[row] = stored[k];
-        e_dst[row] = dst;
-        r[4] = dst;
-        dst += round16(stored[k]);
-    }
+    z_place(rows, w_off, n, block_bytes, arena_base, scratch_base, e_src, e_len, e_dst);
 }
 
 // ---- gather: mi_gather.h's tile body, sources of either kind at any alignment ------------------------------------------------------
@@ -245,9 +146,7 @@ void zbatch_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ r
                            u64* __restrict__ first_bad) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* g = (const u64*)(got + 32 * k);
-    const u64* w = (const u64*)(digests + 32 * rows[kBEntryWords * k + 5]);
-    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+    digest_differs_mark(got, (const u64*)(digests + 32 * rows[kEntryWords * k + 5]), k, first_bad);
 }
 
 // ---- mi_zset_missing: mi_fetch.hip's want list over zset_lookup_kernel's answer -------------------------------------------------
@@ -266,23 +165,23 @@ void zbatch_held_kernel(const u64* __restrict__ src, const u64* __restrict__ wor
     }
 }
 
-// per block of kBTile rows: the first occurrences the set lacks; into the totals: their STATED bytes (the set knows nothing of a
+// per block of kPlanTile rows: the first occurrences the set lacks; into the totals: their STATED bytes (the set knows nothing of a
 // chunk it lacks), the first occurrences, those of them the set holds, and their PLAIN bytes as the set states them
-__global__ __launch_bounds__(kBBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_want_sums_kernel(const i64* __restrict__ dup_of, const u8* __restrict__ held, const u64* __restrict__ len64,
                              const u32* __restrict__ stated, u64 n, u64* __restrict__ block_cnt, u64* __restrict__ totals) {
-    __shared__ u64 lds[5][kBBlock / 64];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
+    __shared__ u64 lds[5][kPlanBlock / 64];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 v[5] = {0, 0, 0, 0, 0};                       // wanted, their stated bytes, firsts, held firsts, their bytes
 #pragma unroll
-    for (int k = 0; k < kBPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const u64 row = base + k;
         if (row >= n || dup_of[row] >= 0) continue;
         ++v[2];
         if (held[row]) { ++v[3]; v[4] += len64[row]; }
         else { ++v[0]; v[1] += stated ? (u64)stated[row] : 0ull; }
     }
-    zbatch_block_sum<5>(v, lds);
+    plan_block_sum<5>(v, lds);
     if (threadIdx.x == 0) {
         block_cnt[blockIdx.x] = v[0];
         if (v[1]) atomicAdd((unsigned long long*)&totals[kMTotWantBytes], (unsigned long long)v[1]);
@@ -293,21 +192,10 @@ void zbatch_want_sums_kernel(const i64* __restrict__ dup_of, const u8* __restric
 }
 
 // the want list: the numbers of the rows at which a digest the set lacks occurs for the first time, ascending
-__global__ __launch_bounds__(kBBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zbatch_want_rows_kernel(const i64* __restrict__ dup_of, const u8* __restrict__ held, u64 n, const u64* __restrict__ block_cnt,
                              u64* __restrict__ want_rows) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kBTile + (u64)threadIdx.x * kBPer;
-    u32 sel = 0;
-    u64 cnt = 0;
-#pragma unroll
-    for (int k = 0; k < kBPer; ++k)
-        if (base + k < n && dup_of[base + k] < 0 && !held[base + k]) { sel |= 1u << k; ++cnt; }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kBBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kBPer; ++k)
-        if (sel & (1u << k)) want_rows[at++] = base + k;
+    want_rows_body([=](u64 row) { return dup_of[row] < 0 && !held[row]; }, n, block_cnt, want_rows);
 }
 
 }  // namespace mi
@@ -315,22 +203,6 @@ void zbatch_want_rows_kernel(const i64* __restrict__ dup_of, const u8* __restric
 namespace {
 
 constexpr u32 kEncodeWaves = 1u << 15;                // one wave an entry; more entries: the waves go round
-
-std::string hex32(const uint8_t* d) {
-    static const char* dig = "0123456789abcdef";
-    std::string out(64, '0');
-    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
-    return out;
-}
-
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_pack.hip's scheme: a scratch does not grow)
-hipError_t alloc_exact(DevBuf* b, u64 want) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
-    return e;
-}
 
 }  // namespace
 
@@ -364,10 +236,10 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
         return MI_OK;
     }
     hipStream_t s = c->stream;
-    const u64 nb = (n + kBTile - 1) / kBTile, nb_sel = (n_sel + kBTile - 1) / kBTile;
+    const u64 nb = (n + kPlanTile - 1) / kPlanTile, nb_sel = (n_sel + kPlanTile - 1) / kPlanTile;
     DevBuf d_sel, d_scan, d_rows, d_woff, d_aoff, d_plen, d_scratch, e_src, e_len, e_dst, d_rule, d_got;
     Event ev[10];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    StreamDrain drain{s};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
     // plan, first half: the entries and what their worst-case spans take
     HIPCHK(c, d_scan.ensure((2 * nb + 8) * 8));
@@ -379,9 +251,9 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     HIPCHK(c, hipMemsetAsync(totals, 0, 6 * 8, s));
     HIPCHK(c, hipMemsetAsync(totals + kBTotBad, 0xFF, 2 * 8, s));
     HIPCHK(c, hipEventRecord(ev[0], s));
-    hipLaunchKernelGGL(zbatch_plan_sums_kernel, dim3((u32)nb), dim3(kBBlock), 0, s, d_sel.as<u8>(), b->chunk_len.as<u64>(), n, block_cnt, block_span,
+    hipLaunchKernelGGL(zbatch_plan_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_sel.as<u8>(), b->chunk_len.as<u64>(), n, block_cnt, block_span,
                        totals);
-    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kBBlock), 0, s, block_cnt, block_span, nb, totals, (int)kBTotEntries,
+    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_cnt, block_span, nb, totals, (int)kBTotEntries,
                        (int)kBTotSpan);
     HIPCHK(c, hipEventRecord(ev[1], s));
     u64* h = c->h_word.as<u64>();
@@ -393,7 +265,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
         return fail(c, MI_ERR_HIP, "%s: the plan counted %llu entries with %llu chunk bytes in %llu bytes of scratch, the selection holds %llu", who,
                     (unsigned long long)h[kBTotEntries], (unsigned long long)chunk_bytes, (unsigned long long)scratch_bytes, (unsigned long long)n_sel);
     // the scratch.  Does not fit: MI_ERR_NOMEM, nothing has changed
-    hipError_t e = alloc_exact(&d_scratch, scratch_bytes);
+    hipError_t e = d_scratch.alloc_exact(scratch_bytes);
     if (e != hipSuccess) {
         size_t free_b = 0, total_b = 0;
         (void)hipMemGetInfo(&free_b, &total_b);
@@ -408,7 +280,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     HIPCHK(c, d_plen.ensure(n_sel * 8));
     // plan, second half; the coder; the layout's totals
     HIPCHK(c, hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(zbatch_compact_kernel, dim3((u32)nb), dim3(kBBlock), 0, s, d_sel.as<u8>(), b->chunk_off.as<u64>(), b->chunk_len.as<u64>(),
+    hipLaunchKernelGGL(zbatch_compact_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_sel.as<u8>(), b->chunk_off.as<u64>(), b->chunk_len.as<u64>(),
                        b->digests.as<u8>(), n, block_cnt, block_span, d_rows.as<u64>(), d_woff.as<u64>(), d_aoff.as<u64>(), d_plen.as<u64>());
     HIPCHK(c, hipEventRecord(ev[3], s));
     if (flags & MI_ZPACK_LEVEL2) {                         // the denser parse (mi_zpack2.hip): the same rows, spans and scratch
@@ -421,8 +293,8 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
     }
     HIPCHK(c, hipEventRecord(ev[4], s));
     u64* block_bytes = block_span;
-    hipLaunchKernelGGL(zbatch_layout_sums_kernel, dim3((u32)nb_sel), dim3(kBBlock), 0, s, d_rows.as<u64>(), n_sel, block_bytes, totals);
-    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kBBlock), 0, s, block_bytes, (u64*)nullptr, nb_sel, totals, (int)kBTotBlob,
+    hipLaunchKernelGGL(zbatch_layout_sums_kernel, dim3((u32)nb_sel), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), n_sel, block_bytes, totals);
+    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_bytes, (u64*)nullptr, nb_sel, totals, (int)kBTotBlob,
                        (int)kBTotBlob);
     HIPCHK(c, hipEventRecord(ev[5], s));
     HIPCHK(c, hipMemcpyAsync(h, totals, 6 * 8, hipMemcpyDeviceToHost, s));
@@ -444,7 +316,7 @@ int mi_batch_zpack_chunks(mi_batch* b, const uint8_t* select, uint64_t n_select,
         HIPCHK(c, d_got.ensure(n_sel * 32));
     }
     HIPCHK(c, hipEventRecord(ev[6], s));
-    hipLaunchKernelGGL(zbatch_place_kernel, dim3((u32)nb_sel), dim3(kBBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n_sel, block_bytes,
+    hipLaunchKernelGGL(zbatch_place_kernel, dim3((u32)nb_sel), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n_sel, block_bytes,
                        (u64)(size_t)b->arena.p, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
     hipLaunchKernelGGL(zbatch_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel, blob_bytes,
                        (u8*)d_blob);
@@ -518,9 +390,9 @@ int mi_zset_missing(const mi_zset* set, const uint8_t* digests, const uint32_t* 
     hipStream_t s = c->stream;
     DevBuf d_dig, d_len32, d_src, d_word, d_len64, d_held, d_dup, d_scan, d_want;
     Event ev[2];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    StreamDrain drain{s};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
-    const u64 nb = (n + kBTile - 1) / kBTile;
+    const u64 nb = (n + kPlanTile - 1) / kPlanTile;
     u64 dd_cap = 1024;
     while (dd_cap < 2 * n) dd_cap <<= 1;
     HIPCHK(c, d_dig.ensure(n * 32));
@@ -550,10 +422,10 @@ int mi_zset_missing(const mi_zset* set, const uint8_t* digests, const uint32_t* 
                        d_held.as<u8>(), totals + kMTotBad);
     launch_dedup_mark(d_dig.as<u8>(), n, nullptr, c->dd_table.as<u32>(), c->dd_slot.as<u32>(), dd_cap, d_dup.as<i64>(), c->dd_nuniq.as<u64>(),
                       true, s);
-    hipLaunchKernelGGL(zbatch_want_sums_kernel, dim3((u32)nb), dim3(kBBlock), 0, s, d_dup.as<i64>(), d_held.as<u8>(), d_len64.as<u64>(), stated, n,
+    hipLaunchKernelGGL(zbatch_want_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_dup.as<i64>(), d_held.as<u8>(), d_len64.as<u64>(), stated, n,
                        block_cnt, totals);
-    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kBBlock), 0, s, block_cnt, (u64*)nullptr, nb, totals, (int)kMTotWant, (int)kMTotWant);
-    hipLaunchKernelGGL(zbatch_want_rows_kernel, dim3((u32)nb), dim3(kBBlock), 0, s, d_dup.as<i64>(), d_held.as<u8>(), n, block_cnt, d_want.as<u64>());
+    hipLaunchKernelGGL(zbatch_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_cnt, (u64*)nullptr, nb, totals, (int)kMTotWant, (int)kMTotWant);
+    hipLaunchKernelGGL(zbatch_want_rows_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_dup.as<i64>(), d_held.as<u8>(), n, block_cnt, d_want.as<u64>());
     HIPCHK(c, hipEventRecord(ev[1], s));
     u64* h = c->h_word.as<u64>();
     HIPCHK(c, hipMemcpyAsync(h, totals, 8 * 8, hipMemcpyDeviceToHost, s));
@@ -567,28 +439,8 @@ int mi_zset_missing(const mi_zset* set, const uint8_t* digests, const uint32_t* 
         return fail(c, MI_ERR_INVALID, "%s: row %llu: the compressed pack set holds digest %s with %u bytes, the request states %u", who,
                     (unsigned long long)bad, hex32(digests + 32 * bad).c_str(), (u32)w, lengths ? lengths[bad] : 0u);
     }
-    mi_want_info got = {};
-    got.n_rows = n;
-    got.n_distinct = h[kMTotFirst];
-    got.n_held = h[kMTotHeld];
-    got.n_want = h[kMTotWant];
-    got.held_bytes = h[kMTotHeldBytes];
-    got.want_bytes = h[kMTotWantBytes];
-    if (got.n_held + got.n_want != got.n_distinct)
-        return fail(c, MI_ERR_HIP, "%s: the plan counted %llu held and %llu missing among %llu distinct digests", who, (unsigned long long)got.n_held,
-                    (unsigned long long)got.n_want, (unsigned long long)got.n_distinct);
-    float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
-    got.ms_resolve = ms;
-    if (info) *info = got;
-    const bool fits = got.n_want <= cap;
-    if (held) HIPCHK(c, hipMemcpyAsync(held, d_held.p, n, hipMemcpyDeviceToHost, s));
-    if (fits && got.n_want) HIPCHK(c, hipMemcpyAsync(want_rows, d_want.p, got.n_want * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(c, hipStreamSynchronize(s));
-    if (!fits && (cap || want_rows))
-        return fail(c, MI_ERR_CAPACITY, "%s: the want list buffer holds %llu rows, need %llu", who, (unsigned long long)cap,
-                    (unsigned long long)got.n_want);
-    return MI_OK;
+    return want_list_finish(c, who, n, h[kMTotFirst], h[kMTotHeld], h[kMTotWant], h[kMTotHeldBytes], h[kMTotWantBytes], ev[0], ev[1], d_held.p,
+                            d_want.p, held, want_rows, cap, info);
 }
 
 }  // extern "C"

@@ -14,10 +14,10 @@
 //             into the table.  Two lanes of a step in one slot: the greater position wins (atomicMax: the order the hardware
 //             writes LDS in does not show).  The block is kept if it is smaller than n - (n >> 4); chunks under 13 bytes are raw;
 //   layout    the wave writes into scratch at the chunk's WORST-CASE span (n + n / 255 + 16, rounded up to 16; the prefix sums
-//             are taken on the host, which has the pack's entries); the stored sizes are known only then: mi_pack.hip's three
-//             launches (block sums over 2 048 rows, one block over the sums, the placing pass) over round16(stored), and a
-//             destination-driven gather of 16 KiB tiles (mi_fetch.hip's, from absolute addresses: a raw chunk is gathered
-//             from the INPUT pack, a coded one from scratch) into a blob of exactly its size;
+//             are taken on the host, which has the pack's entries); the stored sizes are known only then: mi_zrows.h's layout
+//             (mi_plan.h's plan over round16(stored), the placing pass), and a destination-driven gather of 16 KiB tiles
+//             (mi_gather.h, from absolute addresses: a raw chunk is gathered from the INPUT pack, a coded one from scratch)
+//             into a blob of exactly its size;
 //   decode    one wave an entry.  A raw entry is a copy in 16-byte units.  An LZ entry's sequences are taken in order: token and
 //             offset are read by every lane alike, extension bytes 64 at a time with a ballot for the first below 255, the wave
 //             copies literals and match bytes.  A match is PERIODIC with its offset: byte i is the byte (i mod offset) behind
@@ -38,7 +38,7 @@
 #include "mi_internal.h"
 #include "mi_gather.h"
 #include "mi_lz4_wave.h"
-#include "mi_lz4_wave_enc.h"
+#include "mi_zrows.h"
 #include "host_blake2s.h"
 #include "host_lz4.h"
 #include "host_sha256.h"
@@ -56,113 +56,36 @@ namespace mi {
 constexpr u64 kZNone = ~0ull;
 // z_worst_span (what one chunk of n bytes takes in scratch): csrc/mi_lz4_wave_enc.h
 
-constexpr int kZEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
-static_assert(sizeof(mi_zpack_entry) == 56 && kZEntryWords == 7 && sizeof(mi_pack_entry) == 56, "mi_zpack_entry is seven 8-byte words");
-
 // ---- encode ---------------------------------------------------------------------------------------------------------------------
 // z_put_extension, z_encode_block: csrc/mi_lz4_wave_enc.h (mi_zbatch.hip codes with them too)
 // rows[k]: digest | the chunk's offset in the pack's blob | chunk_index | length (the high half is written here: stored)
 __global__ __launch_bounds__(64)
 void zpack_encode_kernel(const u8* __restrict__ blob, u64* __restrict__ rows, const u64* __restrict__ w_off, u8* __restrict__ scratch, u64 n) {
     __shared__ u32 table[kZTable];
-    const int lane = threadIdx.x;
-    for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
-        const u64* r = rows + kZEntryWords * k;
-        const u32 len = (u32)r[6];
-        const u32 stored = z_encode_block(blob + r[4], len, scratch + w_off[k], z_worst_span(len), table, lane);
-        if (lane == 0) rows[kZEntryWords * k + 6] = (u64)len | ((u64)stored << 32);
-    }
+    z_encode_rows<ZLevel1>(blob, rows, w_off, scratch, n, table);
 }
 
-// ---- layout: mi_pack.hip's scan over round16(stored) ---------------------------------------------------------------------------
-constexpr int kZBlock = 256;
-constexpr int kZPer   = 8;                            // rows per thread
-constexpr int kZTile  = kZBlock * kZPer;              // 2048 rows per block
+// ---- layout: mi_zrows.h's, over round16(stored) ----------------------------------------------------------------------------------
 enum : int { kZTotBlob = 0, kZTotStored = 1, kZTotRaw = 2, kZTotChunk = 3, kZTotBad = 4 };
 
-// per block of kZTile rows: the rounded-up stored bytes; into the totals: stored bytes, raw entries, chunk bytes
-__global__ __launch_bounds__(kZBlock)
+// per block of kPlanTile rows: the rounded-up stored bytes; into the totals: stored bytes, raw entries, chunk bytes
+__global__ __launch_bounds__(kPlanBlock)
 void zpack_block_sums_kernel(const u64* __restrict__ rows, u64 n, u64* __restrict__ block_bytes, u64* __restrict__ totals) {
-    __shared__ u64 lds[4][kZBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * kZTile + (u64)threadIdx.x * kZPer;
-    u64 v[4] = {0, 0, 0, 0};                          // rounded-up stored bytes, stored bytes, raw entries, chunk bytes
-#pragma unroll
-    for (int k = 0; k < kZPer; ++k) {
-        if (base + k >= n) continue;
-        const u64 w = rows[kZEntryWords * (base + k) + 6];
-        const u64 len = w & 0xFFFFFFFFull, stored = w >> 32;
-        v[0] += round16(stored);
-        v[1] += stored;
-        v[2] += stored == len ? 1 : 0;
-        v[3] += len;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) lds[q][wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        u64 t[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            t[q] = 0;
-#pragma unroll
-            for (int w = 0; w < kZBlock / 64; ++w) t[q] += lds[q][w];
-        }
-        block_bytes[blockIdx.x] = t[0];
-        if (t[1]) atomicAdd((unsigned long long*)&totals[kZTotStored], (unsigned long long)t[1]);
-        if (t[2]) atomicAdd((unsigned long long*)&totals[kZTotRaw], (unsigned long long)t[2]);
-        if (t[3]) atomicAdd((unsigned long long*)&totals[kZTotChunk], (unsigned long long)t[3]);
-    }
+    z_layout_sums<true>(rows, n, block_bytes, totals, kZTotStored, kZTotRaw, kZTotChunk);
 }
 
 // single block: exclusive scan of the block array in place; totals[kZTotBlob] = the blob's bytes
-__global__ __launch_bounds__(kZBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zpack_block_offsets_kernel(u64* __restrict__ block_bytes, u64 n_blocks, u64* __restrict__ totals) {
-    __shared__ u64 lds[4];
-    u64 carry = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kZBlock) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 v = i < n_blocks ? block_bytes[i] : 0;
-        u64 t;
-        const u64 e = block_exclusive_scan_u64<kZBlock>(v, &t, lds);
-        if (i < n_blocks) block_bytes[i] = carry + e;
-        carry += t;
-    }
-    if (threadIdx.x == 0) totals[kZTotBlob] = carry;
+    plan_block_offsets<false>(block_bytes, nullptr, n_blocks, &totals[kZTotBlob], nullptr);
 }
 
 // every entry's place in the new blob, where its stored form lies now (a raw chunk: in the input pack; a coded one: in its
 // scratch span) and the row's offset word: from here on the rows are the zpack's entries
-__global__ __launch_bounds__(kZBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zpack_place_kernel(u64* __restrict__ rows, const u64* __restrict__ w_off, u64 n, const u64* __restrict__ block_bytes, u64 pack_base,
                         u64 scratch_base, u64* __restrict__ e_src, u64* __restrict__ e_len, u64* __restrict__ e_dst) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kZTile + (u64)threadIdx.x * kZPer;
-    u64 stored[kZPer], len[kZPer];
-    u64 bytes = 0;
-#pragma unroll
-    for (int k = 0; k < kZPer; ++k) {
-        const u64 w = base + k < n ? rows[kZEntryWords * (base + k) + 6] : 0;
-        len[k] = w & 0xFFFFFFFFull;
-        stored[k] = w >> 32;
-        bytes += round16(stored[k]);
-    }
-    u64 t;
-    u64 dst = block_exclusive_scan_u64<kZBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
-#pragma unroll
-    for (int k = 0; k < kZPer; ++k) {
-        const u64 row = base + k;
-        if (row >= n) continue;
-        u64* r = rows + kZEntryWords * row;
-        e_src[row] = stored[k] == len[k] ? pack_base + r[4] : scratch_base + w_off[row];
-        e_len[row] = stored[k];
-        e_dst[row] = dst;
-        r[4] = dst;
-        dst += round16(stored[k]);
-    }
+    z_place(rows, w_off, n, block_bytes, pack_base, scratch_base, e_src, e_len, e_dst);
 }
 
 // ---- gather: mi_gather.h's tile body over aligned sources (a raw chunk in the input pack, a coded one in scratch) -------------
@@ -181,7 +104,7 @@ void zpack_decode_kernel(const u8* __restrict__ zblob, const u64* __restrict__ r
                          u32* __restrict__ rule_out, u64* __restrict__ first_bad) {
     const int lane = threadIdx.x;
     for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
-        const u64* r = rows + kZEntryWords * k;
+        const u64* r = rows + kEntryWords * k;
         const u8* src = zblob + r[4];
         const u64 len = r[6] & 0xFFFFFFFFull, stored = r[6] >> 32;
         u8* dst = out + p_off[k];
@@ -211,9 +134,7 @@ __global__ __launch_bounds__(256)
 void zpack_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ rows, u64 n, u64* __restrict__ first_bad) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* g = (const u64*)(got + 32 * k);
-    const u64* w = rows + kZEntryWords * k;
-    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+    digest_differs_mark(got, rows + kEntryWords * k, k, first_bad);
 }
 
 // ---- mi_zpack_read: mi_pack.hip's PackReader, restated -- the blob through two pinned windows, the copy of one overlapping the
@@ -303,22 +224,6 @@ struct mi_zpack {
 
 namespace {
 
-std::string hex32(const uint8_t* d) {
-    static const char* dig = "0123456789abcdef";
-    std::string out(64, '0');
-    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
-    return out;
-}
-
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_pack.hip's scheme: a blob does not grow)
-hipError_t alloc_exact(DevBuf* b, u64 want) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
-    return e;
-}
-
 int does_not_fit(mi_ctx* c, const char* who, const char* what, hipError_t e, u64 bytes, u64 n) {
     size_t free_b = 0, total_b = 0;
     (void)hipMemGetInfo(&free_b, &total_b);
@@ -377,7 +282,7 @@ int add_compressed(mi_packset* s, mi_ctx* c, const char* who, const u8* d_zblob,
                    double ms_upload, u64* first_bad) {
     std::vector<mi_pack_entry> plain(n);
     DevBuf d_plain;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{c->stream};   // (goes first: the buffer above after it)
+    StreamDrain drain{c->stream};   // (goes first: the buffer above after it)
     u64 plain_bytes = 0, bad = kZNone;
     u32 rule = 0;
     const int rc = mi_zpack_decode_plain(c, who, d_zblob, entries, n, &d_plain, &plain_bytes, plain.data(), &bad, &rule, nullptr);
@@ -416,8 +321,8 @@ int mi_zpack_decode_plain(mi_ctx* c, const char* who, const void* d_zblob, const
     *rule_out = 0;
     DevBuf d_rows, d_poff, d_rule, d_bad;
     Event ev[2];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
-    const hipError_t e = alloc_exact(d_plain, plain_bytes);
+    StreamDrain drain{st};   // (goes first: the buffers above after it)
+    const hipError_t e = d_plain->alloc_exact(plain_bytes);
     if (e != hipSuccess) return does_not_fit(c, who, "the plain blob", e, plain_bytes, n);
     for (auto& v : ev) HIPCHK(c, v.create());
     HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
@@ -464,7 +369,7 @@ int mi_zpack_alloc(mi_ctx* c, const char* who, uint64_t n_entries, uint64_t blob
     *out = nullptr;
     mi_zpack* z = zpack_new(c);
     z->h_rows.resize(n_entries);
-    const hipError_t e = n_entries ? alloc_exact(&z->blob, blob_bytes) : hipSuccess;
+    const hipError_t e = n_entries ? z->blob.alloc_exact(blob_bytes) : hipSuccess;
     if (e != hipSuccess) {
         zpack_delete(z);
         return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n_entries);
@@ -550,12 +455,12 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
         scratch_bytes += z_worst_span(len);
     }
     hipStream_t s = c->stream;
-    const u64 nb = (n + kZTile - 1) / kZTile;
+    const u64 nb = (n + kPlanTile - 1) / kPlanTile;
     DevBuf d_rows, d_woff, d_scratch, d_scan, e_src, e_len, e_dst, d_rule, d_got;
     Event ev[7];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    StreamDrain drain{s};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
-    hipError_t e = alloc_exact(&d_scratch, scratch_bytes);
+    hipError_t e = d_scratch.alloc_exact(scratch_bytes);
     if (e != hipSuccess) return does_not_fit(c, who, "the coder's scratch", e, scratch_bytes, n);
     HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
     HIPCHK(c, d_woff.ensure(n * 8));
@@ -575,8 +480,8 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
                            d_scratch.as<u8>(), n);
     }
     HIPCHK(c, hipEventRecord(ev[1], s));
-    hipLaunchKernelGGL(zpack_block_sums_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), n, block_bytes, totals);
-    hipLaunchKernelGGL(zpack_block_offsets_kernel, dim3(1), dim3(kZBlock), 0, s, block_bytes, nb, totals);
+    hipLaunchKernelGGL(zpack_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), n, block_bytes, totals);
+    hipLaunchKernelGGL(zpack_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_bytes, nb, totals);
     HIPCHK(c, hipEventRecord(ev[2], s));
     u64* h = c->h_word.as<u64>();
     HIPCHK(c, hipMemcpyAsync(h, totals, 4 * 8, hipMemcpyDeviceToHost, s));
@@ -595,7 +500,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
                     (unsigned long long)pi.chunk_bytes);
     const u64 n_tiles = (blob_bytes + kGatherTile - 1) / kGatherTile;
     if (n_tiles >> 31) return fail(c, MI_ERR_INVALID, "%s: a blob of %llu bytes is more than one launch covers", who, (unsigned long long)blob_bytes);
-    if ((e = alloc_exact(&mine.z->blob, blob_bytes)) != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
+    if ((e = mine.z->blob.alloc_exact(blob_bytes)) != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
     HIPCHK(c, e_src.ensure(n * 8));
     HIPCHK(c, e_len.ensure(n * 8));
     HIPCHK(c, e_dst.ensure(n * 8));
@@ -604,7 +509,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
         HIPCHK(c, d_got.ensure(n * 32));
     }
     HIPCHK(c, hipEventRecord(ev[3], s));
-    hipLaunchKernelGGL(zpack_place_kernel, dim3((u32)nb), dim3(kZBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n, block_bytes,
+    hipLaunchKernelGGL(zpack_place_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n, block_bytes,
                        (u64)(size_t)d_pack, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
     hipLaunchKernelGGL(zpack_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n, blob_bytes,
                        mine.z->blob.as<u8>());
@@ -705,7 +610,7 @@ int mi_packset_add_zblob(mi_packset* s, const void* blob, uint64_t blob_bytes, c
     HIPCHK(c, hipSetDevice(c->device));
     if (n == 0) return mi_packset_adopt(s, who, nullptr, 0, nullptr, 0, flags, 0, first_bad);
     DevBuf d_zblob;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{c->stream};
+    StreamDrain drain{c->stream};
     const hipError_t e = d_zblob.ensure(blob_bytes);
     if (e != hipSuccess) return does_not_fit(c, who, "the compressed blob", e, blob_bytes, n);
     double ms_upload = 0;

@@ -1,32 +1,22 @@
-// mi_zpack2.hip -- zpack LEVEL 2's encode kernel (MI_ZPACK_LEVEL2): z_encode_block_l2 (csrc/mi_lz4_wave_enc2.h) over
-// the rows of a plan, one wave an entry.  ONE kernel serves both producers, because their encode launches differ in nothing but
-// the base pointer: mi_pack_compress (mi_zpack.hip) hands it a plain pack's blob, mi_batch_zpack_chunks (mi_zbatch.hip) a
-// batch's arena.  Everything around the coder -- the plan, the layout's scan, the gather, MI_ZPACK_VERIFY -- is those files' own and
-// the same at either level; their level-1 kernels are not touched.  The kernel lives in a file of its own so that the two
-// files compile to what they compiled to before there was a level.
+// mi_zpack2.hip -- zpack LEVEL 2's encode kernel (MI_ZPACK_LEVEL2): z_encode_block_l2 (csrc/mi_lz4_wave_enc2.h) in
+// mi_zrows.h's loop over the rows.  ONE kernel serves both producers, because their encode launches differ in nothing but the
+// base pointer: mi_pack_compress (mi_zpack.hip) hands it a plain pack's blob, mi_batch_zpack_chunks (mi_zbatch.hip) a batch's
+// arena.  Everything around the coder is the same at either level.  The kernel lives in a file of its own because the resource
+// tests of those two files list their kernels by name.
 //
 // BOUNDS.  The coder's: mi_lz4_wave_enc2.h.  rows[k] and w_off[k] are read for k < n; the row's last word is written by lane 0.
 #include "mi_internal.h"
-#include "mi_lz4_wave_enc2.h"
+#include "mi_zrows.h"
 
 using namespace mi;
 
 namespace mi {
 
-constexpr int kZ2EntryWords = sizeof(mi_zpack_entry) / 8;     // digest 4 | offset | chunk_index | length, stored
-static_assert(sizeof(mi_zpack_entry) == 56 && kZ2EntryWords == 7, "mi_zpack_entry is seven 8-byte words");
-
 // rows[k]: digest | the chunk's offset from `base` | chunk_index | length (the high half is written here: stored)
 __global__ __launch_bounds__(64)
 void zencode_l2_kernel(const u8* __restrict__ base, u64* __restrict__ rows, const u64* __restrict__ w_off, u8* __restrict__ scratch, u64 n) {
     __shared__ u32 tables[2 * kZTable];                   // t4 | t8: 32 KiB a wave
-    const int lane = threadIdx.x;
-    for (u64 k = blockIdx.x; k < n; k += gridDim.x) {
-        const u64* r = rows + kZ2EntryWords * k;
-        const u32 len = (u32)r[6];
-        const u32 stored = z_encode_block_l2(base + r[4], len, scratch + w_off[k], z_worst_span(len), tables, tables + kZTable, lane);
-        if (lane == 0) rows[kZ2EntryWords * k + 6] = (u64)len | ((u64)stored << 32);
-    }
+    z_encode_rows<ZLevel2>(base, rows, w_off, scratch, n, tables);
 }
 
 }  // namespace mi

@@ -10,10 +10,9 @@
 //             through per-workgroup bins in LDS (the first 256 blobs; beyond: global atomics) and the totals (survivors,
 //             dropped digests, their stored and chunk bytes) through a workgroup sum -- one global atomic a workgroup and value.
 //             Synchronisation 1: the per-blob sums.  The host classifies: dead (no live bytes), sparse (under the threshold);
-//   plan      over the slots whose blob is sparse: mi_pack.hip's three launches -- block sums over 2 048 slots, one block over
-//             the sums, the compacting pass -- over round16(stored): where each span goes in the new blob, and the list of
-//             (source address, bytes, destination, slot) in slot order.  Synchronisation 2: the totals, before the blob is
-//             allocated;
+//   plan      over the slots whose blob is sparse: mi_plan.h's three launches over round16(stored): where each span goes in the
+//             new blob, and the list of (source address, bytes, destination, slot) in slot order.  Synchronisation 2: the
+//             totals, before the blob is allocated;
 //   move      zset_gather_kernel's form WITHOUT the masking: destination-driven, 16 KiB tiles, one wave searching the entries'
 //             offsets, every lane's units loaded before the first is stored.  Whole units, the pad as it was;
 //   repoint   the moved spans' new addresses into a per-slot array: THE OLD TABLE IS NEVER WRITTEN;
@@ -23,7 +22,7 @@
 //             correct form, and it shrinks the table.  Synchronisation 3 behind it; then the table is swapped, the dead and
 //             the compacted blobs are freed and the new blob joins the set.
 //
-// Everything is allocated before anything changes, by alloc_exact's scheme (the bytes rounded up to 256, plus 256), and the old
+// Everything is allocated before anything changes, by DevBuf::alloc_exact (the bytes rounded up to 256, plus 256), and the old
 // table and blobs go only when the new table is complete: whatever fails, the set is as it was.  Offsets and addresses are 64-bit.
 //
 // BOUNDS.  mark READS digests [0, 32 n), tags / slots [0, cap) (the walk is masked), WRITES mark [0, cap).  sweep READS tags,
@@ -34,6 +33,7 @@
 // the source blob by the structural check of every add (offset + round16(stored) <= blob_bytes), to its last byte when the span
 // ends on the blob's last unit -- and WRITES aligned units inside [0, moved_bytes) of the new blob.  repoint WRITES new_addr at
 // slots the plan listed (< cap).  export READS slot_blob, slots, new_addr [0, cap), WRITES records [0, limit) (the cursor is checked).
+#include "mi_plan.h"
 #include "mi_zset_local.h"
 
 using namespace mi;
@@ -45,9 +45,7 @@ constexpr u32 kPNoBlob = 0xFFFFFFFFu;                 // slot_blob: an empty slo
 enum : u8 { kPStay = 0, kPCompact = 1, kPDead = 2 };  // a blob's fate
 enum : int { kPTotUnknown = 0, kPTotSurvive = 1, kPTotDropped = 2, kPTotDropStored = 3, kPTotDropChunk = 4, kPTotCursor = 6 };
 
-constexpr int kPBlock = 256;
-constexpr int kPPer   = 8;                            // slots per thread
-constexpr int kPTile  = kPBlock * kPPer;              // 2048 slots per block
+constexpr int kPWG    = 256;                          // the workgroup of the sweep, the move and the usage kernel
 constexpr int kPBins  = 256;                          // blobs with a bin in LDS
 
 // ---- mark ---------------------------------------------------------------------------------------------------------------------
@@ -69,17 +67,17 @@ void zprune_mark_kernel(const u8* __restrict__ digests, u64 n, const u64* __rest
 // ---- sweep --------------------------------------------------------------------------------------------------------------------
 // slot_blob[s] = the blob (its place among the sorted bases) a SURVIVING slot points into, kPNoBlob for an empty slot and for a
 // victim; live[b] += round16(stored) of the survivors; the totals: survivors, victims, the victims' stored and chunk bytes
-__global__ __launch_bounds__(kPBlock)
+__global__ __launch_bounds__(kPWG)
 void zprune_sweep_kernel(const u64* __restrict__ tags, const u64* __restrict__ slots, u64 cap, const u8* __restrict__ mark, u32 keep,
                          const u64* __restrict__ bases, u32 n_blobs, u32* __restrict__ slot_blob, u64* __restrict__ live,
                          u64* __restrict__ totals) {
     __shared__ unsigned long long bins[kPBins];
-    __shared__ u64 lds[4][kPBlock / 64];
+    __shared__ u64 lds[4][kPWG / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < kPBins; i += kPBlock) bins[i] = 0;
+    for (int i = threadIdx.x; i < kPBins; i += kPWG) bins[i] = 0;
     __syncthreads();
     u64 v[4] = {0, 0, 0, 0};                          // survivors, victims, the victims' stored bytes, their chunk bytes
-    for (u64 s = (u64)blockIdx.x * kPBlock + threadIdx.x; s < cap; s += (u64)gridDim.x * kPBlock) {
+    for (u64 s = (u64)blockIdx.x * kPWG + threadIdx.x; s < cap; s += (u64)gridDim.x * kPWG) {
         u32 b = kPNoBlob;
         if (tags[s] != 0ull) {
             const u64 word = slots[kSlotWords * s + 5];
@@ -111,89 +109,67 @@ void zprune_sweep_kernel(const u64* __restrict__ tags, const u64* __restrict__ s
     }
     __syncthreads();
     const u32 n_bins = n_blobs < (u32)kPBins ? n_blobs : (u32)kPBins;
-    for (u32 i = threadIdx.x; i < n_bins; i += kPBlock)
+    for (u32 i = threadIdx.x; i < n_bins; i += kPWG)
         if (bins[i]) atomicAdd((unsigned long long*)&live[i], bins[i]);
     if (threadIdx.x < 4) {
         u64 t = 0;
 #pragma unroll
-        for (int w = 0; w < kPBlock / 64; ++w) t += lds[threadIdx.x][w];
+        for (int w = 0; w < kPWG / 64; ++w) t += lds[threadIdx.x][w];
         if (t) atomicAdd((unsigned long long*)&totals[kPTotSurvive + threadIdx.x], (unsigned long long)t);
     }
 }
 
-// ---- plan: mi_pack.hip's scan over round16(stored) of the survivors of the blobs to be compacted --------------------------------
+// ---- plan: mi_plan.h's over round16(stored) of the survivors of the blobs to be compacted, a slot a row ------------------------
 static __device__ __forceinline__ bool zprune_moves(const u32* __restrict__ slot_blob, const u8* __restrict__ cls, u64 s, u64 cap) {
     if (s >= cap) return false;
     const u32 b = slot_blob[s];
     return b != kPNoBlob && cls[b] == kPCompact;
 }
 
-__global__ __launch_bounds__(kPBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zprune_block_sums_kernel(const u32* __restrict__ slot_blob, const u8* __restrict__ cls, const u64* __restrict__ slots, u64 cap,
                               u64* __restrict__ block_cnt, u64* __restrict__ block_bytes) {
-    __shared__ u64 lds[2][kPBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * kPTile + (u64)threadIdx.x * kPPer;
+    __shared__ u64 lds[2][kPlanBlock / 64];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 v[2] = {0, 0};                                // spans, their rounded-up stored bytes
 #pragma unroll
-    for (int k = 0; k < kPPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         if (!zprune_moves(slot_blob, cls, base + k, cap)) continue;
         ++v[0];
         v[1] += round16(slots[kSlotWords * (base + k) + 5] >> 32);
     }
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) lds[q][wave] = v[q];
-    }
-    __syncthreads();
-    if (threadIdx.x < 2) {
-        u64 t = 0;
-#pragma unroll
-        for (int w = 0; w < kPBlock / 64; ++w) t += lds[threadIdx.x][w];
-        (threadIdx.x == 0 ? block_cnt : block_bytes)[blockIdx.x] = t;
+    plan_block_sum<2>(v, lds);
+    if (threadIdx.x == 0) {
+        block_cnt[blockIdx.x] = v[0];
+        block_bytes[blockIdx.x] = v[1];
     }
 }
 
 // single block: exclusive scan of both block arrays in place; totals[0] = the spans, totals[1] = the new blob's bytes
-__global__ __launch_bounds__(kPBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zprune_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ block_bytes, u64 n_blocks, u64* __restrict__ totals) {
-    __shared__ u64 lds[4];
-    u64 carry_c = 0, carry_b = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kPBlock) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
-        u64 tc, tb;
-        const u64 ec = block_exclusive_scan_u64<kPBlock>(vc, &tc, lds);
-        const u64 eb = block_exclusive_scan_u64<kPBlock>(vb, &tb, lds);
-        if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
-        carry_c += tc;
-        carry_b += tb;
-    }
-    if (threadIdx.x == 0) { totals[0] = carry_c; totals[1] = carry_b; }
+    plan_block_offsets<true>(block_cnt, block_bytes, n_blocks, &totals[0], &totals[1]);
 }
 
 // the move list, in slot order: where the span lies, its bytes (round16(stored): whole units), where it goes, whose it is
-__global__ __launch_bounds__(kPBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zprune_compact_kernel(const u32* __restrict__ slot_blob, const u8* __restrict__ cls, const u64* __restrict__ slots, u64 cap,
                            const u64* __restrict__ block_cnt, const u64* __restrict__ block_bytes, u64* __restrict__ e_src,
                            u64* __restrict__ e_len, u64* __restrict__ e_dst, u64* __restrict__ e_slot) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kPTile + (u64)threadIdx.x * kPPer;
-    u64 len[kPPer];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
+    u64 len[kPlanPer];
     u32 sel = 0;
     u64 cnt = 0, bytes = 0;
 #pragma unroll
-    for (int k = 0; k < kPPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const bool m = zprune_moves(slot_blob, cls, base + k, cap);
         len[k] = m ? round16(slots[kSlotWords * (base + k) + 5] >> 32) : 0;
         if (m) { sel |= 1u << k; ++cnt; bytes += len[k]; }
     }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kPBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = block_exclusive_scan_u64<kPBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = plan_first(cnt, block_cnt);
+    u64 dst = plan_first(bytes, block_bytes);
 #pragma unroll
-    for (int k = 0; k < kPPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         if (!(sel & (1u << k))) continue;
         e_src[at] = slots[kSlotWords * (base + k) + 4];
         e_len[at] = len[k];
@@ -205,7 +181,6 @@ void zprune_compact_kernel(const u32* __restrict__ slot_blob, const u8* __restri
 }
 
 // ---- move: the gather of mi_gather.h WITHOUT the masking, the lengths clamped to the tile: a kernel of its own ----------------
-constexpr int kPWG = 256;
 constexpr u32 kPGatherTile = 16384;                   // bytes of the blob a workgroup writes
 constexpr u32 kPUnits = kPGatherTile / 16;            // ... in 16-byte units: a span takes at least one, so at most as many spans
 constexpr int kPUnitsPer = kPUnits / kPWG;            // units per lane
@@ -294,12 +269,12 @@ void zprune_export_kernel(const u32* __restrict__ slot_blob, const u64* __restri
 }
 
 // ---- usage: the sum of round16(stored) over the occupied slots --------------------------------------------------------------------
-__global__ __launch_bounds__(kPBlock)
+__global__ __launch_bounds__(kPWG)
 void zprune_live_kernel(const u64* __restrict__ tags, const u64* __restrict__ slots, u64 cap, u64* __restrict__ total) {
-    __shared__ u64 lds[kPBlock / 64];
+    __shared__ u64 lds[kPWG / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     u64 v = 0;
-    for (u64 s = (u64)blockIdx.x * kPBlock + threadIdx.x; s < cap; s += (u64)gridDim.x * kPBlock)
+    for (u64 s = (u64)blockIdx.x * kPWG + threadIdx.x; s < cap; s += (u64)gridDim.x * kPWG)
         if (tags[s] != 0ull) v += round16(slots[kSlotWords * s + 5] >> 32);
     v = wave_sum(v);
     if (lane == 0) lds[wave] = v;
@@ -307,7 +282,7 @@ void zprune_live_kernel(const u64* __restrict__ tags, const u64* __restrict__ sl
     if (threadIdx.x == 0) {
         u64 t = 0;
 #pragma unroll
-        for (int w = 0; w < kPBlock / 64; ++w) t += lds[w];
+        for (int w = 0; w < kPWG / 64; ++w) t += lds[w];
         if (t) atomicAdd((unsigned long long*)total, (unsigned long long)t);
     }
 }
@@ -315,15 +290,6 @@ void zprune_live_kernel(const u64* __restrict__ tags, const u64* __restrict__ sl
 }  // namespace mi
 
 namespace {
-
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_zset.hip's alloc_exact); *tally += what was allocated
-hipError_t alloc_exact(DevBuf* b, u64 want, u64* tally) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; *tally += alloc; }
-    return e;
-}
 
 int does_not_fit(mi_ctx* c, const char* who, hipError_t e, const char* what, u64 bytes) {
     size_t free_b = 0, total_b = 0;
@@ -335,7 +301,7 @@ int does_not_fit(mi_ctx* c, const char* who, hipError_t e, const char* what, u64
 
 #define PRUNE_ALLOC(buf, want, what)                                                      \
     do {                                                                                  \
-        const hipError_t e_ = alloc_exact(&(buf), (want), &extra);                        \
+        const hipError_t e_ = (buf).alloc_exact((want), &extra);                        \
         if (e_ != hipSuccess) return does_not_fit(c, who, e_, (what), (want));            \
     } while (0)
 
@@ -366,7 +332,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     SlotTable fresh;                                           // the table the survivors go into: this call's, scratch and all
     fresh.sum_bytes = true;                                    // (as the set's own inserts run)
     Event ev[8];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: buffers and events after it)
+    StreamDrain drain{st};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
 
     // the blobs by base address: what a span's address is searched in
@@ -394,8 +360,8 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     if (n)
         hipLaunchKernelGGL(zprune_mark_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_dig.as<u8>(), n, s->table.tags.as<u64>(),
                            s->table.slots.as<u64>(), cap - 1, d_mark.as<u8>(), tot);
-    const u32 sweep_grid = (u32)std::min<u64>((cap + kPBlock - 1) / kPBlock, 2048);
-    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPBlock), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, d_mark.as<u8>(),
+    const u32 sweep_grid = (u32)std::min<u64>((cap + kPWG - 1) / kPWG, 2048);
+    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPWG), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, d_mark.as<u8>(),
                        flags == MI_ZSET_PRUNE_KEEP ? 1u : 0u, d_bases.as<u64>(), (u32)n_blobs, d_slot_blob.as<u32>(), d_live.as<u64>(), tot);
     HIPCHK(c, hipEventRecord(ev[1], st));
     HIPCHK(c, hipMemcpyAsync(h, tot, 40, hipMemcpyDeviceToHost, st));
@@ -430,7 +396,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     }
 
     // ---- plan; synchronisation 2 ------------------------------------------------------------------------------------------------
-    const u64 nb = (cap + kPTile - 1) / kPTile;
+    const u64 nb = (cap + kPlanTile - 1) / kPlanTile;
     u64 n_move = 0, moved_bytes = 0;
     u64* block_cnt = nullptr;
     u64* block_bytes = nullptr;
@@ -443,9 +409,9 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         u64* totals = block_bytes + nb;
         HIPCHK(c, hipEventRecord(ev[2], st));
         HIPCHK(c, hipMemcpyAsync(d_cls.p, cls.data(), n_blobs, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(),
+        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(),
                            cap, block_cnt, block_bytes);
-        hipLaunchKernelGGL(zprune_block_offsets_kernel, dim3(1), dim3(kPBlock), 0, st, block_cnt, block_bytes, nb, totals);
+        hipLaunchKernelGGL(zprune_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, st, block_cnt, block_bytes, nb, totals);
         HIPCHK(c, hipEventRecord(ev[3], st));
         HIPCHK(c, hipMemcpyAsync(h, totals, 16, hipMemcpyDeviceToHost, st));
         HIPCHK(c, hipStreamSynchronize(st));
@@ -460,7 +426,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
                         (unsigned long long)n_move, (unsigned long long)moved_bytes, (unsigned long long)want_bytes, (unsigned long long)n_sparse);
         if ((moved_bytes + kPGatherTile - 1) / kPGatherTile >> 31)
             return fail(c, MI_ERR_INVALID, "%s: a compaction blob of %llu bytes is more than one launch covers", who, (unsigned long long)moved_bytes);
-        const hipError_t e = alloc_exact(&new_blob, moved_bytes, &extra);
+        const hipError_t e = new_blob.alloc_exact(moved_bytes, &extra);
         if (e == hipErrorOutOfMemory) {                        // not an error: the dead blobs still go, the sparse ones stay
             (void)hipGetLastError();
             pi.n_blobs_sparse_kept = n_sparse;
@@ -496,7 +462,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         const u64 n_tiles = (moved_bytes + kPGatherTile - 1) / kPGatherTile;
         HIPCHK(c, hipEventRecord(ev[4], st));
         HIPCHK(c, hipMemsetAsync(d_new_addr.p, 0, cap * 8, st));
-        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(), cap,
+        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(), cap,
                            block_cnt, block_bytes, e_src, e_len, e_dst, e_slot);
         hipLaunchKernelGGL(zprune_gather_kernel, dim3((u32)n_tiles), dim3(kPWG), 0, st, e_src, e_len, e_dst, n_move, moved_bytes, new_blob.as<u8>());
         hipLaunchKernelGGL(zprune_repoint_kernel, dim3((u32)((n_move + 255) / 256)), dim3(256), 0, st, e_slot, e_dst, n_move,
@@ -564,11 +530,11 @@ int mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out) {
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf d_total;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffer above after it)
+    StreamDrain drain{st};   // (goes first: the buffer above after it)
     HIPCHK(c, d_total.ensure(8));
     HIPCHK(c, hipMemsetAsync(d_total.p, 0, 8, st));
-    const u32 grid = (u32)std::min<u64>((s->table.cap + kPBlock - 1) / kPBlock, 2048);
-    hipLaunchKernelGGL(zprune_live_kernel, dim3(grid), dim3(kPBlock), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), s->table.cap, d_total.as<u64>());
+    const u32 grid = (u32)std::min<u64>((s->table.cap + kPWG - 1) / kPWG, 2048);
+    hipLaunchKernelGGL(zprune_live_kernel, dim3(grid), dim3(kPWG), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), s->table.cap, d_total.as<u64>());
     HIPCHK(c, hipMemcpyAsync(c->h_word.p, d_total.p, 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());

@@ -9,9 +9,9 @@
 //             wins); the same digest with another LENGTH makes the set unusable.  Rebuilt at twice the size when it passes half full;
 //   verify    MI_ZSET_VERIFY / MI_ZPACK_VERIFY: the blob decoded by mi_zpack.hip's decode kernel into a scratch laid out as a
 //             plain pack (mi_zpack_decode_plain), hashed by the ctx's launcher (pass kShaBlobs), held against the entries;
-//   cut       mi_fetch.hip's plan: lookup (slot_table_find: tag first, then all 32 bytes), first occurrences by the engine's dedup
-//             marking, three launches of a scan over round16(stored) that carries the totals (entries, stored bytes, raw
-//             entries, chunk bytes), the entries' compaction, and the 16 KiB-tile gather (mi_gather.h) from absolute
+//   cut       mi_fetch.hip's scheme: lookup (slot_table_find: tag first, then all 32 bytes), first occurrences by the engine's
+//             dedup marking, mi_plan.h's plan over round16(stored) with the totals (entries, stored bytes, raw entries, chunk
+//             bytes), and the 16 KiB-tile gather (mi_gather.h) from absolute
 //             16-byte-aligned sources, the bytes at and beyond `stored` zeroed in registers.  One synchronisation: the totals,
 //             before the blob is allocated.  Every offset is 64-bit;
 //   restore   zset_restore_kernel: ONE WAVE A RECIPE ROW (the workgroup is the wave, grid-stride, at most 65 536 waves).  A coded
@@ -29,6 +29,7 @@
 // verify pass reads up to 67 bytes behind the last string: a scratch's 256 bytes of slack, the arena's 4 KiB.
 #include "mi_gather.h"
 #include "mi_lz4_wave.h"
+#include "mi_plan.h"
 #include "mi_zset_local.h"
 
 #include <string.h>
@@ -44,15 +45,12 @@ namespace mi {
 
 constexpr u64 kQNone = ~0ull;
 
-constexpr int kQEntryWords = sizeof(mi_zpack_entry) / 8;      // digest 4 | offset | chunk_index | length, stored
-static_assert(sizeof(mi_zpack_entry) == 56 && kQEntryWords == 7, "mi_zpack_entry is seven 8-byte words");
-
 // ---- the set: entries -> the table's records (the table itself: mi_slot_table.hip) -------------------------------------------
 __global__ __launch_bounds__(256)
 void zset_unpack_kernel(const u64* __restrict__ entries, u64 n, u64 base, u64* __restrict__ recs) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* e = entries + kQEntryWords * k;
+    const u64* e = entries + kEntryWords * k;
     u64* r = recs + kSlotWords * k;
     r[0] = e[0]; r[1] = e[1]; r[2] = e[2]; r[3] = e[3];
     r[4] = base + e[4];
@@ -86,23 +84,19 @@ void zset_lookup_kernel(const u8* __restrict__ digests, const u32* __restrict__ 
     if (bad) atomicMin((unsigned long long*)first_bad, (unsigned long long)r);
 }
 
-// ---- plan: mi_pack.hip's scan over round16(stored) of the first occurrences -----------------------------------------------
-constexpr int kQBlock = 256;
-constexpr int kQPer   = 8;                            // rows per thread
-constexpr int kQTile  = kQBlock * kQPer;              // 2048 rows per block
+// ---- plan: mi_plan.h's over round16(stored) of the first occurrences ---------------------------------------------------------
 enum : int { kQTotEntries = 0, kQTotBlob = 1, kQTotStored = 2, kQTotRaw = 3, kQTotChunk = 4, kQTotBad = 6, kQTotDiffer = 7 };
 
-// per block of kQTile rows: the first occurrences and their rounded-up stored bytes; into the totals: stored bytes, raw
+// per block of kPlanTile rows: the first occurrences and their rounded-up stored bytes; into the totals: stored bytes, raw
 // entries, chunk bytes
-__global__ __launch_bounds__(kQBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zset_block_sums_kernel(const i64* __restrict__ dup_of, const u64* __restrict__ word, u64 n, u64* __restrict__ block_cnt,
                             u64* __restrict__ block_bytes, u64* __restrict__ totals) {
-    __shared__ u64 lds[5][kQBlock / 64];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    const u64 base = (u64)blockIdx.x * kQTile + (u64)threadIdx.x * kQPer;
+    __shared__ u64 lds[5][kPlanBlock / 64];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
     u64 v[5] = {0, 0, 0, 0, 0};                       // entries, rounded-up stored bytes, stored bytes, raw entries, chunk bytes
 #pragma unroll
-    for (int k = 0; k < kQPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const u64 row = base + k;
         if (row >= n || dup_of[row] >= 0) continue;
         const u64 w = word[row];
@@ -113,81 +107,50 @@ void zset_block_sums_kernel(const i64* __restrict__ dup_of, const u64* __restric
         v[3] += stored == len ? 1 : 0;
         v[4] += len;
     }
-#pragma unroll
-    for (int q = 0; q < 5; ++q) {
-        v[q] = wave_sum(v[q]);
-        if (lane == 0) lds[q][wave] = v[q];
-    }
-    __syncthreads();
+    plan_block_sum<5>(v, lds);
     if (threadIdx.x == 0) {
-        u64 t[5];
-#pragma unroll
-        for (int q = 0; q < 5; ++q) {
-            t[q] = 0;
-#pragma unroll
-            for (int w = 0; w < kQBlock / 64; ++w) t[q] += lds[q][w];
-        }
-        block_cnt[blockIdx.x] = t[0];
-        block_bytes[blockIdx.x] = t[1];
-        if (t[2]) atomicAdd((unsigned long long*)&totals[kQTotStored], (unsigned long long)t[2]);
-        if (t[3]) atomicAdd((unsigned long long*)&totals[kQTotRaw], (unsigned long long)t[3]);
-        if (t[4]) atomicAdd((unsigned long long*)&totals[kQTotChunk], (unsigned long long)t[4]);
+        block_cnt[blockIdx.x] = v[0];
+        block_bytes[blockIdx.x] = v[1];
+        if (v[2]) atomicAdd((unsigned long long*)&totals[kQTotStored], (unsigned long long)v[2]);
+        if (v[3]) atomicAdd((unsigned long long*)&totals[kQTotRaw], (unsigned long long)v[3]);
+        if (v[4]) atomicAdd((unsigned long long*)&totals[kQTotChunk], (unsigned long long)v[4]);
     }
 }
 
 // single block: exclusive scan of both block arrays in place; the totals: entries, the blob's bytes
-__global__ __launch_bounds__(kQBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zset_block_offsets_kernel(u64* __restrict__ block_cnt, u64* __restrict__ block_bytes, u64 n_blocks, u64* __restrict__ totals) {
-    __shared__ u64 lds[4];
-    u64 carry_c = 0, carry_b = 0;
-    for (u64 b0 = 0; b0 < n_blocks; b0 += kQBlock) {
-        const u64 i = b0 + threadIdx.x;
-        const u64 vc = i < n_blocks ? block_cnt[i] : 0, vb = i < n_blocks ? block_bytes[i] : 0;
-        u64 tc, tb;
-        const u64 ec = block_exclusive_scan_u64<kQBlock>(vc, &tc, lds);
-        const u64 eb = block_exclusive_scan_u64<kQBlock>(vb, &tb, lds);
-        if (i < n_blocks) { block_cnt[i] = carry_c + ec; block_bytes[i] = carry_b + eb; }
-        carry_c += tc;
-        carry_b += tb;
-    }
-    if (threadIdx.x == 0) { totals[kQTotEntries] = carry_c; totals[kQTotBlob] = carry_b; }
+    plan_block_offsets<true>(block_cnt, block_bytes, n_blocks, &totals[kQTotEntries], &totals[kQTotBlob]);
 }
 
 // the new zpack's entries, in order of first occurrence: where the stored span lies, its stored size, where it goes in the blob,
 // and the mi_zpack_entry row (digest | offset | chunk_index = the request row | length, stored)
-__global__ __launch_bounds__(kQBlock)
+__global__ __launch_bounds__(kPlanBlock)
 void zset_compact_entries_kernel(const i64* __restrict__ dup_of, const u64* __restrict__ src, const u64* __restrict__ word,
                                  const u8* __restrict__ digests, u64 n, const u64* __restrict__ block_cnt,
                                  const u64* __restrict__ block_bytes, u64* __restrict__ e_src, u64* __restrict__ e_len,
                                  u64* __restrict__ e_dst, u64* __restrict__ rows) {
-    __shared__ u64 lds[4];
-    const u64 base = (u64)blockIdx.x * kQTile + (u64)threadIdx.x * kQPer;
-    u64 w[kQPer];
+    const u64 base = (u64)blockIdx.x * kPlanTile + (u64)threadIdx.x * kPlanPer;
+    u64 w[kPlanPer];
     u32 sel = 0;
     u64 cnt = 0, bytes = 0;
 #pragma unroll
-    for (int k = 0; k < kQPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         const bool s = base + k < n && dup_of[base + k] < 0;
         w[k] = s ? word[base + k] : 0;
         if (s) { sel |= 1u << k; ++cnt; bytes += round16(w[k] >> 32); }
     }
-    u64 t;
-    u64 at = block_exclusive_scan_u64<kQBlock>(cnt, &t, lds) + block_cnt[blockIdx.x];
-    u64 dst = block_exclusive_scan_u64<kQBlock>(bytes, &t, lds) + block_bytes[blockIdx.x];
+    u64 at = plan_first(cnt, block_cnt);
+    u64 dst = plan_first(bytes, block_bytes);
 #pragma unroll
-    for (int k = 0; k < kQPer; ++k) {
+    for (int k = 0; k < kPlanPer; ++k) {
         if (!(sel & (1u << k))) continue;
         const u64 row = base + k;
         const u64 stored = w[k] >> 32;
         e_src[at] = src[row];
         e_len[at] = stored;
         e_dst[at] = dst;
-        const u64* d = (const u64*)(digests + 32 * row);
-        u64* r = rows + kQEntryWords * at;
-        r[0] = d[0]; r[1] = d[1]; r[2] = d[2]; r[3] = d[3];
-        r[4] = dst;
-        r[5] = row;
-        r[6] = w[k];
+        put_entry_row(rows + kEntryWords * at, digests + 32 * row, dst, row, w[k]);
         ++at;
         dst += round16(stored);
     }
@@ -244,9 +207,7 @@ __global__ __launch_bounds__(256)
 void zset_compare_kernel(const u8* __restrict__ got, const u64* __restrict__ want, u32 stride, u64 n, u64* __restrict__ first_bad) {
     const u64 k = (u64)blockIdx.x * 256 + threadIdx.x;
     if (k >= n) return;
-    const u64* g = (const u64*)(got + 32 * k);
-    const u64* w = want + (u64)stride * k;
-    if (g[0] != w[0] || g[1] != w[1] || g[2] != w[2] || g[3] != w[3]) atomicMin((unsigned long long*)first_bad, (unsigned long long)k);
+    digest_differs_mark(got, want + (u64)stride * k, k, first_bad);
 }
 
 }  // namespace mi
@@ -255,22 +216,6 @@ namespace {
 
 double ms_since(std::chrono::steady_clock::time_point t0) {
     return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
-std::string hex32(const uint8_t* d) {
-    static const char* dig = "0123456789abcdef";
-    std::string out(64, '0');
-    for (int i = 0; i < 32; ++i) { out[2 * i] = dig[d[i] >> 4]; out[2 * i + 1] = dig[d[i] & 15]; }
-    return out;
-}
-
-// device memory of exactly `want` bytes + DevBuf's 256 bytes of slack (mi_pack.hip's scheme: a blob does not grow)
-hipError_t alloc_exact(DevBuf* b, u64 want) {
-    const size_t alloc = (size_t)(((want + 255) & ~(u64)255) + 256);
-    void* p = nullptr;
-    const hipError_t e = dev_alloc(&p, alloc);
-    if (e == hipSuccess) { b->release(); b->p = p; b->bytes = alloc; }
-    return e;
 }
 
 int blob_does_not_fit(mi_ctx* c, const char* who, hipError_t e, u64 blob_bytes, u64 n) {
@@ -296,7 +241,7 @@ int verify_stored(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpac
     hipStream_t st = c->stream;
     std::vector<mi_pack_entry> plain(n);
     DevBuf d_plain, d_off, d_len, d_got, d_bad;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    StreamDrain drain{st};   // (goes first: the buffers above after it)
     u64 plain_bytes = 0;
     int rc = mi_zpack_decode_plain(c, who, d_zblob, entries, n, &d_plain, &plain_bytes, plain.data(), bad, rule, ms_decode);
     if (rc || *bad != kQNone) return rc;
@@ -310,7 +255,7 @@ int verify_stored(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpac
     const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
     hash_items(kShaBlobs, d_plain.as<u8>(), d_off.as<u64>(), d_off.as<u64>() + n, nullptr, (u32)n, nullptr, c->heads.as<u32>(), nullptr, true,
                d_got.as<u8>(), c->sha, c->prop.multiProcessorCount, plain_bytes, st);
-    hipLaunchKernelGGL(zset_compare_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_got.as<u8>(), d_rows, (u32)kQEntryWords, n,
+    hipLaunchKernelGGL(zset_compare_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_got.as<u8>(), d_rows, (u32)kEntryWords, n,
                        d_bad.as<u64>());
     u64* h = c->h_word.as<u64>();
     HIPCHK(c, hipMemcpyAsync(h, d_bad.p, 8, hipMemcpyDeviceToHost, st));
@@ -328,7 +273,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
     hipStream_t st = c->stream;
     DevBuf mine = std::move(blob);                     // freed on every early return -- after the stream has drained
     DevBuf d_ent, d_recs;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    StreamDrain drain{st};   // (goes first: the buffers above after it)
     s->info.ms_verify = s->info.ms_insert = 0;
     if (n == 0) {                                      // a zpack of nothing
         ++s->info.n_packs;
@@ -421,7 +366,7 @@ int mi_zset_add_zblob(mi_zset* s, const void* blob, uint64_t blob_bytes, const m
     s->info.ms_upload = 0;
     DevBuf d_blob;
     if (blob_bytes && n) {
-        const hipError_t e = alloc_exact(&d_blob, blob_bytes);
+        const hipError_t e = d_blob.alloc_exact(blob_bytes);
         if (e != hipSuccess) return blob_does_not_fit(c, who, e, blob_bytes, n);
         const auto t0 = std::chrono::steady_clock::now();
         rc = s->up.upload(c, d_blob.as<u8>(), blob, blob_bytes);
@@ -450,7 +395,7 @@ int mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags) {
     s->info.ms_upload = 0;
     DevBuf d_blob;
     if (blob_bytes && n) {
-        const hipError_t e = alloc_exact(&d_blob, blob_bytes);
+        const hipError_t e = d_blob.alloc_exact(blob_bytes);
         if (e != hipSuccess) return blob_does_not_fit(c, who, e, blob_bytes, n);
         const auto t0 = std::chrono::steady_clock::now();
         hipError_t ce = hipMemcpyAsync(d_blob.p, src, blob_bytes, hipMemcpyDeviceToDevice, c->stream);
@@ -489,7 +434,7 @@ int mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint3
     HIPCHK(c, hipSetDevice(c->device));
     hipStream_t st = c->stream;
     DevBuf d_recs, d_cursor;
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{st};   // (goes first: the buffers above after it)
+    StreamDrain drain{st};   // (goes first: the buffers above after it)
     std::vector<u64> recs(s->table.count * kSlotWords);
     HIPCHK(c, d_recs.ensure(s->table.count * kSlotWords * 8));
     HIPCHK(c, d_cursor.ensure(8));
@@ -554,9 +499,9 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
     hipStream_t s = c->stream;
     DevBuf d_dig, d_len32, d_src, d_word, d_len64, d_dup, d_scan, e_src, e_len, e_dst, d_rows;
     Event ev[4];
-    struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+    StreamDrain drain{s};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
-    const u64 nb = (n + kQTile - 1) / kQTile;
+    const u64 nb = (n + kPlanTile - 1) / kPlanTile;
     u64 dd_cap = 1024;
     while (dd_cap < 2 * n) dd_cap <<= 1;
     HIPCHK(c, d_dig.ensure(n * 32));
@@ -583,9 +528,9 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
                        d_src.as<u64>(), d_word.as<u64>(), d_len64.as<u64>(), totals + kQTotBad);
     launch_dedup_mark(d_dig.as<u8>(), n, nullptr, c->dd_table.as<u32>(), c->dd_slot.as<u32>(), dd_cap, d_dup.as<i64>(), c->dd_nuniq.as<u64>(),
                       true, s);
-    hipLaunchKernelGGL(zset_block_sums_kernel, dim3((u32)nb), dim3(kQBlock), 0, s, d_dup.as<i64>(), d_word.as<u64>(), n, block_cnt, block_bytes,
+    hipLaunchKernelGGL(zset_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_dup.as<i64>(), d_word.as<u64>(), n, block_cnt, block_bytes,
                        totals);
-    hipLaunchKernelGGL(zset_block_offsets_kernel, dim3(1), dim3(kQBlock), 0, s, block_cnt, block_bytes, nb, totals);
+    hipLaunchKernelGGL(zset_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_cnt, block_bytes, nb, totals);
     HIPCHK(c, hipEventRecord(ev[1], s));
     u64* h = c->h_word.as<u64>();
     HIPCHK(c, hipMemcpyAsync(h, totals, 8 * 8, hipMemcpyDeviceToHost, s));
@@ -617,7 +562,7 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
     HIPCHK(c, e_len.ensure(n_sel * 8));
     HIPCHK(c, e_dst.ensure(n_sel * 8));
     HIPCHK(c, hipEventRecord(ev[2], s));
-    hipLaunchKernelGGL(zset_compact_entries_kernel, dim3((u32)nb), dim3(kQBlock), 0, s, d_dup.as<i64>(), d_src.as<u64>(), d_word.as<u64>(),
+    hipLaunchKernelGGL(zset_compact_entries_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_dup.as<i64>(), d_src.as<u64>(), d_word.as<u64>(),
                        d_dig.as<u8>(), n, block_cnt, block_bytes, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), d_rows.as<u64>());
     hipLaunchKernelGGL(zset_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n_sel,
                        blob_bytes, (u8*)d_blob);
@@ -708,7 +653,7 @@ int mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, con
         hipStream_t s = c->stream;
         DevBuf d_dig, d_len32, d_dst, d_src, d_word, d_len64, d_rule, d_cell, d_got;
         Event ev[4];
-        struct Drain { hipStream_t st; ~Drain() { (void)hipStreamSynchronize(st); } } drain{s};   // (goes first: buffers and events after it)
+        StreamDrain drain{s};   // (goes first: buffers and events after it)
         for (auto& e : ev) HIPCHK(c, e.create());
         HIPCHK(c, d_dig.ensure(n_rows * 32));
         HIPCHK(c, d_len32.ensure(n_rows * 4));

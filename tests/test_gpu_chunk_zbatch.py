@@ -473,6 +473,34 @@ def test_digests_that_share_their_first_eight_bytes_are_each_their_own():
         _same_missing(zs.missing(dig[order], lens), model)
 
 
+def test_a_request_of_more_than_256_plan_blocks_against_a_small_zset():
+    """600 000 rows are 293 blocks of the plan's 2 048: the one block that scans the block sums (csrc/mi_plan.h) goes round
+    twice and carries between the rounds -- from mi_zset_missing, its second caller beside mi_packset_missing
+    (test_gpu_chunk_fetch.py).  No lengths are stated.  The compacting kernels that take real chunk bytes (pack, zbatch, the
+    zset's cut, zprune) have their 2047 / 2048 / 2049 cases; more than 256 blocks of real chunks is not a test of a few
+    seconds: that is left to the shared body and the two want-list tests."""
+    rng = np.random.default_rng(113)
+    n_set, n_unknown, n = 48, 450_000, 600_000
+    dig = fc.fake_digests(rng, n_set + n_unknown)
+    chunks = [zc.text_like(k, k) if k % 3 == 0 else rng.integers(0, 256, k, dtype=np.uint8).tobytes() for k in range(20, 20 + 7 * n_set, 7)]
+    pe, pb, ze, zb = qc.zpack_of(chunks, digests=dig[:n_set])
+    # the set's own digests repeated, every unknown digest once and some of them again, permuted
+    pick = np.concatenate([rng.integers(0, n_set, 100_000), n_set + np.arange(n_unknown), rng.integers(n_set, n_set + n_unknown, 50_000)])
+    pick = pick[rng.permutation(n)]
+    assert len(pick) == n and n // fc.PLAN_BLOCK > 256
+    # numpy's answer: a digest counts where it occurs first; held iff it is the set's; the want rows ascending
+    distinct, first = np.unique(pick, return_index=True)
+    w_held = (pick < n_set).astype(np.uint8)
+    w_rows = np.sort(first[distinct >= n_set]).astype(np.uint64)
+    held_ids = distinct[distinct < n_set]
+    w_info = dict(n_rows=n, n_distinct=len(distinct), n_held=len(held_ids), n_want=len(w_rows),
+                  held_bytes=sum(len(chunks[k]) for k in held_ids), want_bytes=0)
+    assert w_info["n_held"] == n_set and w_info["n_want"] == n_unknown
+    with M.Engine() as e, e.zset() as zs:
+        zs.add_zblob(zb, ze)                                           # (verify is off: the digests are opaque)
+        _same_missing(zs.missing(dig[pick]), (w_held, w_rows, w_info))
+
+
 # ---- 10. the bounds, checked by the hardware ----------------------------------------------------------------------------------------------
 # The bounds, from the code (csrc/mi_zbatch.hip): the coder reads inside the chunk only; a unit's load of the gather begins at
 # src + o, o a multiple of 16 below `stored`, and is 16 bytes long -- the last unit of a RAW entry of len bytes ends at most 15 bytes

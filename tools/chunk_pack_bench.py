@@ -68,7 +68,7 @@ def resident(eng, n_files, runs, say):
         W.fill_batch(b, sh)
         b.run()
         b.rerun()
-        ms_chunk_pass = eng.stats().as_dict()["ms_sha_chunks"]
+        ms_chunk_pass = eng.stats()["ms_sha_chunks"]
         chunks = b.chunks()
         known, n_new, n_known = ix.add_batch(b)
         sel = ((known == 0) & (chunks["dup_of"] < 0)).astype(np.uint8)
