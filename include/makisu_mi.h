@@ -1395,6 +1395,64 @@ MI_BLOCK int  mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out);
 MI_BLOCK int  mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint32_t* stored, uint64_t cap,
                               uint64_t* n);
 
+/* ---- recoding a compressed set in place ---------------------------------------------------------------------------- *
+ * A commit codes at level 1 (level 2's encode is too slow for its critical path); a store densifies AT REST.  A resident set
+ * codes every chunk it holds again at a requested level and replaces a stored form only where the new one is STRICTLY SMALLER:
+ * no chunk ever grows, whatever the level does to it.  No plain pack set, no second set, no second table in the caller's hands.
+ *   mi_zset_recode        flags: the level as the coders take it -- MI_ZPACK_LEVEL2, or absent = level 1 -- and optionally
+ *                         MI_ZSET_RECODE_VERIFY; any other bit, or s = NULL: MI_ERR_INVALID.  THE RULE: for every digest the
+ *                         set holds, `plain` is what its stored form decodes to (a raw form is its own bytes); the CANDIDATE
+ *                         is exactly what the coder of the level stores for `plain` -- the LZ4 block if it is smaller than
+ *                         length - (length >> 4), else raw; chunks under 13 bytes are always raw; the stored form is replaced
+ *                         if and only if the candidate's size < stored, otherwise the entry keeps its bytes verbatim.  A
+ *                         chunk's new form is a pure function of its current stored form and the level: a second call at the
+ *                         same level changes nothing; `length` and the digest never change; a set of raw entries holds
+ *                         afterwards, byte for byte, mi_pack_compress's forms at that level.  BLOBS: a blob with at least one
+ *                         replaced entry is REWRITTEN -- every entry the table holds in it goes to ONE new blob shared by the
+ *                         call, replaced entries in their new form with ZERO pads, the others verbatim (whole 16-byte units,
+ *                         round16(stored) bytes a span, the pad as it was, as in mi_zset_prune) -- and then freed, with
+ *                         whatever dead spans it carried.  A blob with no replaced entry is not touched: no span moves, no
+ *                         address changes.  The order inside the new blob is the table's slot order, as in a prune's
+ *                         compaction; no caller may depend on it.  The table is REBUILT through the set's own insert (a power
+ *                         of two, at least 1 024 slots, at most half full) and swapped; the old table is never written.
+ *                         Nothing to replace: the set is untouched -- no new blob, no new table -- and the call is MI_OK with
+ *                         *info (may be NULL) filled.  mi_zset_info afterwards: stored_bytes describes what is held;
+ *                         n_packs, n_entries and blob_bytes stay sums over what was added, as after a prune (residency and
+ *                         live bytes: mi_zset_get_usage).  ROUNDS: scratch_bytes bounds one round's scratch -- the plain
+ *                         bytes decoded (round16(length) of every coded entry; a raw one is coded where it lies) plus the
+ *                         worst-case coded spans (length + length / 255 + 16, rounded up to 16) of its entries; 0 = 256 MiB; a
+ *                         single chunk that needs more gets a round of its own with scratch of its size; the result does
+ *                         not depend on scratch_bytes, n_rounds says how many ran.  The new forms wait in staging memory of
+ *                         exactly their size (one piece a round) until the new blob is written.  UNDECODABLE ENTRIES: an
+ *                         unverified set may hold a form that breaks a rule of mi_zpack_check (a non-zero pad byte among
+ *                         them).  Without VERIFY that is no error: the entry is counted in n_undecodable and kept verbatim
+ *                         -- moved verbatim if its blob is rewritten -- and readers refuse it exactly as before.  The decoder
+ *                         is the bounds-safe one of every reader; neither it nor the coder reads or writes outside the span
+ *                         and the scratch it was given.  MI_ZSET_RECODE_VERIFY: (a) every held entry's `plain` is hashed by
+ *                         the ctx's own hashing kernel (SHA-256 or BLAKE2s, as the ctx is) and held against its digest; if
+ *                         any entry does not decode or does not hash, the call is MI_ERR_IO, the message gives the count and
+ *                         one such digest in hex, and the set is unchanged; (b) before the swap every replaced form is
+ *                         decoded again FROM THE NEW BLOB and hashed against its digest; a difference is MI_ERR_IO saying so,
+ *                         the set unchanged.  With VERIFY and nothing to replace the call is a scrub of the whole set.
+ *                         Everything is allocated before anything changes: scratch, staging, new blob or table that does not
+ *                         fit is MI_ERR_NOMEM naming the size and what the device has free, the set unchanged.  A set in its
+ *                         sticky failed state: MI_ERR_STATE with the first message.  An empty set: MI_OK, *info zero.  Zpacks
+ *                         cut and batches restored earlier own their bytes and are not affected.  Blocking, on the ctx
+ *                         stream.  One GPU; a plain mi_packset has no counterpart.                                          */
+#define MI_ZSET_RECODE_VERIFY 0x1u
+typedef struct {               /* 152 bytes */
+    uint64_t n_digests;                       /* held when the call began */
+    uint64_t n_recoded, n_raw_recoded;        /* forms replaced; of them, those that were raw */
+    uint64_t n_undecodable;                   /* stored forms that break a decoding rule: left as they are */
+    uint64_t stored_before, stored_after;     /* sums of stored over the held digests */
+    uint64_t live_before, live_after;         /* sums of round16(stored) */
+    uint64_t n_blobs_rewritten, n_blobs_freed, freed_bytes, new_blob_bytes;   /* freed_bytes: ALLOCATED bytes given back */
+    uint64_t n_rounds;
+    uint64_t peak_extra_bytes;                /* as mi_prune_info's: device bytes this call allocated before it freed anything, from the sizes */
+    double   ms_decode, ms_encode, ms_move, ms_rebuild, ms_verify;   /* HIP events on the ctx stream; ms_move: choose, stage, plan, gather */
+} mi_recode_info;
+MI_BLOCK int  mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode_info* info);
+
 /* ---- the chunk index: asking without adding, forgetting ------------------------------------------------------------ *
  * The index's half of garbage collection.  A store that prunes its set (mi_zset_prune) hands the same list to the index, or a
  * builder's index would go on calling a dropped chunk "known", the commit would leave it out of its pack, and the layer's

@@ -22,7 +22,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
            "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK", "ZPACK_LEVEL2", "MEMFS_ZPACK_LEVEL2",
-           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP",
+           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP", "RecodeInfo", "ZSET_RECODE_VERIFY",
            "IndexPruneInfo", "INDEX_PRUNE_KEEP", "INDEX_PRUNE_DROP"]
 
 FLAG_FILE_SHA256 = 0x1
@@ -216,6 +216,20 @@ class PruneInfo(C.Structure):
 class ZSetUsage(C.Structure):
     """mi_zset_usage."""
     _fields_ = [(n, C.c_uint64) for n in ("n_blobs", "resident_bytes", "live_bytes", "table_slots", "table_bytes")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+ZSET_RECODE_VERIFY = 0x1                 # mi_zset_recode: hash what every entry decodes to, before and after (beside ZPACK_LEVEL2)
+
+
+class RecodeInfo(C.Structure):
+    """mi_recode_info."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_digests", "n_recoded", "n_raw_recoded", "n_undecodable", "stored_before", "stored_after",
+                                          "live_before", "live_after", "n_blobs_rewritten", "n_blobs_freed", "freed_bytes", "new_blob_bytes",
+                                          "n_rounds", "peak_extra_bytes")] + \
+               [(n, C.c_double) for n in ("ms_decode", "ms_encode", "ms_move", "ms_rebuild", "ms_verify")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -504,6 +518,7 @@ def load_library(rebuild=False):
         "mi_memfs_take_zpack": ([vp, C.POINTER(vp)], C.c_int),
         "mi_zset_missing": ([vp, vp, vp, u64, vp, vp, u64, C.POINTER(WantInfo)], C.c_int),
         "mi_zset_prune": ([vp, vp, u64, C.c_uint32, C.c_uint32, C.POINTER(PruneInfo)], C.c_int),
+        "mi_zset_recode": ([vp, C.c_uint32, u64, C.POINTER(RecodeInfo)], C.c_int),
         "mi_zset_get_usage": ([vp, C.POINTER(ZSetUsage)], C.c_int),
         "mi_zset_entries": ([vp, vp, vp, vp, u64, u64p], C.c_int),
         "mi_index_query": ([vp, vp, u64, vp, u64p], C.c_int),
@@ -1533,6 +1548,17 @@ class ZSet:
         info = PruneInfo()
         rc = self._lib.mi_zset_prune(self._h, d.ctypes.data if len(d) else None, len(d), ZSET_PRUNE_KEEP if keep else ZSET_PRUNE_DROP,
                                      min_live_permille, C.byref(info))
+        if rc:
+            self._raise(rc)
+        return info
+
+    def recode(self, level=2, verify=False, scratch_bytes=0):
+        """mi_zset_recode: code every chunk the set holds again at `level` and replace a stored form only where the new one is
+        strictly smaller; the blobs that held a replaced form are rewritten into one new blob and freed, the others are not
+        touched.  verify: every entry's bytes are hashed against its digest first, every replaced form again from the new blob.
+        scratch_bytes bounds one round's scratch (0: 256 MiB); the result does not depend on it.  -> RecodeInfo"""
+        info = RecodeInfo()
+        rc = self._lib.mi_zset_recode(self._h, _zpack_level_flag(level) | (ZSET_RECODE_VERIFY if verify else 0), scratch_bytes, C.byref(info))
         if rc:
             self._raise(rc)
         return info

@@ -1,6 +1,6 @@
-// mi_zset_local.h -- what a compressed pack set IS, for the two translation units that work on one: mi_zset.hip (create, add,
-// cut, restore) and mi_zprune.hip (prune in place, usage).  Host types only: no kernel lives here, and mi_zset.hip's device
-// code does not depend on it.  The table both work on is a mi::SlotTable (mi_slot_table.h).
+// mi_zset_local.h -- what a compressed pack set IS, for the translation units that work on one: mi_zset.hip (create, add,
+// cut, restore), mi_zprune.hip (prune in place, usage) and mi_zrecode.hip (recode in place).  Host types only: no kernel lives
+// here, and mi_zset.hip's device code does not depend on it.  The table all three work on is a mi::SlotTable (mi_slot_table.h).
 #pragma once
 #include "mi_slot_table.h"
 
