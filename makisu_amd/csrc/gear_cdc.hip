@@ -224,31 +224,36 @@ __device__ __forceinline__ void hash16(u64& h, const u32x4 v, u32 tab, u32 thres
 // (bit p <-> cut end ts + p + 1).  fptr is 16-byte aligned, ts a multiple of kGearTile.
 // pk/ovf: the lane's packed candidates for the fast selection path (cand_push / cand_compact).
 // kBitmap = false: no bitmap at all (bitmap may be nullptr); the candidates are in pk only.
-template <int kC, bool kBitmap>
-__device__ __forceinline__ void mark_tile(const u8* __restrict__ fptr, u64 ts, u32 tlen,
-                                          u32* bitmap, u32 tab, u32 thresh_m1, int lane,
-                                          CandPack& pk, bool& ovf) {
-    if (kBitmap) {   // clear the bitmap: 32 words per lane
-        u32x4* bz = (u32x4*)bitmap;
-        const u32x4 z = {0, 0, 0, 0};
+// mark_tile in two steps, so that a kernel can issue a tile's first loads -- which need no table -- before it
+// fills the table: tile_first_loads requests the first piece of the lane's run and the 64 bytes before it,
+// mark_tile_loaded does the rest.
+__device__ __forceinline__ void tile_first_loads(const u8* __restrict__ fptr, u64 ts, u32 tlen, int lane,
+                                                 u32x4 (&cur)[kPieceUnits], u32x4 (&wq)[4]) {
+    const u32 run0 = (u32)lane * kLaneRun;               // tile-relative start of my run
+    if (run0 >= tlen) return;
+    const u8* p = fptr + ts + run0;
+    load_piece(p, cur);
+    if (ts + run0 != 0) {                                // the window's warm-up: 64 bytes before my run
 #pragma unroll
-        for (int i = 0; i < kBitmapWords / 4 / 64; ++i) bz[i * 64 + lane] = z;
+        for (int i = 0; i < 4; ++i) wq[i] = *(const u32x4*)(p - 64 + 16 * i);
     }
+}
+
+template <int kC, bool kBitmap>
+__device__ __forceinline__ void mark_tile_loaded(const u8* __restrict__ fptr, u64 ts, u32 tlen,
+                                                 u32* bitmap, u32 tab, u32 thresh_m1, int lane,
+                                                 u32x4 (&cur)[kPieceUnits], const u32x4 (&wq)[4],
+                                                 CandPack& pk, bool& ovf) {
     pk.a = pk.b = 0;
     ovf = false;
-    const u32 run0 = (u32)lane * kLaneRun;               // tile-relative start of my run
+    const u32 run0 = (u32)lane * kLaneRun;
     if (run0 >= tlen) return;
     const u8* p = fptr + ts + run0;
     const u32 run_len = tlen - run0 < (u32)kLaneRun ? tlen - run0 : (u32)kLaneRun;
     const int n_pieces = (int)((run_len + kPiece - 1) / kPiece);
-    u32x4 cur[kPieceUnits];
-    load_piece(p, cur);
     u64 h = 0;
     u32 hh[16];
-    if (ts + run0 != 0) {                                // warm the window: 64 bytes before my run
-        u32x4 wq[4];
-#pragma unroll
-        for (int i = 0; i < 4; ++i) wq[i] = *(const u32x4*)(p - 64 + 16 * i);
+    if (ts + run0 != 0) {                                // warm the window
 #pragma unroll
         for (int i = 0; i < 4; ++i) roll16<kC>(h, wq[i], tab, hh);
     }
@@ -264,6 +269,21 @@ __device__ __forceinline__ void mark_tile(const u8* __restrict__ fptr, u64 ts, u
     // (Round 3 tried one piece of registers instead of two -- each 16-byte unit of the next piece requested
     // into the registers of the unit just hashed, 84 VGPRs, five or six waves per SIMD: 2.15-2.28 ms instead
     // of 1.34, profiles/r03_gear_ab.txt; a load per unit means a wait per unit.)
+}
+
+template <int kC, bool kBitmap>
+__device__ __forceinline__ void mark_tile(const u8* __restrict__ fptr, u64 ts, u32 tlen,
+                                          u32* bitmap, u32 tab, u32 thresh_m1, int lane,
+                                          CandPack& pk, bool& ovf) {
+    if (kBitmap) {   // clear the bitmap: 32 words per lane
+        u32x4* bz = (u32x4*)bitmap;
+        const u32x4 z = {0, 0, 0, 0};
+#pragma unroll
+        for (int i = 0; i < kBitmapWords / 4 / 64; ++i) bz[i * 64 + lane] = z;
+    }
+    u32x4 cur[kPieceUnits], wq[4];
+    tile_first_loads(fptr, ts, tlen, lane, cur, wq);
+    mark_tile_loaded<kC, kBitmap>(fptr, ts, tlen, bitmap, tab, thresh_m1, lane, cur, wq, pk, ovf);
 }
 
 // Wave-uniform cut selection over one marked tile.  Every cut is handed to emit(cut) (wave-uniform
@@ -344,6 +364,18 @@ __device__ __forceinline__ void load_table(u64* table, const u64* __restrict__ g
     for (int i = tid; i < 256 * kC; i += kWG) table[i] = gear_table[i / kC];
 }
 
+// The 32-copy table of a 512-thread workgroup: two threads per entry, each reads G[b] ONCE and writes
+// sixteen copies of it, two per 16-byte LDS store (load_table: a global load and an 8-byte store per copy).
+typedef u64 u64x2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void load_table_fast(u64* table, const u64* __restrict__ gear_table, int tid) {
+    static_assert(kFastWG == 2 * 256 && kFastCopies == 32, "two threads per entry, sixteen copies each");
+    const u64 g = gear_table[tid >> 1];
+    const u64x2 gg = {g, g};
+    u64x2* dst = (u64x2*)(table + (tid >> 1) * kFastCopies + (tid & 1) * (kFastCopies / 2));
+#pragma unroll
+    for (int i = 0; i < kFastCopies / 4; ++i) dst[i] = gg;
+}
+
 // ---- small files: one wave per file (size <= kGearTile) ----------------------------------
 // A small file is one SEGMENT: its chunk ends go to ends32[seg_slot[s] ..] (u32, file-relative),
 // its chunk count to seg_n[s].
@@ -360,23 +392,35 @@ void gear_cdc_small_fast_kernel(const u8* __restrict__ data, const u64* __restri
                                 u32* __restrict__ dense_list, u32* __restrict__ dense_count) {
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     u64* table = (u64*)smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);                    // wave-uniform: the descriptor loads are scalar
     u32* cand_list = (u32*)(smem + kFastListOff) + wave * 64;
-    load_table<kFastCopies, kFastWG>(table, gear_table, tid);
+    // The file's descriptor and its first loads need no table: they are issued FIRST and are under way while the
+    // workgroup fills the table and meets at the barrier (a wave past the list's end only helps with the table).
+    const u32 li = blockIdx.x * kFastWaves + wave;
+    const bool have = li < n_list;
+    u32 s = 0;
+    u64 size = 0, off = 0, slot = 0;
+    if (have) {
+        s = list[li];
+        const u32 f = seg_file[s];
+        size = file_size[f];
+        off = file_off[f];
+        slot = seg_slot[s];
+    }
+    u32x4 cur[kPieceUnits], wq[4];
+    tile_first_loads(data + off, 0, (u32)size, lane, cur, wq);
+    load_table_fast(table, gear_table, tid);
     __syncthreads();
     const u32 lane_tab = lds_lane_table<kFastCopies>(table, lane);
-    const u32 li = blockIdx.x * kFastWaves + wave;
-    if (li >= n_list) return;
-    const u32 s = list[li];
-    const u32 f = seg_file[s];
-    const u64 size = file_size[f];
-    u32* ends = ends32 + seg_slot[s];
+    if (!have) return;
+    u32* ends = ends32 + slot;
     u64 last = 0;
     u32 n_out = 0;
     if (size) {
         CandPack pk;
         bool ovf;
-        mark_tile<kFastCopies, false>(data + file_off[f], 0, (u32)size, nullptr, lane_tab, p.thresh_m1, lane, pk, ovf);
+        mark_tile_loaded<kFastCopies, false>(data + off, 0, (u32)size, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf);
         if (!cand_compact(pk, ovf, (u32)lane * kLaneRun, lane, cand_list)) {      // wave-uniform
             if (lane == 0) dense_list[atomicAdd(dense_count, 1u)] = s;
             return;
@@ -533,26 +577,35 @@ void gear_tile_mark_kernel(const u8* __restrict__ data, const u64* __restrict__ 
     // -- or a lane with more than six -- is DENSE (tile_fast = 0) and re-marked, with bitmaps, by C
     extern __shared__ __attribute__((aligned(16))) u8 smem[];
     u64* table = (u64*)smem;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     u32* cl = (u32*)(smem + kFastListOff) + wave * 64;
-    load_table<kFastCopies, kFastWG>(table, gear_table, tid);
-    __syncthreads();
-    const u32 lane_tab = lds_lane_table<kFastCopies>(table, lane);
-    // one wave per tile, four tiles per group, whatever the workgroup's size
+    // one wave per tile, four tiles per group, whatever the workgroup's size; like the small-file kernel, the
+    // tile's descriptor and first loads come before the table and the barrier
     const u64 gw = (u64)blockIdx.x * kFastWaves + (u64)wave;
     const u32 g = (u32)(gw / kWavesPerWG);
-    if (g >= n_groups) return;
+    const bool have = g < n_groups;
     const int tw = (int)(gw % kWavesPerWG);
     const u64 t = (u64)g * kWavesPerWG + tw;
-    const u32 f = group_file[g];
-    const u64 size = file_size[f];
-    const u64 ts = (u64)group_index[g] * kGroupBytes + (u64)tw * kGearTile;
+    u64 size = 0, off = 0, ts = 0;
+    if (have) {
+        const u32 f = group_file[g];
+        size = file_size[f];
+        off = file_off[f];
+        ts = (u64)group_index[g] * kGroupBytes + (u64)tw * kGearTile;
+    }
+    const u32 tlen = ts >= size ? 0u : (u32)((size - ts < (u64)kGearTile) ? (size - ts) : (u64)kGearTile);
+    u32x4 cur[kPieceUnits], wq[4];
+    tile_first_loads(data + off, ts, tlen, lane, cur, wq);
+    load_table_fast(table, gear_table, tid);
+    __syncthreads();
+    const u32 lane_tab = lds_lane_table<kFastCopies>(table, lane);
+    if (!have) return;
     bool fast = true;                                         // tiles past the end count as listed
-    if (ts < size) {
-        const u32 tlen = (u32)((size - ts < (u64)kGearTile) ? (size - ts) : (u64)kGearTile);
+    if (tlen) {
         CandPack pk;
         bool ovf;
-        mark_tile<kFastCopies, false>(data + file_off[f], ts, tlen, nullptr, lane_tab, p.thresh_m1, lane, pk, ovf);
+        mark_tile_loaded<kFastCopies, false>(data + off, ts, tlen, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf);
         fast = cand_compact(pk, ovf, (u32)lane * kLaneRun, lane, cl);
         __builtin_amdgcn_wave_barrier();
         tile_lists[t * 64 + lane] = fast ? cl[lane] : kNoCand;
