@@ -1186,6 +1186,30 @@ MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const
  * that CODE: mi_pack_compress and mi_batch_zpack_chunks, alone or with MI_ZPACK_VERIFY.  Nothing that reads, moves or decodes a
  * stored form takes it or needs it: mi_zpack_check, mi_packset_add_z*, mi_zset_add_z*, mi_zset_zpack, mi_zset_missing,
  * mi_zset_prune and mi_batch_add_zrecipes treat a block of either level alike.
+ * THE ENTROPY STAGE (MI_ZPACK_ENTROPY, beside either level).  A stored span with stored < length whose FIRST BYTE IS 0x00 is an
+ * entropy form, "form H" -- no LZ4 block begins with a token without literals: a match at output position 0 has no source:
+ *     byte 0 0x00 | byte 1 kind | byte 2 S - 1 (0..63) | byte 3 0 | bytes 4..7 the inner length, u32 little-endian |
+ *     128 bytes: 256 code lengths of 4 bits, symbol 2k in the low nibble of byte k, 0 = absent, 1..11 |
+ *     S stream sizes, u16 little-endian | the streams
+ * kind 1: the inner bytes are ONE STANDARD LZ4 BLOCK of the chunk, as above (0 < inner length < length); kind 2: they are the
+ * chunk's plain bytes (inner length == length).  Stream s holds the symbols s, s + S, s + 2S, ... of the inner bytes in a
+ * canonical Huffman code assigned by (length, symbol) ascending, packed as deflate packs: LSB first, codes bit-reversed, the
+ * last byte of a stream padded with zero bits.  Form H is made only for chunks of at most 65 536 bytes, always with S = 32, and
+ * kept only where it is smaller than the form under it (the level's LZ4 block, or the raw chunk) by more than a sixteenth of
+ * that form; the code lengths are a stated function of the byte counts (tests/zentropy_cases.py): the stored form stays a pure
+ * function of the chunk, the level and the stage.  Everything that MOVES stored spans (mi_zset_zpack, mi_zset_prune,
+ * mi_zset_missing, the gathers) is untouched.  Everything that DECODES accepts form H with 1..64 streams: mi_zpack_check,
+ * mi_packset_add_z*, MI_ZSET_VERIFY, MI_ZPACK_VERIFY and mi_batch_add_zrecipes unwrap it first (one classify launch where no
+ * form H is; else one scratch for the inner forms -- it does not fit: MI_ERR_NOMEM naming its size, nothing changed).  The
+ * unwrap trusts nothing; its refusals continue the decoder's numbering: 8 the header (kind, reserved byte, stream count, inner
+ * length, a span shorter than header, table and sizes, a chunk above 65 536 bytes), 9 the code (a length above 11, no symbol,
+ * an over-subscribed code; an incomplete one is legal), 10 stream sizes that do not sum to the rest of the span, 11 a stream
+ * that ends early, meets an unassigned code, has a whole byte left over or a pad bit set; then the inner block's own rules.
+ * A library from before the stage refuses such a span cleanly (its decoder fails the 0x00 token's offset).  mi_zset_recode takes
+ * the flag beside the level and MI_ZSET_RECODE_VERIFY: its rule is unchanged (a stored form is replaced only where the candidate
+ * is strictly smaller; a second call changes nothing), the candidate is the level's form with the stage over it, and with or
+ * without the flag it decodes the form H a set already holds.  mi_batch_zpack_chunks and the commit's zpack options refuse the
+ * flag: the commit's critical path codes at level 1, a store densifies at rest.
  *   mi_pack_compress      any pack (mi_batch_pack_chunks, mi_memfs_take_pack, mi_packset_pack), which stays the caller's and is
  *                         not changed.  Blocking, on the ctx stream.  The zpack is a child of the pack's ctx (mi_ctx_destroy
  *                         refuses while one lives).  0 entries: a zpack of 0 entries.  The coder's scratch (worst-case spans)
@@ -1213,13 +1237,14 @@ MI_BLOCK int  mi_packset_pack(const mi_packset* s, const uint8_t* digests, const
  *                         does not hash).                                                                                */
 #define MI_ZPACK_VERIFY 0x1u
 #define MI_ZPACK_LEVEL2 0x4u   /* mi_pack_compress, mi_batch_zpack_chunks: the denser parse (LEVELS above) */
+#define MI_ZPACK_ENTROPY 0x20u /* mi_pack_compress, mi_zset_recode: the entropy stage over the level's forms (THE ENTROPY STAGE above) */
 typedef struct mi_zpack mi_zpack;
 typedef struct {               /* 56 bytes: mi_pack_entry's layout */
     uint8_t  digest[32];       /* of the chunk's PLAIN bytes (the ctx's algorithm) */
     uint64_t offset;           /* where the stored form begins in the blob: a multiple of 16 */
     uint64_t chunk_index;      /* as in the pack the zpack was made from */
     uint32_t length;           /* the chunk's bytes, never 0 */
-    uint32_t stored;           /* bytes in the blob: == length raw, < length one LZ4 block */
+    uint32_t stored;           /* bytes in the blob: == length raw, < length one LZ4 block or, first byte 0x00, form H */
 } mi_zpack_entry;
 typedef struct {               /* 80 bytes */
     uint64_t n_entries, blob_bytes, chunk_bytes;   /* blob_bytes = sum of stored sizes rounded up to 16 */
@@ -1240,6 +1265,14 @@ MI_BLOCK int  mi_packset_add_zblob(mi_packset* s, const void* blob, uint64_t blo
 MI_BLOCK int  mi_packset_add_zpack(mi_packset* s, const mi_zpack* z, uint32_t flags);
 MI_BLOCK int  mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n,
                              uint32_t alg, uint64_t* first_bad);
+/* the census of a zpack's (a compressed pack set's) stored forms, counted on the device from every span's first bytes: [0] raw,
+ * [1] one LZ4 block, [2] form H over an LZ4 block, [3] form H over the plain bytes.  Blocking, on the ctx stream.  The info
+ * structs do not change */
+typedef struct {               /* 64 bytes */
+    uint64_t n[4];             /* entries (digests) of each form */
+    uint64_t stored[4];        /* the sum of their stored sizes */
+} mi_zforms;
+MI_BLOCK int  mi_zpack_count_forms(const mi_zpack* z, mi_zforms* out);
 
 /* ---- compressed pack sets: zpacks resident AS STORED, cut by digest and restored without recoding ------------------ *
  * A chunk's stored form is a pure function of its bytes and the level (every chunk is coded on its own), so a store server
@@ -1298,6 +1331,7 @@ MI_BLOCK int  mi_zset_add_zblob(mi_zset* s, const void* blob, uint64_t blob_byte
                                 uint64_t n, uint32_t flags, uint64_t* first_bad);
 MI_BLOCK int  mi_zset_add_zpack(mi_zset* s, const mi_zpack* z, uint32_t flags);
 MI_BLOCK int  mi_zset_get_info(const mi_zset* s, mi_zset_info* out);
+MI_BLOCK int  mi_zset_count_forms(const mi_zset* s, mi_zforms* out);   /* mi_zpack_count_forms for what the set holds now */
 MI_BLOCK void mi_zset_free(mi_zset* s);
 MI_BLOCK int  mi_zset_zpack(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
                             uint32_t flags, mi_zpack** out, uint64_t* first_bad);
@@ -1400,7 +1434,8 @@ MI_BLOCK int  mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* leng
  * codes every chunk it holds again at a requested level and replaces a stored form only where the new one is STRICTLY SMALLER:
  * no chunk ever grows, whatever the level does to it.  No plain pack set, no second set, no second table in the caller's hands.
  *   mi_zset_recode        flags: the level as the coders take it -- MI_ZPACK_LEVEL2, or absent = level 1 -- and optionally
- *                         MI_ZSET_RECODE_VERIFY; any other bit, or s = NULL: MI_ERR_INVALID.  THE RULE: for every digest the
+ *                         MI_ZSET_RECODE_VERIFY and MI_ZPACK_ENTROPY (the candidate is then the level's form with the entropy
+ *                         stage over it, "compressed packs" above); any other bit, or s = NULL: MI_ERR_INVALID.  THE RULE: for every digest the
  *                         set holds, `plain` is what its stored form decodes to (a raw form is its own bytes); the CANDIDATE
  *                         is exactly what the coder of the level stores for `plain` -- the LZ4 block if it is smaller than
  *                         length - (length >> 4), else raw; chunks under 13 bytes are always raw; the stored form is replaced

@@ -21,7 +21,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "Pack", "PackEntry", "PackInfo", "PACK_ENTRY_DTYPE", "PACK_VERIFY", "pack_check",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
-           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK", "ZPACK_LEVEL2", "MEMFS_ZPACK_LEVEL2",
+           "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK", "ZPACK_LEVEL2", "MEMFS_ZPACK_LEVEL2", "ZPACK_ENTROPY", "ZForms",
            "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP", "RecodeInfo", "ZSET_RECODE_VERIFY",
            "IndexPruneInfo", "INDEX_PRUNE_KEEP", "INDEX_PRUNE_DROP"]
 
@@ -168,6 +168,7 @@ class WantInfo(C.Structure):
 
 ZPACK_VERIFY = 0x1                       # mi_pack_compress: the new blob decoded and hashed again on the device
 ZPACK_LEVEL2 = 0x4                       # mi_pack_compress, mi_batch_zpack_chunks: the denser parse, the same block format
+ZPACK_ENTROPY = 0x20                     # mi_pack_compress: the entropy stage over the level's forms (form H where it is smaller)
 
 
 class ZPackEntry(C.Structure):
@@ -187,6 +188,16 @@ class ZPackInfo(C.Structure):
 
 
 ZSET_VERIFY = 0x1                        # mi_zset_add_*: the blob decoded into a scratch and hashed on the device before the set takes it
+
+
+class ZForms(C.Structure):
+    """mi_zforms: entries and stored bytes per form -- [0] raw, [1] one LZ4 block, [2] form H over an LZ4 block, [3] form H over
+    the plain bytes."""
+    _fields_ = [("n", C.c_uint64 * 4), ("stored", C.c_uint64 * 4)]
+    NAMES = ("raw", "lz4", "h_lz4", "h_raw")
+
+    def as_dict(self):
+        return dict((name, (int(self.n[i]), int(self.stored[i]))) for i, name in enumerate(self.NAMES))
 
 
 class ZSetInfo(C.Structure):
@@ -511,6 +522,8 @@ def load_library(rebuild=False):
         "mi_zset_add_zblob": ([vp, vp, u64, vp, u64, C.c_uint32, u64p], C.c_int),
         "mi_zset_add_zpack": ([vp, vp, C.c_uint32], C.c_int),
         "mi_zset_get_info": ([vp, C.POINTER(ZSetInfo)], C.c_int),
+        "mi_zset_count_forms": ([vp, C.POINTER(ZForms)], C.c_int),
+        "mi_zpack_count_forms": ([vp, C.POINTER(ZForms)], C.c_int),
         "mi_zset_free": ([vp], None),
         "mi_zset_zpack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
         "mi_batch_add_zrecipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
@@ -1293,11 +1306,13 @@ class Pack:
         self._eng._check(self._lib.mi_pack_device(self._h, C.byref(p), C.byref(n)))
         return p.value, n.value
 
-    def compress(self, verify=False, level=1):
+    def compress(self, verify=False, level=1, entropy=False):
         """mi_pack_compress: every chunk coded on its own as one LZ4 block (or kept raw) on the device -> ZPack; this pack
-        is not changed.  level=2 (MI_ZPACK_LEVEL2): the denser parse, the same block format"""
+        is not changed.  level=2 (MI_ZPACK_LEVEL2): the denser parse, the same block format.  entropy=True (MI_ZPACK_ENTROPY):
+        the level's form wrapped in a Huffman code where that is smaller by more than a sixteenth (form H)"""
         h = C.c_void_p()
-        self._eng._check(self._lib.mi_pack_compress(self._h, (ZPACK_VERIFY if verify else 0) | _zpack_level_flag(level), C.byref(h)))
+        flags = (ZPACK_VERIFY if verify else 0) | _zpack_level_flag(level) | (ZPACK_ENTROPY if entropy else 0)
+        self._eng._check(self._lib.mi_pack_compress(self._h, flags, C.byref(h)))
         return ZPack(self._eng, h)
 
     def close(self):
@@ -1333,6 +1348,12 @@ class ZPack:
 
     def __len__(self):
         return self.info.n_entries
+
+    def count_forms(self):
+        """mi_zpack_count_forms: ZForms, counted on the device from every stored span's first bytes"""
+        out = ZForms()
+        self._eng._check(self._lib.mi_zpack_count_forms(self._h, C.byref(out)))
+        return out
 
     def entries(self):
         """the entries in blob order: a numpy array of ZPACK_ENTRY_DTYPE"""
@@ -1552,13 +1573,15 @@ class ZSet:
             self._raise(rc)
         return info
 
-    def recode(self, level=2, verify=False, scratch_bytes=0):
+    def recode(self, level=2, verify=False, scratch_bytes=0, entropy=False):
         """mi_zset_recode: code every chunk the set holds again at `level` and replace a stored form only where the new one is
         strictly smaller; the blobs that held a replaced form are rewritten into one new blob and freed, the others are not
         touched.  verify: every entry's bytes are hashed against its digest first, every replaced form again from the new blob.
-        scratch_bytes bounds one round's scratch (0: 256 MiB); the result does not depend on it.  -> RecodeInfo"""
+        scratch_bytes bounds one round's scratch (0: 256 MiB); the result does not depend on it.  entropy=True (MI_ZPACK_ENTROPY):
+        the candidate is the level's form with the entropy stage over it (form H where that is smaller).  -> RecodeInfo"""
         info = RecodeInfo()
-        rc = self._lib.mi_zset_recode(self._h, _zpack_level_flag(level) | (ZSET_RECODE_VERIFY if verify else 0), scratch_bytes, C.byref(info))
+        flags = _zpack_level_flag(level) | (ZSET_RECODE_VERIFY if verify else 0) | (ZPACK_ENTROPY if entropy else 0)
+        rc = self._lib.mi_zset_recode(self._h, flags, scratch_bytes, C.byref(info))
         if rc:
             self._raise(rc)
         return info
@@ -1583,6 +1606,12 @@ class ZSet:
     def info(self):
         out = ZSetInfo()
         self._eng._check(self._lib.mi_zset_get_info(self._h, C.byref(out)))
+        return out
+
+    def count_forms(self):
+        """mi_zset_count_forms: ZForms of what the set holds now"""
+        out = ZForms()
+        self._eng._check(self._lib.mi_zset_count_forms(self._h, C.byref(out)))
         return out
 
     def close(self):

@@ -39,7 +39,9 @@
 #include "mi_gather.h"
 #include "mi_lz4_wave.h"
 #include "mi_zrows.h"
+#include "mi_zentropy.h"
 #include "host_blake2s.h"
+#include "host_huff.h"
 #include "host_lz4.h"
 #include "host_sha256.h"
 
@@ -291,7 +293,7 @@ int add_compressed(mi_packset* s, mi_ctx* c, const char* who, const u8* d_zblob,
         if (first_bad) *first_bad = bad;
         const mi_zpack_entry en = bad < n ? entries[bad] : mi_zpack_entry{};
         return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) does not decode: %s", who, (unsigned long long)bad,
-                    (unsigned long long)en.offset, en.stored, en.length, mi_host::lz4_rule_name(rule));
+                    (unsigned long long)en.offset, en.stored, en.length, mi_host::zrule_name(rule));
     }
     return mi_packset_adopt(s, who, &d_plain, plain_bytes, plain.data(), n, flags, ms_upload, first_bad);
 }
@@ -332,6 +334,11 @@ int mi_zpack_decode_plain(mi_ctx* c, const char* who, const void* d_zblob, const
     HIPCHK(c, hipMemcpyAsync(d_rows.p, entries, n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemcpyAsync(d_poff.p, p_off.data(), n * 8, hipMemcpyHostToDevice, st));
     HIPCHK(c, hipMemsetAsync(d_bad.p, 0xFF, 8, st));
+    // the entropy forms unwrapped first (mi_zentropy.h): d_rows is this call's copy, its form H rows then point at their inner
+    // forms in `unwrap`'s scratch, which lives until the decode below has run.  No form H: one launch, nothing else
+    ZhUnwrap unwrap;
+    const int urc = unwrap.run(c, who, (u64)(size_t)d_zblob, d_rows.as<u64>() + 4, (u32)kEntryWords, d_rows.as<u64>() + 6, (u32)kEntryWords, n);
+    if (urc) return urc;
     HIPCHK(c, hipEventRecord(ev[0], st));
     hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, st, (const u8*)d_zblob, d_rows.as<u64>(), d_poff.as<u64>(), n,
                        d_plain->as<u8>(), d_rule.as<u32>(), d_bad.as<u64>());
@@ -352,6 +359,7 @@ int mi_zpack_decode_plain(mi_ctx* c, const char* who, const void* d_zblob, const
         *bad_out = bad;
         *rule_out = rule;
     }
+    unwrap.merge(bad_out, rule_out);
     return MI_OK;
 }
 
@@ -422,7 +430,8 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     if (!p || !out) return MI_ERR_INVALID;
     static const char* who = "mi_pack_compress";
     mi_ctx* c = mi_pack_ctx(p);
-    if (flags & ~(uint32_t)(MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    if (flags & ~(uint32_t)(MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2 | MI_ZPACK_ENTROPY)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    const bool entropy = (flags & MI_ZPACK_ENTROPY) != 0;
     mi_pack_info pi;
     const void* d_pack = nullptr;
     u64 pack_bytes = 0;
@@ -456,12 +465,17 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     }
     hipStream_t s = c->stream;
     const u64 nb = (n + kPlanTile - 1) / kPlanTile;
-    DevBuf d_rows, d_woff, d_scratch, d_scan, e_src, e_len, e_dst, d_rule, d_got;
+    DevBuf d_rows, d_woff, d_scratch, d_scan, e_src, e_len, e_dst, d_rule, d_got, d_scratch2, d_hsrc, d_rows2;
+    ZhUnwrap unwrap;                                       // (MI_ZPACK_ENTROPY with MI_ZPACK_VERIFY)
     Event ev[7];
     StreamDrain drain{s};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
     hipError_t e = d_scratch.alloc_exact(scratch_bytes);
     if (e != hipSuccess) return does_not_fit(c, who, "the coder's scratch", e, scratch_bytes, n);
+    if (entropy) {                                         // the entropy forms' spans: the same places in a second scratch
+        if ((e = d_scratch2.alloc_exact(scratch_bytes)) != hipSuccess) return does_not_fit(c, who, "the entropy stage's scratch", e, scratch_bytes, n);
+        HIPCHK(c, d_hsrc.ensure(n * 8));
+    }
     HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
     HIPCHK(c, d_woff.ensure(n * 8));
     HIPCHK(c, d_scan.ensure((nb + 8) * 8));
@@ -479,6 +493,8 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
         hipLaunchKernelGGL(zpack_encode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, (const u8*)d_pack, d_rows.as<u64>(), d_woff.as<u64>(),
                            d_scratch.as<u8>(), n);
     }
+    if (entropy)                                           // behind the coder: form H where it is smaller by more than a sixteenth (mi_zentropy.hip)
+        zh_encode_enqueue(c, d_pack, d_rows.as<u64>(), d_woff.as<u64>(), d_scratch.p, d_scratch2.p, d_hsrc.as<u64>(), n, wave_grid(n));
     HIPCHK(c, hipEventRecord(ev[1], s));
     hipLaunchKernelGGL(zpack_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), n, block_bytes, totals);
     hipLaunchKernelGGL(zpack_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, s, block_bytes, nb, totals);
@@ -511,6 +527,7 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
     HIPCHK(c, hipEventRecord(ev[3], s));
     hipLaunchKernelGGL(zpack_place_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, s, d_rows.as<u64>(), d_woff.as<u64>(), n, block_bytes,
                        (u64)(size_t)d_pack, (u64)(size_t)d_scratch.p, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>());
+    if (entropy) zh_sources_enqueue(c, d_hsrc.as<u64>(), e_src.as<u64>(), n);          // a form H row: from the second scratch
     hipLaunchKernelGGL(zpack_gather_kernel, dim3((u32)n_tiles), dim3(kGatherWG), 0, s, e_src.as<u64>(), e_len.as<u64>(), e_dst.as<u64>(), n, blob_bytes,
                        mine.z->blob.as<u8>());
     HIPCHK(c, hipEventRecord(ev[4], s));
@@ -520,7 +537,18 @@ int mi_pack_compress(const mi_pack* p, uint32_t flags, mi_zpack** out) {
         std::vector<u64> lens(n);
         for (u64 k = 0; k < n; ++k) lens[k] = rows[k].length;
         HIPCHK(c, hipMemcpyAsync(e_len.p, lens.data(), n * 8, hipMemcpyHostToDevice, s));
-        hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, mine.z->blob.as<u8>(), d_rows.as<u64>(), d_woff.as<u64>(), n,
+        const u64* v_rows = d_rows.as<u64>();
+        if (entropy) {                                     // a COPY of the rows is unwrapped: d_rows are the zpack's entries
+            HIPCHK(c, d_rows2.ensure(n * sizeof(mi_zpack_entry)));
+            HIPCHK(c, hipMemcpyAsync(d_rows2.p, d_rows.p, n * sizeof(mi_zpack_entry), hipMemcpyDeviceToDevice, s));
+            if ((rc = unwrap.run(c, who, (u64)(size_t)mine.z->blob.p, d_rows2.as<u64>() + 4, (u32)kEntryWords, d_rows2.as<u64>() + 6, (u32)kEntryWords, n)))
+                return rc;
+            if (unwrap.bad != kZNone)
+                return fail(c, MI_ERR_IO, "%s: entry %llu: the entropy form just coded does not unwrap on the device: %s", who,
+                            (unsigned long long)unwrap.bad, mi_host::zrule_name(unwrap.rule));
+            v_rows = d_rows2.as<u64>();
+        }
+        hipLaunchKernelGGL(zpack_decode_kernel, dim3(wave_grid(n)), dim3(64), 0, s, mine.z->blob.as<u8>(), v_rows, d_woff.as<u64>(), n,
                            d_scratch.as<u8>(), d_rule.as<u32>(), totals + kZTotBad);
         HIPCHK(c, hipEventRecord(ev[6], s));
         const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
@@ -589,6 +617,20 @@ void mi_zpack_free(mi_zpack* z) {
     if (z) zpack_delete(z);
 }
 
+int mi_zpack_count_forms(const mi_zpack* z, mi_zforms* out) {
+    if (!z || !out) return MI_ERR_INVALID;
+    mi_ctx* c = z->ctx;
+    memset(out, 0, sizeof *out);
+    const u64 n = z->info.n_entries;
+    if (!n) return MI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    DevBuf d_rows;
+    StreamDrain drain{c->stream};
+    HIPCHK(c, d_rows.ensure(n * sizeof(mi_zpack_entry)));
+    HIPCHK(c, hipMemcpyAsync(d_rows.p, z->h_rows.data(), n * sizeof(mi_zpack_entry), hipMemcpyHostToDevice, c->stream));
+    return zh_count_forms(c, (u64)(size_t)z->blob.p, d_rows.as<u64>() + 4, (u32)kEntryWords, d_rows.as<u64>() + 6, (u32)kEntryWords, n, nullptr, out);
+}
+
 int mi_packset_add_zblob(mi_packset* s, const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n, uint32_t flags,
                          uint64_t* first_bad) {
     if (first_bad) *first_bad = 0;
@@ -651,7 +693,7 @@ int mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* 
         return MI_ERR_INVALID;
     }
     const u8* base = (const u8*)blob;
-    std::vector<u8> plain;
+    std::vector<u8> plain, inner;                      // (inner: what an entropy form wraps, host_huff.h)
     u64 hash_bad = kZNone;
     for (u64 k = 0; k < n; ++k) {
         const mi_zpack_entry& en = entries[k];
@@ -660,7 +702,8 @@ int mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* 
         bool ok = true;
         if (en.stored < en.length) {
             plain.resize(en.length);
-            ok = mi_host::lz4_block_decode(src, en.stored, plain.data(), en.length) == mi_host::kLz4Ok;
+            if (mi_host::is_form_h(src, en.stored, en.length) && en.length <= mi_host::kHuffMaxChunk) inner.resize(en.length);
+            ok = mi_host::zform_decode(src, en.stored, plain.data(), en.length, inner.data()) == mi_host::kLz4Ok;
             chunk = plain.data();
         }
         for (u64 i = en.stored; i < round16(en.stored); ++i) ok = ok && src[i] == 0;

@@ -50,6 +50,7 @@
 #include "mi_lz4_wave.h"
 #include "mi_zrows.h"
 #include "mi_zset_local.h"
+#include "mi_zentropy.h"
 
 using namespace mi;
 
@@ -445,8 +446,8 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     mi_ctx* c = nullptr;
     int rc = mi_zset_ctx(s, who, &c);                          // MI_ERR_STATE with the first message for a set in its failed state
     if (rc) return rc;
-    if (flags & ~(uint32_t)(MI_ZSET_RECODE_VERIFY | MI_ZPACK_LEVEL2)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
-    const bool verify = (flags & MI_ZSET_RECODE_VERIFY) != 0, level2 = (flags & MI_ZPACK_LEVEL2) != 0;
+    if (flags & ~(uint32_t)(MI_ZSET_RECODE_VERIFY | MI_ZPACK_LEVEL2 | MI_ZPACK_ENTROPY)) return fail(c, MI_ERR_INVALID, "%s: unknown flags %#x", who, flags);
+    const bool verify = (flags & MI_ZSET_RECODE_VERIFY) != 0, level2 = (flags & MI_ZPACK_LEVEL2) != 0, entropy = (flags & MI_ZPACK_ENTROPY) != 0;
     mi_recode_info ri = {};
     const u64 n = s->table.count, cap = s->table.cap, n_blobs = s->blobs.size();
     ri.n_digests = n;
@@ -463,6 +464,8 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
 
     DevBuf d_bases, d_mark, d_tot, d_scan, d_rows, d_rule, d_cand, d_new, d_blob_of, d_rep, d_hash, d_got, d_scratch;
     DevBuf d_scan2, d_list, d_addr, d_recs, d_vstr, d_got2, new_blob;
+    DevBuf d_urows, d_scratch2, d_vrows;                       // the entropy stage's (mi_zentropy.h): unwrapped rows, form H's scratch, the recheck's rows
+    ZhUnwrap unwrap, unwrap2;                                  // ... the held forms' inner forms; the replaced forms', for the recheck
     std::vector<DevBuf> pieces;                                // the staging pieces, one a round that replaces something
     SlotTable fresh;                                           // the table the records go into: this call's, scratch and all
     fresh.sum_bytes = true;
@@ -530,6 +533,23 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     if (h[kRTotRows] != n)
         return fail(c, MI_ERR_STATE, "%s: the set holds %llu digests, the scan counted %llu", who, (unsigned long long)n, (unsigned long long)h[kRTotRows]);
     ri.live_before = ri.live_after = h[kRTotLive];
+    // the entropy forms the set holds (mi_zentropy.h) are unwrapped first, into a scratch of the call's: the decode, the coder and
+    // the staging read a row through u_src / u_word, COPIES in which a form H row points at its inner form (kind 1: an LZ4 row,
+    // kind 2: a raw row); everything that compares, counts or exports reads r_src / r_word, the set's own words.  A row's place in a
+    // round's scratch comes from r_word: a kind 2 row has room for plain bytes that it does not use.  No form H: no copy
+    mi_zforms forms;
+    if ((rc = zh_count_forms(c, 0, r_src, 1u, r_word, 1u, n, nullptr, &forms))) return rc;
+    const bool holds_h = forms.n[2] + forms.n[3] != 0;
+    const u64* u_src = r_src;
+    const u64* u_word = r_word;
+    if (holds_h) {
+        RECODE_ALLOC(d_urows, 2 * n * 8, "the unwrapped rows");
+        HIPCHK(c, hipMemcpyAsync(d_urows.p, r_src, 2 * n * 8, hipMemcpyDeviceToDevice, st));      // (r_src and r_word lie side by side)
+        if ((rc = unwrap.run(c, who, 0, d_urows.as<u64>(), 1u, d_urows.as<u64>() + n, 1u, n))) return rc;
+        extra += unwrap.inner_bytes;
+        u_src = d_urows.as<u64>();
+        u_word = u_src + n;
+    }
 
     // ---- the rounds: rows [r0, r1) whose need is at most the bound; a row that needs more is a round of its own -------------------
     std::vector<Round> rounds;
@@ -544,6 +564,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     }
     ri.n_rounds = rounds.size();
     RECODE_ALLOC(d_scratch, scratch_max, "the scratch");
+    if (entropy) RECODE_ALLOC(d_scratch2, scratch_max, "the entropy stage's scratch");
     u8* scratch = d_scratch.as<u8>();
     const auto hash_items = (c->cfg.flags & MI_FLAG_CHUNK_BLAKE2S) ? launch_blake2s_items : launch_sha256_items;
 
@@ -553,15 +574,18 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
         r.rep_before = n_rep;
         r.staged_before = staged;
         HIPCHK(c, hipEventRecord(ev[0], st));
-        hipLaunchKernelGGL(zrecode_decode_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, r_src, r_word, r_off, r.r0, nr, r.base_off, scratch, r_rule,
+        hipLaunchKernelGGL(zrecode_decode_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, u_src, u_word, r_off, r.r0, nr, r.base_off, scratch, r_rule,
                            h_off, h_len);
+        if (holds_h) zh_rules_merge_enqueue(c, unwrap.rules(), r_rule, r.r0, nr);
         HIPCHK(c, hipEventRecord(ev[1], st));
         if (level2)
-            hipLaunchKernelGGL(zrecode_encode_l2_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, r_src, r_word, r_off, r_rule, r.r0, nr, r.base_off,
+            hipLaunchKernelGGL(zrecode_encode_l2_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, u_src, u_word, r_off, r_rule, r.r0, nr, r.base_off,
                                scratch, r_cand);
         else
-            hipLaunchKernelGGL(zrecode_encode_l1_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, r_src, r_word, r_off, r_rule, r.r0, nr, r.base_off,
+            hipLaunchKernelGGL(zrecode_encode_l1_kernel, dim3(wave_grid(nr)), dim3(64), 0, st, u_src, u_word, r_off, r_rule, r.r0, nr, r.base_off,
                                scratch, r_cand);
+        if (entropy)                                           // form H over the candidates, where it is smaller by more than a sixteenth
+            zh_recode_encode_enqueue(c, u_src, u_word, r_off, r_rule, r.r0, nr, r.base_off, scratch, d_scratch2.p, r_cand, wave_grid(nr));
         HIPCHK(c, hipEventRecord(ev[2], st));
         if (verify)                                            // base 0: the offsets are absolute device addresses
             hash_items(kShaBlobs, (const u8*)nullptr, h_off + r.r0, h_len + r.r0, nullptr, (u32)nr, nullptr, c->heads.as<u32>(), nullptr, true,
@@ -595,7 +619,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
             pieces.emplace_back();
             RECODE_ALLOC(pieces.back(), piece_bytes, "a staging piece");
             HIPCHK(c, hipEventRecord(ev[0], st));
-            hipLaunchKernelGGL(zrecode_stage_kernel, dim3(wave_grid(r.n_rep)), dim3(64), 0, st, rep_rows + r.rep_before, r.n_rep, r_word, r_off, r_new,
+            hipLaunchKernelGGL(zrecode_stage_kernel, dim3(wave_grid(r.n_rep)), dim3(64), 0, st, rep_rows + r.rep_before, r.n_rep, u_word, r_off, r_new,
                                r.base_off, scratch, r.staged_before, pieces.back().as<u8>(), r_stage);
             HIPCHK(c, hipEventRecord(ev[1], st));
             HIPCHK(c, hipStreamSynchronize(st));               // (the events are the next round's)
@@ -619,7 +643,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
         return fail(c, MI_ERR_IO, "%s: %llu of %llu entries do not decode to bytes that hash to their digest (%llu of them do not decode at all); "
                     "one of them: digest %s, %s%s -- the set was fed a damaged blob without MI_ZSET_VERIFY; the set is unchanged", who,
                     (unsigned long long)h[kRTotBad], (unsigned long long)n, (unsigned long long)ri.n_undecodable, hex32(dg).c_str(),
-                    rule ? "the stored form does not decode: " : "the decoded bytes hash to another digest", rule ? mi_host::lz4_rule_name(rule) : "");
+                    rule ? "the stored form does not decode: " : "the decoded bytes hash to another digest", rule ? mi_host::zrule_name(rule) : "");
     }
     ri.n_recoded = n_rep;
     ri.n_raw_recoded = h[kRTotRawRecoded];
@@ -670,6 +694,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     if (verify) {
         RECODE_ALLOC(d_vstr, 2 * n_rep * 8, "the recheck's strings");
         RECODE_ALLOC(d_got2, n_rep * 32, "the recheck's digests");
+        if (entropy) RECODE_ALLOC(d_vrows, 2 * n_rep * 8, "the recheck's rows");
     }
     ri.peak_extra_bytes = extra;
 
@@ -705,10 +730,20 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     if (verify) {
         u64* v_off = d_vstr.as<u64>();
         u64* v_len = v_off + n_rep;
+        u64* v_src = entropy ? d_vrows.as<u64>() : nullptr;
+        u64* v_word = entropy ? v_src + n_rep : nullptr;
+        if (entropy) {                                         // the replaced forms may be form H: their rows, unwrapped from the new blob
+            zh_rep_rows_enqueue(c, rep_rows, n_rep, r_word, r_new, r_addr, v_src, v_word);
+            if ((rc = unwrap2.run(c, who, 0, v_src, 1u, v_word, 1u, n_rep))) return rc;
+        }
         for (const Round& r : rounds) {
             if (!r.n_rep) continue;
-            hipLaunchKernelGGL(zrecode_redecode_kernel, dim3(wave_grid(r.n_rep)), dim3(64), 0, st, rep_rows + r.rep_before, r.n_rep, r_word, r_off, r_new, r_addr,
-                               r.base_off, scratch, v_off + r.rep_before, v_len + r.rep_before, tot);
+            if (entropy)
+                zh_redecode_enqueue(c, rep_rows + r.rep_before, r.n_rep, v_src + r.rep_before, v_word + r.rep_before, r_off, r.base_off, scratch,
+                                    v_off + r.rep_before, v_len + r.rep_before, tot + kRTotBad2, tot + kRTotFirstBad2, wave_grid(r.n_rep));
+            else
+                hipLaunchKernelGGL(zrecode_redecode_kernel, dim3(wave_grid(r.n_rep)), dim3(64), 0, st, rep_rows + r.rep_before, r.n_rep, r_word, r_off, r_new,
+                                   r_addr, r.base_off, scratch, v_off + r.rep_before, v_len + r.rep_before, tot);
             hash_items(kShaBlobs, (const u8*)nullptr, v_off + r.rep_before, v_len + r.rep_before, nullptr, (u32)r.n_rep, nullptr, c->heads.as<u32>(), nullptr,
                        true, d_got2.as<u8>() + 32 * r.rep_before, c->sha, c->prop.multiProcessorCount, r.bytes, st);
         }

@@ -31,6 +31,7 @@
 #include "mi_lz4_wave.h"
 #include "mi_plan.h"
 #include "mi_zset_local.h"
+#include "mi_zentropy.h"
 
 #include <string.h>
 
@@ -296,7 +297,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
             const mi_zpack_entry en = bad < n ? entries[bad] : mi_zpack_entry{};
             if (rule)
                 return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) does not decode: %s", who,
-                            (unsigned long long)bad, (unsigned long long)en.offset, en.stored, en.length, mi_host::lz4_rule_name(rule));
+                            (unsigned long long)bad, (unsigned long long)en.offset, en.stored, en.length, mi_host::zrule_name(rule));
             return fail(c, MI_ERR_INVALID, "%s: entry %llu (offset %llu, %u bytes stored for %u) does not hash to its digest on the device", who,
                         (unsigned long long)bad, (unsigned long long)en.offset, en.stored, en.length);
         }
@@ -456,6 +457,18 @@ int mi_zset_entries(const mi_zset* s, uint8_t* digests, uint32_t* lengths, uint3
     return MI_OK;
 }
 
+int mi_zset_count_forms(const mi_zset* s, mi_zforms* out) {
+    if (!s || !out) return MI_ERR_INVALID;
+    mi_ctx* c = s->ctx;
+    memset(out, 0, sizeof *out);
+    const int rc = set_state(s, "mi_zset_count_forms");
+    if (rc) return rc;
+    if (!s->table.count) return MI_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const u64* slots = s->table.slots.as<u64>();           // a slot: digest 4 | the span's address | length, stored
+    return zh_count_forms(c, 0, slots + 4, (u32)kSlotWords, slots + 5, (u32)kSlotWords, s->table.cap, s->table.tags.as<u64>(), out);
+}
+
 int mi_zset_get_info(const mi_zset* s, mi_zset_info* out) {
     if (!s || !out) return MI_ERR_INVALID;
     const int rc = set_state(s, "mi_zset_get_info");
@@ -591,7 +604,7 @@ int mi_zset_zpack(const mi_zset* set, const uint8_t* digests, const uint32_t* le
                         "set was fed a damaged blob without MI_ZSET_VERIFY", who, (unsigned long long)row.chunk_index, (unsigned long long)bad,
                         row.stored, row.length, (unsigned long long)row.offset,
                         rule ? "the stored form does not decode: " : "the decoded bytes do not hash to the requested digest",
-                        rule ? mi_host::lz4_rule_name(rule) : "", hex32(row.digest).c_str());
+                        rule ? mi_host::zrule_name(rule) : "", hex32(row.digest).c_str());
         }
     }
     mi_zpack_set_result(mine.z, stored_bytes, n_raw, chunk_bytes, (flags & MI_ZPACK_VERIFY) ? 1u : 0u, (double)ms + ms2, ms_verify, ms_decode);
@@ -702,6 +715,11 @@ int mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, con
                         "bytes, the recipe states %u", who, (unsigned long long)f, (unsigned long long)k, (unsigned long long)bad, dg.c_str(),
                         (u32)w, lengths[bad]);
         }
+        // the entropy forms unwrapped first (mi_zentropy.h): d_src and d_word are this call's, their form H rows then point at the
+        // inner forms in `unwrap`'s scratch, which lives until the fused kernel has run.  No form H: one launch, nothing else
+        ZhUnwrap unwrap;
+        rc = unwrap.run(c, who, 0, d_src.as<u64>(), 1u, d_word.as<u64>(), 1u, n_rows);
+        if (rc) return rc;
         // the fused kernel: one wave a row, at most 65 536 of them
         const u32 grid = (u32)std::min<u64>(n_rows, 65536);
         HIPCHK(c, hipMemsetAsync(cell, 0xFF, 8, s));
@@ -727,15 +745,18 @@ int mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_files, con
             HIPCHK(c, hipEventElapsedTime(&ms, ev[2], ev[3]));
             st.ms_verify = ms;
         }
-        if (h[0] != kQNone) {                          // a stored form that does not decode: what an unverified set costs its reader
-            const u64 bad = h[0];
+        u64 lz_bad = h[0];
+        u32 lz_rule = 0;
+        if (lz_bad != kQNone && lz_bad < n_rows) HIPCHK(c, hipMemcpy(&lz_rule, d_rule.as<u32>() + lz_bad, 4, hipMemcpyDeviceToHost));
+        unwrap.merge(&lz_bad, &lz_rule);
+        if (lz_bad != kQNone) {                        // a stored form that does not decode: what an unverified set costs its reader
+            const u64 bad = lz_bad;
             u64 f = 0, k = 0;
-            u32 rule = 0;
+            const u32 rule = lz_rule;
             locate(bad, &f, &k);
-            HIPCHK(c, hipMemcpy(&rule, d_rule.as<u32>() + bad, 4, hipMemcpyDeviceToHost));
             return fail(c, MI_ERR_INVALID, "%s: file %llu, row %llu (row %llu of the call), digest %s: the stored form does not decode: %s", who,
                         (unsigned long long)f, (unsigned long long)k, (unsigned long long)bad, hex32(digests + 32 * bad).c_str(),
-                        mi_host::lz4_rule_name(rule));
+                        mi_host::zrule_name(rule));
         }
         if (h[1] != kQNone) {
             const u64 bad = h[1];
