@@ -11,8 +11,9 @@ of zentropy_rows_cases.py (whose conditions tests/test_host_chunk_zentropy_rows.
   5. the keep rule h < under - (under >> 4) on its line, in the coder and in the recode.
 
 Everything is compared with zentropy_cases.py's model byte for byte: there are no tolerances.  Sections 1 to 3 run at level 1
-(300 rows of section 1 also at level 2).  NOT covered here, for their sizes: the second trip of the encode kernels (more than
-2^20 rows) and the carry between the rounds of plan_block_offsets (more than 524 288 rows)."""
+(300 rows of section 1 also at level 2).  NOT covered here, for their sizes, and covered by tests/test_gpu_chunk_store_rows.py
+and tests/test_gpu_chunk_store_rows_batch.py: the second trip of the encode kernels (more than 2^20 rows) and the carry between
+the rounds of plan_block_offsets (more than 524 288 rows)."""
 import os
 import sys
 import time

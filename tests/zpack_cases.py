@@ -46,14 +46,19 @@ def sequence(literals, offset=None, match_len=None):
     return out
 
 
-def parse(data):
-    """-> the sequences of one chunk as (literal run, offset, match length) triples; the last is (run, None, None)"""
+def parse(data, table=None):
+    """-> the sequences of one chunk as (literal run, offset, match length) triples; the last is (run, None, None).  table: None
+    for the kernel's own, 4 096 zeros for every chunk; an int64 array of TABLE positions is used IN PLACE instead -- the caller
+    sees what the parse left in it, and may begin another chunk's parse on it (what a coder that does not clear its table would
+    do: tests/store_rows_cases.py's wrong model)"""
     n = len(data)
     a = np.frombuffer(bytes(data), dtype=np.uint8)
     assert n >= MIN_CHUNK
     quad = (a[:-3].astype(np.uint32) | a[1:-2].astype(np.uint32) << 8 | a[2:-1].astype(np.uint32) << 16 | a[3:].astype(np.uint32) << 24)
     hashes = ((quad.astype(np.uint64) * 2654435761 & 0xFFFFFFFF) >> 20).astype(np.int64)
-    table = np.zeros(TABLE, dtype=np.int64)
+    if table is None:
+        table = np.zeros(TABLE, dtype=np.int64)
+    assert table.shape == (TABLE,) and table.dtype == np.int64
     last, limit = n - 12, n - 5
     p = anchor = 0
     out = []
