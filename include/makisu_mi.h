@@ -1266,8 +1266,9 @@ MI_BLOCK int  mi_packset_add_zpack(mi_packset* s, const mi_zpack* z, uint32_t fl
 MI_BLOCK int  mi_zpack_check(const void* blob, uint64_t blob_bytes, const mi_zpack_entry* entries, uint64_t n,
                              uint32_t alg, uint64_t* first_bad);
 /* the census of a zpack's (a compressed pack set's) stored forms, counted on the device from every span's first bytes: [0] raw,
- * [1] one LZ4 block, [2] form H over an LZ4 block, [3] form H over the plain bytes.  Blocking, on the ctx stream.  The info
- * structs do not change */
+ * [1] one LZ4 block, [2] form H over an LZ4 block, [3] form H over the plain bytes.  Nothing is decoded: a span an unverified set
+ * holds that begins like form H counts by its kind byte alone, 1 under [2] and ANY other value under [3].  Blocking, on the ctx
+ * stream.  The info structs do not change */
 typedef struct {               /* 64 bytes */
     uint64_t n[4];             /* entries (digests) of each form */
     uint64_t stored[4];        /* the sum of their stored sizes */

@@ -52,7 +52,9 @@ static __device__ __forceinline__ u32 zh_form(const u8* src, u64 word) {
     const u64 len = word & 0xFFFFFFFFull, stored = word >> 32;
     if (stored >= len) return kZhRaw;
     if (src[0] != 0) return kZhLz4;
-    return stored >= 2 && src[1] == mi_host::kHuffKindRaw ? kZhOverRaw : kZhOverLz4;     // (a bad kind: rule 8 says so at the unwrap)
+    // (a bad kind: rule 8 says so at the unwrap.  The census, makisu_mi.h "the census of a zpack's ... stored forms": a span that begins
+    // like form H counts by its kind byte alone, 1 under [2], any other value -- or no kind byte at all, stored == 1 -- under [3])
+    return stored >= 2 && src[1] == mi_host::kHuffKindLz4 ? kZhOverLz4 : kZhOverRaw;
 }
 
 // what a form H row takes in the unwrap's scratch: round16(inner length) if the header's length obeys rule 8, else 0 (the row is

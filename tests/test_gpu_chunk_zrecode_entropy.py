@@ -106,6 +106,28 @@ def test_a_set_of_form_h_from_compress_recodes_to_the_same_forms(level1_set):
             held = want
 
 
+def test_the_census_counts_a_form_h_with_a_bad_kind_as_the_model_does():
+    """found by the store walks (test_gpu_chunk_store_walk.py, the damaged kind): a span that begins like form H with a kind byte
+    that is neither 1 nor 2 -- only an unverified add brings one -- was counted under [2] by the device and under [3] by
+    zentropy_cases.form_of.  The header now says [3]; the set's census and the cut's agree with the model"""
+    rows = [(entries, blob) for name, entries, blob, _, _ in ze.malformed_zpacks() if name in ("kind 0, behind good entries", "kind 3, behind good entries")]
+    assert len(rows) == 2
+    with M.Engine() as e:
+        for entries, blob in rows:
+            want = ze.count_forms(entries, blob)
+            assert want[3][0] == 2 and want[2][0] == 0                              # the good form H over plain, and the bad kind
+            with e.zset() as zs:
+                zs.add_zblob(blob, entries)
+                assert _forms(zs.count_forms()) == want
+                with zs.zpack(np.ascontiguousarray(entries["digest"])) as z:
+                    assert _forms(z.count_forms()) == want
+        # one stored byte, 0x00, for a chunk of 5: there is no kind byte at all (form_of has no answer); the header says [3]
+        entries, blob = zc.build_zpack([zc._entry(zc.GOOD_STREAM, 34, zc.GOOD_PLAIN), zc._entry(b"\0", 5)])
+        with e.zset() as zs:
+            zs.add_zblob(blob, entries)
+            assert _forms(zs.count_forms()) == [[0, 0], [1, 31], [0, 0], [1, 1]]
+
+
 def test_a_malformed_form_h_in_an_unverified_set_is_counted_kept_and_named_under_verify():
     words = {8: "an entropy form with a bad header", 9: "an entropy form whose code lengths", 10: "an entropy form whose stream sizes",
              11: "an entropy form with a stream that ends early", 7: "a pad byte behind the stored span", 2: "a match offset beyond", 6: "short of the chunk's length"}
