@@ -1340,6 +1340,49 @@ MI_BLOCK int  mi_batch_add_zrecipes(mi_batch* b, const mi_zset* set, uint64_t n_
                                     const uint8_t* digests, const uint32_t* lengths, const uint64_t* user_tags,
                                     uint32_t flags, mi_recipe_stats* stats_out);
 
+/* ---- a compressed set cut for a reader that knows less than the set ------------------------------------------------ *
+ * A set that was densified at rest holds form H almost everywhere, and mi_zset_zpack moves form H verbatim.  These two cuts take
+ * the same request and follow mi_zset_zpack's contract word for word -- host digests and optional lengths, fewer than 2^32
+ * rows, every distinct digest once in order of first occurrence, chunk_index = the request row of the first occurrence, n = 0:
+ * the empty result; MI_ERR_INVALID with *first_bad and mi_zset_zpack's message words for a digest the set lacks, a stated length
+ * of 0 or another one than the set's; MI_ERR_STATE with the first message for a sticky set; a blob that does not fit:
+ * MI_ERR_NOMEM naming both sizes; the result owns a copy, survives mi_zset_free and is a child of the ctx; blocking, on the ctx
+ * stream -- except where stated here.  THE SET NEVER CHANGES: mi_zset_get_info, _get_usage, _entries and _count_forms answer
+ * the same before and after, on success and on every failure.  Neither call builds a plain set, a table or an intermediate zpack.
+ *   mi_zset_zpack_unwrapped  THE CUT WITHOUT FORM H, for a reader built before the entropy stage.  An entry whose stored form in
+ *                         the set is form H carries its INNER form: kind 1, the LZ4 block, stored = the inner length; kind 2,
+ *                         the chunk's plain bytes, stored == length, a raw entry.  Every other entry is moved verbatim.  Entry k
+ *                         lies at the sum of the NEW stored sizes before it, each rounded up to 16, the pads zero; the info
+ *                         carries stored_bytes, n_raw and chunk_bytes of the new blob, ms_encode is 0, ms_compact the device
+ *                         time of lookup, sizing, scan, unwrap and gather.  The stage wraps a chunk's FINISHED stored form, so
+ *                         for forms the coders made the result is byte for byte, blob and entries, what mi_zset_zpack gives
+ *                         from a set that was fed the same chunks coded at the same level WITHOUT MI_ZPACK_ENTROPY.  A
+ *                         requested form H row that does not unwrap (rules 8..11, and 7 for the pad behind its span) is
+ *                         MI_ERR_INVALID naming the request row, the digest and the rule, the smallest such row in *first_bad,
+ *                         and no zpack is returned; the inner LZ4 block is MOVED, not decoded, and rows that are moved verbatim
+ *                         are not looked at, as in mi_zset_zpack.  MI_ZPACK_VERIFY (the only flag) decodes and hashes the new
+ *                         blob against the requested digests as mi_zset_zpack does, with its MI_ERR_IO message.  A request
+ *                         that meets no form H is byte for byte mi_zset_zpack's answer; where form H is met, each such row is
+ *                         unwrapped by one wave straight to its place in the new blob -- the inner length stands in the form's
+ *                         header, so sizes and offsets come first and there is no scratch of inner forms.
+ *   mi_zset_pack          THE PLAIN CUT, for a reader that knows no compression: mi_packset_pack's contract word for word over
+ *                         a compressed set, an ordinary mi_pack -- length is the set's, entry k at the sum of the lengths
+ *                         before it, each rounded up to 16, the pads zero, reserved 0; everything that takes a pack takes it --
+ *                         byte for byte, blob and entries, what mi_packset_pack gives from a plain set fed the same zpacks.  One
+ *                         launch, one wave an entry, decoded straight to its place: a raw row is copied, an LZ4 row decoded,
+ *                         form H over raw unwrapped into the pack, form H over LZ4 unwrapped into a per-call scratch and decoded
+ *                         from there by the same wave.  The scratch holds the inner lengths of the requested kind-1 rows only
+ *                         (each rounded up to 64); if it does not fit: MI_ERR_NOMEM naming its size, nothing has changed.  A row
+ *                         that does not decode under mi_zpack_check's rules (1..11, the non-zero pad among them) is
+ *                         MI_ERR_INVALID naming the request row, the digest and the rule, the smallest bad row in *first_bad;
+ *                         on one row an unwrap rule (8..11) comes before the inner block's (1..6) before the pad's (7).
+ *                         MI_SUBPACK_VERIFY (the only flag) hashes the new blob with the ctx's algorithm against the requested
+ *                         digests: MI_ERR_IO as in mi_packset_pack. */
+MI_BLOCK int  mi_zset_zpack_unwrapped(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                                      uint32_t flags /* MI_ZPACK_VERIFY only */, mi_zpack** out, uint64_t* first_bad);
+MI_BLOCK int  mi_zset_pack(const mi_zset* s, const uint8_t* digests, const uint32_t* lengths, uint64_t n,
+                           uint32_t flags /* MI_SUBPACK_VERIFY only */, mi_pack** out, uint64_t* first_bad);
+
 /* ---- zpacks straight from the arena; a compressed set asked what it lacks ------------------------------------------ *
  * The producing side without the plain detour: the chunks of a batch are coded WHERE THEY LIE, so a commit hands a zpack over
  * without the plain blob, its gather and its hashing pass; and the pulling side asks the compressed set it keeps.  With both,

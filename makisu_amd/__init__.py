@@ -526,6 +526,8 @@ def load_library(rebuild=False):
         "mi_zpack_count_forms": ([vp, C.POINTER(ZForms)], C.c_int),
         "mi_zset_free": ([vp], None),
         "mi_zset_zpack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
+        "mi_zset_zpack_unwrapped": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
+        "mi_zset_pack": ([vp, vp, vp, u64, C.c_uint32, C.POINTER(vp), u64p], C.c_int),
         "mi_batch_add_zrecipes": ([vp, vp, u64, vp, vp, vp, vp, C.c_uint32, C.POINTER(RecipeStats)], C.c_int),
         "mi_batch_zpack_chunks": ([vp, vp, u64, C.c_uint32, C.POINTER(vp)], C.c_int),
         "mi_memfs_take_zpack": ([vp, C.POINTER(vp)], C.c_int),
@@ -1540,6 +1542,32 @@ class ZSet:
         if rc:
             self._raise(rc, bad.value)
         return ZPack(self._eng, h)
+
+    def zpack_unwrapped(self, digests, lengths=None, verify=False):
+        """mi_zset_zpack_unwrapped: ZSet.zpack for a reader built before the entropy stage -- an entry the set holds as form H
+        carries its inner form (the LZ4 block, or the plain bytes as a raw entry), every other entry is moved as it is.  A
+        failure raises MiError with .first_bad = the request row."""
+        d, ln = PackSet._request(digests, lengths)
+        n = len(d)
+        h, bad = C.c_void_p(), C.c_uint64()
+        rc = self._lib.mi_zset_zpack_unwrapped(self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n,
+                                               ZPACK_VERIFY if verify else 0, C.byref(h), C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+        return ZPack(self._eng, h)
+
+    def pack(self, digests, lengths=None, verify=False):
+        """mi_zset_pack: PackSet.pack over the compressed set -- a plain Pack of every distinct requested digest once, in order
+        of first occurrence, every stored form decoded straight to its place.  A failure raises MiError with .first_bad = the
+        request row."""
+        d, ln = PackSet._request(digests, lengths)
+        n = len(d)
+        h, bad = C.c_void_p(), C.c_uint64()
+        rc = self._lib.mi_zset_pack(self._h, d.ctypes.data if n else None, ln.ctypes.data if ln is not None and n else None, n,
+                                    SUBPACK_VERIFY if verify else 0, C.byref(h), C.byref(bad))
+        if rc:
+            self._raise(rc, bad.value)
+        return Pack(self._eng, h)
 
     def missing(self, digests, lengths=None):
         """mi_zset_missing: PackSet.missing over the compressed set -- which of the request's digests (n x 32 bytes; lengths:

@@ -330,6 +330,16 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
 
 }  // namespace
 
+namespace mi {
+
+// (hidden: mi_zset_local.h) for mi_zserve.hip's MI_ZPACK_VERIFY
+int zset_verify_stored(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpack_entry* entries, const u64* d_rows, u64 n, u64* bad, u32* rule,
+                       double* ms_decode) {
+    return verify_stored(c, who, d_zblob, entries, d_rows, n, bad, rule, ms_decode);
+}
+
+}  // namespace mi
+
 extern "C" {
 
 int mi_zset_create(mi_ctx* c, uint64_t entries_hint, mi_zset** out) {

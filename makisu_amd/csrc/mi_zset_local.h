@@ -62,6 +62,13 @@ struct ZsetBlob {
     u64 bytes = 0;
 };
 
+// mi_zset.hip, for mi_zserve.hip: MI_ZSET_VERIFY / MI_ZPACK_VERIFY over a compressed blob on the device, its entries on the host
+// (structurally sound) and on the device (d_rows: what the digests are held against), n > 0 -- decoded into a scratch laid out as
+// a plain pack, hashed there.  *bad = the smallest entry that does not decode (then *rule says why) or, if all decode, that does
+// not hash (*rule = 0); ~0: none.  Blocking; the scratch is gone when it returns
+MI_LOCAL int zset_verify_stored(mi_ctx* c, const char* who, const void* d_zblob, const mi_zpack_entry* entries, const u64* d_rows, u64 n, u64* bad,
+                                u32* rule, double* ms_decode);
+
 }  // namespace mi
 
 struct mi_zset {
