@@ -1532,6 +1532,66 @@ typedef struct {               /* 152 bytes */
 } mi_recode_info;
 MI_BLOCK int  mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode_info* info);
 
+/* ---- ageing a compressed set ---------------------------------------------------------------------------------------- *
+ * A store behind keyvalue.Store expires by age.  A set can know when each chunk was last used: a 32-bit STAMP per digest on
+ * the device, a clock (the set's EPOCH) the caller advances, and "everything older than epoch E goes" through mi_zset_prune's
+ * sweep, compaction and rebuild.  No timestamp table on the host, no digest list uploaded: touch, census, expire and
+ * mi_index_retain_zset make a whole collection cycle.  What an epoch means (hours, builds, ...) is the caller's.  OFF UNTIL
+ * ASKED FOR: until mi_zset_set_epoch is called nothing is allocated or launched for it, and every other call allocates,
+ * answers and counts as before.  INVARIANT while ageing is on: every held digest has exactly one stamp, stamp <= epoch; the
+ * stamp follows the digest through every table rebuild (growth inside an add, mi_zset_prune, mi_zset_recode, mi_zset_expire),
+ * and those calls count the new table's stamp array (4 bytes a slot) in their peak_extra_bytes.  READERS DO NOT TOUCH:
+ * mi_zset_zpack, both plainer cuts, mi_zset_missing and mi_batch_add_zrecipes take a const set; the caller touches with the
+ * digests it passed to them.  Stamps are not kept across mi_zset_free (mi_zset_stamps over mi_zset_entries is what a caller
+ * saves).  All calls block, run on the ctx stream, and answer MI_ERR_STATE with the first message for a set in its sticky failed
+ * state.  One GPU; a plain mi_packset has no counterpart.  Measured once (profiles/chunk_zage.txt): on 10^6
+ * digests an expiry that drops half is 1.68 ms a call against 2.30 ms for mi_zset_prune(DROP) fed the digests as a list.
+ *   mi_zset_set_epoch     the first call turns ageing on: the stamp array (4 bytes x table slots) is allocated and everything
+ *                         held is stamped `epoch`; if it does not fit: MI_ERR_NOMEM naming the size and what the device has
+ *                         free, the set unchanged and ageing still off.  Later calls advance the clock: an epoch below the
+ *                         set's is MI_ERR_INVALID, the same epoch changes nothing.  0xFFFFFFFF is reserved: MI_ERR_INVALID.
+ *   mi_zset_get_epoch     *ageing = 1 once ageing is on, *epoch = the clock, *stamp_bytes = the device bytes allocated for the
+ *                         stamps (0 while ageing is off); any of the three may be NULL.
+ *   mi_zset_touch         digests: n x 32 bytes of host memory, n < 2^32, repeats allowed (NULL with n > 0, or more rows:
+ *                         MI_ERR_INVALID; n = 0: MI_OK).  A held digest's stamp becomes the set's epoch; a digest the set lacks
+ *                         is no error.  n_unknown counts the ROWS not held (repeats counted per row, as mi_prune_info does),
+ *                         n_refreshed the DISTINCT digests whose stamp was older than the epoch before the call.  Nothing but
+ *                         stamps changes.  Ageing off: MI_ERR_STATE saying so.
+ *   adds                  while ageing is on every digest an add brings gets the current epoch, whether it is new or already
+ *                         held: the first form still wins, but a re-add is a use.
+ *   mi_zset_stamps        stamps[r] = the stamp of row r's digest, 0xFFFFFFFF where the set does not hold it.  Read-only.
+ *                         Ageing off: MI_ERR_STATE.
+ *   mi_zset_age_census    bounds: 1 to 255 strictly ascending values (anything else: MI_ERR_INVALID); bins: n_bounds + 1 entries.
+ *                         Bin i takes the held digests with bounds[i-1] <= stamp < bounds[i]; bin 0 begins at stamp 0, the last
+ *                         bin is open above.  live_bytes is the sum of round16(stored), as mi_zset_get_usage counts it: with
+ *                         bounds = {E}, bin 0 is what mi_zset_expire(E) will drop -- how a store with a byte budget picks E.
+ *                         Read-only.  Ageing off: MI_ERR_STATE.
+ *   mi_zset_expire        drops every held digest whose stamp is below min_epoch; no list is involved.  For everything else
+ *                         mi_zset_prune's contract with MI_ZSET_PRUNE_DROP, word for word: dead blobs are freed, blobs under
+ *                         min_live_permille are compacted verbatim into one new blob in slot order, the table is rebuilt and
+ *                         swapped, everything is allocated before anything changes (whatever fails, the set is as it was), a
+ *                         compaction blob that does not fit is not an error (n_blobs_sparse_kept), nothing to drop leaves the
+ *                         set untouched with *info (may be NULL) filled.  n_rows = n_unknown = 0.  Survivors keep their
+ *                         stamps.  peak_extra_bytes: what mi_zset_prune allocates for the same drop with an empty request,
+ *                         plus the new stamp array when the table is rebuilt.  min_epoch above the set's epoch is
+ *                         MI_ERR_INVALID -- it would empty the set on a clock mistake, and MI_ZSET_PRUNE_KEEP with n = 0 is how
+ *                         one empties a set; min_live_permille > 1000: MI_ERR_INVALID; ageing off: MI_ERR_STATE.               */
+typedef struct {               /* 32 bytes */
+    uint64_t n_rows, n_unknown;              /* request rows; rows whose digest the set did not hold (repeats counted per row) */
+    uint64_t n_refreshed;                    /* distinct digests whose stamp was older than the epoch */
+    double   ms_touch;                       /* HIP events on the ctx stream */
+} mi_touch_info;
+typedef struct {               /* 32 bytes */
+    uint64_t n_digests, stored_bytes;        /* held digests whose stamp lies in the bin, and the sum of their stored sizes */
+    uint64_t live_bytes, chunk_bytes;        /* sums of round16(stored) and of the lengths */
+} mi_zage_bin;
+MI_BLOCK int  mi_zset_set_epoch(mi_zset* s, uint32_t epoch);
+MI_BLOCK int  mi_zset_get_epoch(const mi_zset* s, uint32_t* ageing, uint32_t* epoch, uint64_t* stamp_bytes);
+MI_BLOCK int  mi_zset_touch(mi_zset* s, const uint8_t* digests, uint64_t n, mi_touch_info* info);
+MI_BLOCK int  mi_zset_stamps(const mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t* stamps);
+MI_BLOCK int  mi_zset_age_census(const mi_zset* s, const uint32_t* bounds, uint32_t n_bounds, mi_zage_bin* bins);
+MI_BLOCK int  mi_zset_expire(mi_zset* s, uint32_t min_epoch, uint32_t min_live_permille, mi_prune_info* info);
+
 /* ---- the chunk index: asking without adding, forgetting ------------------------------------------------------------ *
  * The index's half of garbage collection.  A store that prunes its set (mi_zset_prune) hands the same list to the index, or a
  * builder's index would go on calling a dropped chunk "known", the commit would leave it out of its pack, and the layer's

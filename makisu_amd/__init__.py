@@ -22,7 +22,7 @@ __all__ = ["Engine", "Batch", "Config", "MiError", "load_library", "FILE_DTYPE",
            "PackSet", "PackSetInfo", "RecipeStats", "PACKSET_VERIFY", "RECIPE_VERIFY", "WantInfo", "SUBPACK_VERIFY",
            "ZPack", "ZPackEntry", "ZPackInfo", "ZPACK_ENTRY_DTYPE", "ZPACK_VERIFY", "zpack_check",
            "ZSet", "ZSetInfo", "ZSET_VERIFY", "MEMFS_CHUNK_ZPACK", "ZPACK_LEVEL2", "MEMFS_ZPACK_LEVEL2", "ZPACK_ENTROPY", "ZForms",
-           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP", "RecodeInfo", "ZSET_RECODE_VERIFY",
+           "PruneInfo", "ZSetUsage", "ZSET_PRUNE_KEEP", "ZSET_PRUNE_DROP", "RecodeInfo", "ZSET_RECODE_VERIFY", "TouchInfo", "AgeBin", "STAMP_NONE",
            "IndexPruneInfo", "INDEX_PRUNE_KEEP", "INDEX_PRUNE_DROP"]
 
 FLAG_FILE_SHA256 = 0x1
@@ -241,6 +241,25 @@ class RecodeInfo(C.Structure):
                                           "live_before", "live_after", "n_blobs_rewritten", "n_blobs_freed", "freed_bytes", "new_blob_bytes",
                                           "n_rounds", "peak_extra_bytes")] + \
                [(n, C.c_double) for n in ("ms_decode", "ms_encode", "ms_move", "ms_rebuild", "ms_verify")]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+STAMP_NONE = 0xFFFFFFFF                  # mi_zset_stamps: the set does not hold the digest; as an epoch: reserved
+
+
+class TouchInfo(C.Structure):
+    """mi_touch_info."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_rows", "n_unknown", "n_refreshed")] + [("ms_touch", C.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class AgeBin(C.Structure):
+    """mi_zage_bin."""
+    _fields_ = [(n, C.c_uint64) for n in ("n_digests", "stored_bytes", "live_bytes", "chunk_bytes")]
 
     def as_dict(self):
         return {n: getattr(self, n) for n, _ in self._fields_}
@@ -536,6 +555,12 @@ def load_library(rebuild=False):
         "mi_zset_recode": ([vp, C.c_uint32, u64, C.POINTER(RecodeInfo)], C.c_int),
         "mi_zset_get_usage": ([vp, C.POINTER(ZSetUsage)], C.c_int),
         "mi_zset_entries": ([vp, vp, vp, vp, u64, u64p], C.c_int),
+        "mi_zset_set_epoch": ([vp, C.c_uint32], C.c_int),
+        "mi_zset_get_epoch": ([vp, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32), u64p], C.c_int),
+        "mi_zset_touch": ([vp, vp, u64, C.POINTER(TouchInfo)], C.c_int),
+        "mi_zset_stamps": ([vp, vp, u64, vp], C.c_int),
+        "mi_zset_age_census": ([vp, vp, C.c_uint32, vp], C.c_int),
+        "mi_zset_expire": ([vp, C.c_uint32, C.c_uint32, C.POINTER(PruneInfo)], C.c_int),
         "mi_index_query": ([vp, vp, u64, vp, u64p], C.c_int),
         "mi_index_query_batch": ([vp, vp, vp, u64, u64p], C.c_int),
         "mi_index_prune": ([vp, vp, u64, C.c_uint32, C.POINTER(IndexPruneInfo)], C.c_int),
@@ -1610,6 +1635,60 @@ class ZSet:
         info = RecodeInfo()
         flags = _zpack_level_flag(level) | (ZSET_RECODE_VERIFY if verify else 0) | (ZPACK_ENTROPY if entropy else 0)
         rc = self._lib.mi_zset_recode(self._h, flags, scratch_bytes, C.byref(info))
+        if rc:
+            self._raise(rc)
+        return info
+
+    def set_epoch(self, epoch):
+        """mi_zset_set_epoch: the first call turns ageing on (a stamp per table slot on the device, everything held stamped
+        `epoch`); later calls advance the clock and never turn it back"""
+        rc = self._lib.mi_zset_set_epoch(self._h, epoch)
+        if rc:
+            self._raise(rc)
+
+    @property
+    def epoch(self):
+        """mi_zset_get_epoch -> (ageing: bool, epoch, stamp_bytes: device bytes of the stamps, 0 while ageing is off)"""
+        on, ep, nbytes = C.c_uint32(), C.c_uint32(), C.c_uint64()
+        rc = self._lib.mi_zset_get_epoch(self._h, C.byref(on), C.byref(ep), C.byref(nbytes))
+        if rc:
+            self._raise(rc)
+        return bool(on.value), ep.value, nbytes.value
+
+    def touch(self, digests):
+        """mi_zset_touch: the stamp of every held digest among `digests` (n x 32 bytes, repeats and unknown ones allowed)
+        becomes the set's epoch -> TouchInfo"""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        info = TouchInfo()
+        rc = self._lib.mi_zset_touch(self._h, d.ctypes.data if len(d) else None, len(d), C.byref(info))
+        if rc:
+            self._raise(rc)
+        return info
+
+    def stamps(self, digests):
+        """mi_zset_stamps -> uint32[n]: each row's stamp, STAMP_NONE where the set does not hold the digest"""
+        d = np.ascontiguousarray(digests, dtype=np.uint8).reshape(-1, 32)
+        out = np.zeros(max(len(d), 1), dtype=np.uint32)
+        rc = self._lib.mi_zset_stamps(self._h, d.ctypes.data if len(d) else None, len(d), out.ctypes.data)
+        if rc:
+            self._raise(rc)
+        return out[:len(d)]
+
+    def age_census(self, bounds):
+        """mi_zset_age_census: bounds (1 to 255 strictly ascending epochs) -> a list of len(bounds) + 1 AgeBin: bin i holds the
+        digests with bounds[i-1] <= stamp < bounds[i], the first begins at 0, the last is open above"""
+        b = np.ascontiguousarray(bounds, dtype=np.uint32).reshape(-1)
+        bins = (AgeBin * (len(b) + 1))()
+        rc = self._lib.mi_zset_age_census(self._h, b.ctypes.data if len(b) else None, len(b), C.addressof(bins))
+        if rc:
+            self._raise(rc)
+        return list(bins)
+
+    def expire(self, min_epoch, min_live_permille=0):
+        """mi_zset_expire: drop every digest whose stamp is below min_epoch, as prune(..., keep=False) drops a list; no list is
+        involved -> PruneInfo"""
+        info = PruneInfo()
+        rc = self._lib.mi_zset_expire(self._h, min_epoch, min_live_permille, C.byref(info))
         if rc:
             self._raise(rc)
         return info

@@ -11,6 +11,8 @@
 #include "mi_internal.h"
 #include "mi_wave.h"
 
+#include <functional>
+
 namespace mi {
 
 constexpr int kSlotWords = 6;                               // digest 4 | device address | length, stored
@@ -45,8 +47,11 @@ struct MI_LOCAL SlotTable {
     // 64-bit tags collide): sums[0] of them were not held, with (sum_bytes) sums[1] stored bytes and sums[2] chunk bytes;
     // *conflict = the smallest row whose digest is held with another length (kSlotNone: none)
     int insert(mi_ctx* c, const u64* d_recs, u64 n, u64 sums[3], u64* conflict, const char* what);
-    // room for n_more digests under half full: rebuilt at the next power of two that has it
-    int make_room(mi_ctx* c, u64 n_more, const char* what);
+    // room for n_more digests under half full: rebuilt at the next power of two that has it.  before_swap (may be empty): called
+    // when a rebuilt table is complete and the stream idle, with the OLD table still this one's -- for an owner that keeps something
+    // per slot and has to carry it over (mi_zage.hip's stamps); what it returns but MI_OK ends the call, the owner as it was
+    using BeforeSwap = std::function<int(const u64* new_tags, const u64* new_slots, u64 new_cap)>;
+    int make_room(mi_ctx* c, u64 n_more, const char* what, const BeforeSwap& before_swap = BeforeSwap());
     // ENQUEUED: every occupied slot's record to d_out[0, limit); *d_cursor (zeroed by the caller) counts them all
     void export_records(mi_ctx* c, u64* d_out, u64 limit, u64* d_cursor) const;
 

@@ -162,7 +162,7 @@ void SlotTable::export_records(mi_ctx* c, u64* d_out, u64 limit, u64* d_cursor) 
 }
 
 // The new table is complete before the old one goes: a failure leaves the owner as it was
-int SlotTable::make_room(mi_ctx* c, u64 n_more, const char* what) {
+int SlotTable::make_room(mi_ctx* c, u64 n_more, const char* what, const BeforeSwap& before_swap) {
     const u64 need = (count + n_more) * 2;
     if (need <= cap) return MI_OK;
     u64 new_cap = cap ? cap : 1024;
@@ -187,6 +187,7 @@ int SlotTable::make_room(mi_ctx* c, u64 n_more, const char* what) {
             return fail(c, MI_ERR_HIP, "%s rebuild lost entries (%llu of %llu)", what, (unsigned long long)sums[0], (unsigned long long)count);
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (before_swap && (rc = before_swap(new_tags.as<u64>(), new_slots.as<u64>(), new_cap))) return rc;
     tags = std::move(new_tags);                         // (DevBuf's move swaps: the old table goes with the locals)
     slots = std::move(new_slots);
     cap = new_cap;

@@ -24,6 +24,8 @@
 //
 // Everything is allocated before anything changes, by DevBuf::alloc_exact (the bytes rounded up to 256, plus 256), and the old
 // table and blobs go only when the new table is complete: whatever fails, the set is as it was.  Offsets and addresses are 64-bit.
+// The host's side is mi::ZsetSweep (mi_zset_local.h): begin(), the caller's mark, finish() -- mi_zset_prune marks by a list,
+// mi_zset_expire (mi_zage.hip) by age; an ageing set's stamps follow the survivors into the new table.
 //
 // BOUNDS.  mark READS digests [0, 32 n), tags / slots [0, cap) (the walk is masked), WRITES mark [0, cap).  sweep READS tags,
 // slots, mark [0, cap) and bases [0, n_blobs), WRITES slot_blob [0, cap), live [0, n_blobs) -- the index comes from the search,
@@ -307,69 +309,66 @@ int does_not_fit(mi_ctx* c, const char* who, hipError_t e, const char* what, u64
 
 }  // namespace
 
-extern "C" {
+namespace mi {
 
-int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags, uint32_t min_live_permille, mi_prune_info* info) {
-    if (info) memset(info, 0, sizeof *info);
-    if (!s || (n && !digests)) return MI_ERR_INVALID;
-    static const char* who = "mi_zset_prune";
-    mi_ctx* c = nullptr;
-    int rc = mi_zset_ctx(s, who, &c);                          // MI_ERR_STATE with the first message for a set in its failed state
-    if (rc) return rc;
-    if (flags != MI_ZSET_PRUNE_KEEP && flags != MI_ZSET_PRUNE_DROP)
-        return fail(c, MI_ERR_INVALID, "%s: flags %#x: exactly one of MI_ZSET_PRUNE_KEEP and MI_ZSET_PRUNE_DROP", who, flags);
-    if (min_live_permille > 1000) return fail(c, MI_ERR_INVALID, "%s: min_live_permille %u is more than 1000", who, min_live_permille);
-    if (n >> 32) return fail(c, MI_ERR_INVALID, "%s: %llu rows, a request holds fewer than 2^32", who, (unsigned long long)n);
-    HIPCHK(c, hipSetDevice(c->device));
+// (hidden: mi_zset_local.h) what the sweep needs, allocated; where ms_mark begins; the memsets and the blob bases, ENQUEUED
+int ZsetSweep::begin(mi_zset* s, const char* who) {
+    mi_ctx* c = s->ctx;
+    hipStream_t st = c->stream;
+    const u64 cap = s->table.cap, n_blobs = s->blobs.size();
+    HIPCHK(c, ev_begin.create());
+
+    // the blobs by base address: what a span's address is searched in
+    order.resize(n_blobs);
+    for (u32 i = 0; i < n_blobs; ++i) order[i] = i;
+    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return (size_t)s->blobs[a].mem.p < (size_t)s->blobs[b].mem.p; });
+    h_bases.resize(n_blobs);
+    for (u64 i = 0; i < n_blobs; ++i) h_bases[i] = (u64)(size_t)s->blobs[order[i]].mem.p;
+
+    PRUNE_ALLOC(mark, cap, "the mark array");
+    PRUNE_ALLOC(slot_blob, cap * 4, "the per-slot blob array");
+    PRUNE_ALLOC(bases, n_blobs * 8, "the blob bases");
+    PRUNE_ALLOC(blob_live, n_blobs * 8, "the per-blob sums");
+    PRUNE_ALLOC(totals, 64, "the totals");
+    HIPCHK(c, hipEventRecord(ev_begin, st));
+    if (n_blobs) HIPCHK(c, hipMemcpyAsync(bases.p, h_bases.data(), n_blobs * 8, hipMemcpyHostToDevice, st));
+    HIPCHK(c, hipMemsetAsync(mark.p, 0, cap, st));
+    if (n_blobs) HIPCHK(c, hipMemsetAsync(blob_live.p, 0, n_blobs * 8, st));
+    HIPCHK(c, hipMemsetAsync(totals.p, 0, 64, st));
+    return MI_OK;
+}
+
+// (hidden: mi_zset_local.h) everything of a prune behind the mark
+int ZsetSweep::finish(mi_zset* s, const char* who, u64 n_rows, bool keep, u32 min_live_permille, mi_prune_info* info) {
+    mi_ctx* c = s->ctx;
     hipStream_t st = c->stream;
     const u64 cap = s->table.cap, n_blobs = s->blobs.size();
     mi_prune_info pi = {};
-    pi.n_rows = n;
-    u64 extra = 0;                                             // what this call allocates, from the sizes
+    pi.n_rows = n_rows;
+    int rc = MI_OK;
 
-    DevBuf d_dig, d_mark, d_slot_blob, d_bases, d_live, d_tot, d_cls, d_scan, d_list, d_new_addr, d_recs;
+    DevBuf d_cls, d_scan, d_list, d_new_addr, d_recs, new_stamps;
     DevBuf new_blob;
     SlotTable fresh;                                           // the table the survivors go into: this call's, scratch and all
     fresh.sum_bytes = true;                                    // (as the set's own inserts run)
     Event ev[8];
     StreamDrain drain{st};   // (goes first: buffers and events after it)
     for (auto& e : ev) HIPCHK(c, e.create());
+    std::vector<u64> live(n_blobs);
 
-    // the blobs by base address: what a span's address is searched in
-    std::vector<u32> order(n_blobs);
-    for (u32 i = 0; i < n_blobs; ++i) order[i] = i;
-    std::sort(order.begin(), order.end(), [&](u32 a, u32 b) { return (size_t)s->blobs[a].mem.p < (size_t)s->blobs[b].mem.p; });
-    std::vector<u64> bases(n_blobs), live(n_blobs);
-    for (u64 i = 0; i < n_blobs; ++i) bases[i] = (u64)(size_t)s->blobs[order[i]].mem.p;
-
-    // ---- mark, sweep; synchronisation 1 ---------------------------------------------------------------------------------------
-    PRUNE_ALLOC(d_dig, n * 32, "the request");
-    PRUNE_ALLOC(d_mark, cap, "the mark array");
-    PRUNE_ALLOC(d_slot_blob, cap * 4, "the per-slot blob array");
-    PRUNE_ALLOC(d_bases, n_blobs * 8, "the blob bases");
-    PRUNE_ALLOC(d_live, n_blobs * 8, "the per-blob sums");
-    PRUNE_ALLOC(d_tot, 64, "the totals");
-    u64* tot = d_tot.as<u64>();
+    // ---- sweep; synchronisation 1 -----------------------------------------------------------------------------------------------
+    u64* tot = totals.as<u64>();
     u64* h = c->h_word.as<u64>();
-    HIPCHK(c, hipEventRecord(ev[0], st));
-    if (n) HIPCHK(c, hipMemcpyAsync(d_dig.p, digests, n * 32, hipMemcpyHostToDevice, st));
-    if (n_blobs) HIPCHK(c, hipMemcpyAsync(d_bases.p, bases.data(), n_blobs * 8, hipMemcpyHostToDevice, st));
-    HIPCHK(c, hipMemsetAsync(d_mark.p, 0, cap, st));
-    if (n_blobs) HIPCHK(c, hipMemsetAsync(d_live.p, 0, n_blobs * 8, st));
-    HIPCHK(c, hipMemsetAsync(tot, 0, 64, st));
-    if (n)
-        hipLaunchKernelGGL(zprune_mark_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_dig.as<u8>(), n, s->table.tags.as<u64>(),
-                           s->table.slots.as<u64>(), cap - 1, d_mark.as<u8>(), tot);
     const u32 sweep_grid = (u32)std::min<u64>((cap + kPWG - 1) / kPWG, 2048);
-    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPWG), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, d_mark.as<u8>(),
-                       flags == MI_ZSET_PRUNE_KEEP ? 1u : 0u, d_bases.as<u64>(), (u32)n_blobs, d_slot_blob.as<u32>(), d_live.as<u64>(), tot);
+    hipLaunchKernelGGL(zprune_sweep_kernel, dim3(sweep_grid), dim3(kPWG), 0, st, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, mark.as<u8>(),
+                       keep ? 1u : 0u, bases.as<u64>(), (u32)n_blobs, slot_blob.as<u32>(), blob_live.as<u64>(), tot);
     HIPCHK(c, hipEventRecord(ev[1], st));
     HIPCHK(c, hipMemcpyAsync(h, tot, 40, hipMemcpyDeviceToHost, st));
-    if (n_blobs) HIPCHK(c, hipMemcpyAsync(live.data(), d_live.p, n_blobs * 8, hipMemcpyDeviceToHost, st));
+    if (n_blobs) HIPCHK(c, hipMemcpyAsync(live.data(), blob_live.p, n_blobs * 8, hipMemcpyDeviceToHost, st));
     HIPCHK(c, hipStreamSynchronize(st));
     HIPCHK(c, hipGetLastError());
     float ms = 0;
-    HIPCHK(c, hipEventElapsedTime(&ms, ev[0], ev[1]));
+    HIPCHK(c, hipEventElapsedTime(&ms, ev_begin, ev[1]));
     pi.ms_mark = ms;
     pi.n_unknown = h[kPTotUnknown];
     const u64 n_survive = h[kPTotSurvive];
@@ -409,7 +408,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         u64* totals = block_bytes + nb;
         HIPCHK(c, hipEventRecord(ev[2], st));
         HIPCHK(c, hipMemcpyAsync(d_cls.p, cls.data(), n_blobs, hipMemcpyHostToDevice, st));
-        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(),
+        hipLaunchKernelGGL(zprune_block_sums_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(),
                            cap, block_cnt, block_bytes);
         hipLaunchKernelGGL(zprune_block_offsets_kernel, dim3(1), dim3(kPlanBlock), 0, st, block_cnt, block_bytes, nb, totals);
         HIPCHK(c, hipEventRecord(ev[3], st));
@@ -450,6 +449,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     PRUNE_ALLOC(fresh.row_state, n_survive + 16, "the insert's row states");
     PRUNE_ALLOC(fresh.row_slot, n_survive * 8 + 16, "the insert's row slots");
     PRUNE_ALLOC(fresh.counter, 64, "the insert's counters");
+    if (s->ageing) PRUNE_ALLOC(new_stamps, new_cap * 4, "the new table's stamps");
     pi.peak_extra_bytes = extra;
 
     // ---- move, repoint ----------------------------------------------------------------------------------------------------------
@@ -462,7 +462,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
         const u64 n_tiles = (moved_bytes + kPGatherTile - 1) / kPGatherTile;
         HIPCHK(c, hipEventRecord(ev[4], st));
         HIPCHK(c, hipMemsetAsync(d_new_addr.p, 0, cap * 8, st));
-        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, d_slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(), cap,
+        hipLaunchKernelGGL(zprune_compact_kernel, dim3((u32)nb), dim3(kPlanBlock), 0, st, slot_blob.as<u32>(), d_cls.as<u8>(), s->table.slots.as<u64>(), cap,
                            block_cnt, block_bytes, e_src, e_len, e_dst, e_slot);
         hipLaunchKernelGGL(zprune_gather_kernel, dim3((u32)n_tiles), dim3(kPWG), 0, st, e_src, e_len, e_dst, n_move, moved_bytes, new_blob.as<u8>());
         hipLaunchKernelGGL(zprune_repoint_kernel, dim3((u32)((n_move + 255) / 256)), dim3(256), 0, st, e_slot, e_dst, n_move,
@@ -475,13 +475,18 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     rc = fresh.alloc(c, new_cap);                              // (both are large enough: only the tags' memset is enqueued)
     if (rc) return rc;
     if (n_survive) {
-        hipLaunchKernelGGL(zprune_export_kernel, dim3((u32)((cap + 255) / 256)), dim3(256), 0, st, d_slot_blob.as<u32>(), s->table.slots.as<u64>(), cap,
+        hipLaunchKernelGGL(zprune_export_kernel, dim3((u32)((cap + 255) / 256)), dim3(256), 0, st, slot_blob.as<u32>(), s->table.slots.as<u64>(), cap,
                            n_move ? d_new_addr.as<u64>() : (const u64*)nullptr, d_recs.as<u64>(), n_survive, tot + kPTotCursor);
         u64 sums[3], conflict = kPNone;
         rc = fresh.insert(c, d_recs.as<u64>(), n_survive, sums, &conflict, "compressed pack set");
         if (rc) return rc;
         if (sums[0] != n_survive || conflict != kPNone)
             return fail(c, MI_ERR_HIP, "%s: the rebuild took %llu of %llu records", who, (unsigned long long)sums[0], (unsigned long long)n_survive);
+    }
+    if (s->ageing) {                                           // the survivors' stamps follow them: the new table is complete
+        rc = zage_carry_enqueue(c, s->table.tags.as<u64>(), s->table.slots.as<u64>(), cap, s->stamps.as<u32>(), fresh.tags.as<u64>(),
+                                fresh.slots.as<u64>(), new_cap, new_stamps.as<u32>());
+        if (rc) return rc;
     }
     HIPCHK(c, hipEventRecord(ev[7], st));
     HIPCHK(c, hipMemcpyAsync(h, tot + kPTotCursor, 8, hipMemcpyDeviceToHost, st));
@@ -497,6 +502,7 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     // ---- the set changes: nothing below can fail -------------------------------------------------------------------------------
     std::swap(s->table.tags, fresh.tags);                      // (the old table goes with the locals, and the insert's scratch)
     std::swap(s->table.slots, fresh.slots);
+    if (s->ageing) std::swap(s->stamps, new_stamps);
     s->table.cap = new_cap;
     s->table.count = n_survive;
     std::vector<u8> fate(n_blobs);
@@ -518,6 +524,37 @@ int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags
     s->info.chunk_bytes -= pi.dropped_chunk_bytes;
     if (info) *info = pi;
     return MI_OK;
+}
+
+}  // namespace mi
+
+extern "C" {
+
+int mi_zset_prune(mi_zset* s, const uint8_t* digests, uint64_t n, uint32_t flags, uint32_t min_live_permille, mi_prune_info* info) {
+    if (info) memset(info, 0, sizeof *info);
+    if (!s || (n && !digests)) return MI_ERR_INVALID;
+    static const char* who = "mi_zset_prune";
+    mi_ctx* c = nullptr;
+    int rc = mi_zset_ctx(s, who, &c);                          // MI_ERR_STATE with the first message for a set in its failed state
+    if (rc) return rc;
+    if (flags != MI_ZSET_PRUNE_KEEP && flags != MI_ZSET_PRUNE_DROP)
+        return fail(c, MI_ERR_INVALID, "%s: flags %#x: exactly one of MI_ZSET_PRUNE_KEEP and MI_ZSET_PRUNE_DROP", who, flags);
+    if (min_live_permille > 1000) return fail(c, MI_ERR_INVALID, "%s: min_live_permille %u is more than 1000", who, min_live_permille);
+    if (n >> 32) return fail(c, MI_ERR_INVALID, "%s: %llu rows, a request holds fewer than 2^32", who, (unsigned long long)n);
+    HIPCHK(c, hipSetDevice(c->device));
+    hipStream_t st = c->stream;
+    DevBuf d_dig;
+    ZsetSweep sweep;                                           // mark, sweep and everything behind them (mi_zset_local.h)
+    u64& extra = sweep.extra;                                  // what this call allocates, from the sizes
+    StreamDrain drain{st};   // (goes first: buffers and events after it)
+    PRUNE_ALLOC(d_dig, n * 32, "the request");
+    if ((rc = sweep.begin(s, who))) return rc;
+    if (n) {
+        HIPCHK(c, hipMemcpyAsync(d_dig.p, digests, n * 32, hipMemcpyHostToDevice, st));
+        hipLaunchKernelGGL(zprune_mark_kernel, dim3((u32)((n + 255) / 256)), dim3(256), 0, st, d_dig.as<u8>(), n, s->table.tags.as<u64>(),
+                           s->table.slots.as<u64>(), s->table.cap - 1, sweep.mark.as<u8>(), sweep.totals.as<u64>());
+    }
+    return sweep.finish(s, who, n, flags == MI_ZSET_PRUNE_KEEP, min_live_permille, info);
 }
 
 int mi_zset_get_usage(const mi_zset* s, mi_zset_usage* out) {

@@ -463,7 +463,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     u64 extra = 0;                                             // what this call allocates, from the sizes
 
     DevBuf d_bases, d_mark, d_tot, d_scan, d_rows, d_rule, d_cand, d_new, d_blob_of, d_rep, d_hash, d_got, d_scratch;
-    DevBuf d_scan2, d_list, d_addr, d_recs, d_vstr, d_got2, new_blob;
+    DevBuf d_scan2, d_list, d_addr, d_recs, d_vstr, d_got2, new_blob, new_stamps;
     DevBuf d_urows, d_scratch2, d_vrows;                       // the entropy stage's (mi_zentropy.h): unwrapped rows, form H's scratch, the recheck's rows
     ZhUnwrap unwrap, unwrap2;                                  // ... the held forms' inner forms; the replaced forms', for the recheck
     std::vector<DevBuf> pieces;                                // the staging pieces, one a round that replaces something
@@ -696,6 +696,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
         RECODE_ALLOC(d_got2, n_rep * 32, "the recheck's digests");
         if (entropy) RECODE_ALLOC(d_vrows, 2 * n_rep * 8, "the recheck's rows");
     }
+    if (s->ageing) RECODE_ALLOC(new_stamps, new_cap * 4, "the new table's stamps");
     ri.peak_extra_bytes = extra;
 
     // ---- move, repoint ----------------------------------------------------------------------------------------------------------
@@ -724,6 +725,10 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     if (sums[0] != n || conflict != kRNone || sums[1] != ri.stored_before - saved_stored)
         return fail(c, MI_ERR_HIP, "%s: the rebuild took %llu of %llu records with %llu stored bytes", who, (unsigned long long)sums[0], (unsigned long long)n,
                     (unsigned long long)sums[1]);
+    if (s->ageing) {                                           // (mi_zage.hip) every digest's stamp follows it: the new table is complete
+        rc = zage_carry_enqueue(c, tags, slots, cap, s->stamps.as<u32>(), fresh.tags.as<u64>(), fresh.slots.as<u64>(), new_cap, new_stamps.as<u32>());
+        if (rc) return rc;
+    }
     HIPCHK(c, hipEventRecord(ev[4], st));
 
     // ---- recheck (VERIFY): what the new blob holds, decoded and hashed round by round, before the swap -----------------------------
@@ -779,6 +784,7 @@ int mi_zset_recode(mi_zset* s, uint32_t flags, uint64_t scratch_bytes, mi_recode
     // ---- the set changes: nothing below can fail -------------------------------------------------------------------------------
     std::swap(s->table.tags, fresh.tags);                      // (the old table goes with the locals, and the insert's scratch)
     std::swap(s->table.slots, fresh.slots);
+    if (s->ageing) std::swap(s->stamps, new_stamps);
     s->table.cap = new_cap;
     std::vector<u8> fate(n_blobs);
     for (u64 i = 0; i < n_blobs; ++i) fate[order[i]] = mark[i];

@@ -273,7 +273,7 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
     mi_ctx* c = s->ctx;
     hipStream_t st = c->stream;
     DevBuf mine = std::move(blob);                     // freed on every early return -- after the stream has drained
-    DevBuf d_ent, d_recs;
+    DevBuf d_ent, d_recs, new_stamps;
     StreamDrain drain{st};   // (goes first: the buffers above after it)
     s->info.ms_verify = s->info.ms_insert = 0;
     if (n == 0) {                                      // a zpack of nothing
@@ -303,7 +303,26 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
         }
     }
     const auto t0 = std::chrono::steady_clock::now();
-    int rc = s->table.make_room(c, n, "compressed pack set");
+    int rc = MI_OK;
+    if (s->ageing) {                                   // (mi_zage.hip) a table that grows takes the stamps along, before the old one goes
+        rc = s->table.make_room(c, n, "compressed pack set", [&](const u64* new_tags, const u64* new_slots, u64 new_cap) -> int {
+            const hipError_t e = new_stamps.alloc_exact(new_cap * 4);
+            if (e != hipSuccess) {
+                (void)hipGetLastError();
+                return fail(c, e == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "%s: the grown table's stamps of %llu bytes do not fit (%s)", who,
+                            (unsigned long long)(new_cap * 4), hipGetErrorString(e));
+            }
+            const int rc2 = zage_carry_enqueue(c, s->table.tags.as<u64>(), s->table.slots.as<u64>(), s->table.cap, s->stamps.as<u32>(), new_tags, new_slots,
+                                               new_cap, new_stamps.as<u32>());
+            if (rc2) return rc2;
+            HIPCHK(c, hipStreamSynchronize(st));
+            HIPCHK(c, hipGetLastError());
+            return MI_OK;
+        });
+        if (rc == MI_OK && new_stamps.p) s->stamps = std::move(new_stamps);      // (DevBuf's move swaps: the old stamps go with the local)
+    } else {
+        rc = s->table.make_room(c, n, "compressed pack set");
+    }
     if (rc) return rc;
     u64 sums[3], conflict = kQNone;
     rc = s->table.insert(c, d_recs.as<u64>(), n, sums, &conflict, "compressed pack set");
@@ -316,6 +335,10 @@ int set_add(mi_zset* s, const char* who, DevBuf&& blob, u64 blob_bytes, const mi
         if (first_bad) *first_bad = conflict;
         rc = fail(c, MI_ERR_INVALID, "%s: entry %llu (%u bytes) has a digest the set holds with another length -- unverified input; the set "
                   "is unusable from here on", who, (unsigned long long)conflict, conflict < n ? entries[conflict].length : 0u);
+    }
+    if (rc == MI_OK && s->ageing) {                    // an add is a use: every digest it brought, new or held, gets the set's epoch
+        rc = zage_touch_records_enqueue(s, d_recs.as<u64>(), n);
+        if (rc == MI_OK && hipStreamSynchronize(st) != hipSuccess) rc = fail(c, MI_ERR_HIP, "%s: stamping the added digests failed", who);
     }
     if (rc) {                                          // the table is not rolled back: sticky
         s->broken = ctx_error(c);
