@@ -792,6 +792,36 @@ MI_BLOCK int  mi_layer_add_whiteout(mi_layer* layer, const char* deleted_path);
 MI_BLOCK int  mi_layer_finish(mi_layer* layer, mi_layer_result* out);
 MI_BLOCK const char* mi_layer_error(mi_layer* layer);
 MI_BLOCK void mi_layer_free(mi_layer* layer);
+/* THE DEVICE DEFLATE LEG (opt-in; csrc/mi_deflate_wave.h).  mi_layer_set_gzip_ctx, after mi_layer_begin and before
+ * the first add (later: MI_ERR_STATE; with gzip_level MI_GZIP_OFF or 0: MI_ERR_INVALID, there is nothing to code): the gzip leg
+ * of this layer is coded on ctx's device instead of by zlib's pool threads, which are then not started.  The sink collects whole
+ * 1 MiB blocks of the tar into a window (MI_GZIP_DEVICE_WINDOW_MB, 1..1024, default 32), two windows in flight on streams of the
+ * leg's own, and writes the pieces in order, with SHA-256 and `write` as the host leg does; then 03 00, the combined CRC-32 and
+ * the length.  The ten header bytes are the host leg's with XFL = 4.  THERE IS ONE DEVICE LEVEL: gzip_level 1..9 or default does
+ * not change the device leg's bytes.  A device error is the layer's error (mi_layer_error) and fails mi_layer_finish; a layer that
+ * has begun never falls back to zlib.  The ctx must outlive the layer.  The tar, TarDigest and everything else are unchanged;
+ * gzip_sha256 and gzip_bytes describe the blob written, as ever (the gzip bytes are this writer's own).
+ *
+ * FORMAT.  The member's deflate stream is the PIECES' stored forms end to end, then the writer's 03 00.  Piece k is tar bytes
+ * [k * 65536, (k + 1) * 65536), the last one shorter; no match reaches before a piece's first byte, so the blob is a pure
+ * function of the tar stream, whatever window, thread count or GPU produced it.  A piece is stored as (D) one dynamic-Huffman
+ * block (BFINAL 0, BTYPE 2) followed by an empty stored block -- three zero bits, zero bits to the byte boundary, 00 00 FF FF, what
+ * Z_SYNC_FLUSH writes: the piece ends on a byte boundary -- or as (S) stored blocks of at most 65 535 bytes (a full piece: 65 535
+ * and 1).  (D) is kept only where it is smaller than (S).  No fixed-Huffman blocks, no BFINAL in a piece.  The parse, the split of
+ * long matches, the length-limited COMPLETE codes and the header's run rule are stated in csrc/mi_deflate_wave.h and restated by the
+ * model the tests hold the bytes against (tests/deflate_cases.py).
+ *
+ * mi_deflate_buffer is the coder alone, host bytes in, host bytes out: the pieces' stored forms of src[0, n) end to end in dst, no
+ * gzip header and no final block -- zlib.decompressobj(-15).decompress(out + b"\x03\x00") gives src back.  *crc32 (may be NULL):
+ * the CRC-32 of src, computed on the device; info (may be NULL): the pieces by form, the bytes, the device time of the windows.
+ * n == 0 gives 0 bytes.  cap below mi_deflate_bound(n) is MI_ERR_CAPACITY, a NULL ctx, dst, out_bytes or src (with n > 0)
+ * MI_ERR_INVALID.  Any failure leaves dst unspecified and the ctx usable.  The bytes cross PCIe through pinned windows on streams
+ * of the call's own (MI_GZIP_DEVICE_WINDOW_MB as above).                                                                       */
+typedef struct { uint64_t n_pieces, n_dynamic, n_stored, in_bytes, out_bytes; double ms_device; } mi_deflate_info;
+MI_BLOCK uint64_t mi_deflate_bound(uint64_t n);   /* what dst must hold for any n bytes */
+MI_BLOCK int  mi_deflate_buffer(mi_ctx* ctx, const void* src, uint64_t n, void* dst, uint64_t cap, uint64_t* out_bytes, uint32_t* crc32,
+                                mi_deflate_info* info);
+MI_BLOCK int  mi_layer_set_gzip_ctx(mi_layer* layer, mi_ctx* ctx);
 /* step.commitLayer (lib/builder/step/common.go:67-111) in one call on a MemFS handle: the step's layer by scan
  * (must_scan: the root is walked here, with the handle's blacklist) or by its copy operations, written through the layer
  * writer configured by cfg (tarAndGzipDiffs: tar framing, TarDigest, the gzip leg with its digest and size), folded into
@@ -921,6 +951,11 @@ MI_CORE int  mi_memfs_commit_stats(const mi_memfs* fs, mi_commit_stats* out);
  * (mi_batch_zpack_chunks with MI_ZPACK_VERIFY | MI_ZPACK_LEVEL2): mi_memfs_take_zpack is then byte for byte what
  * mi_memfs_take_pack followed by mi_pack_compress(MI_ZPACK_LEVEL2) gives.  The layer, the recipes and the index are the same. */
 #define MI_MEMFS_ZPACK_LEVEL2 0x10u
+/* MI_MEMFS_GZIP_DEVICE: a commit with a ctx codes its layer's gzip leg on that ctx's device (mi_layer_set_gzip_ctx; with
+ * mi_memfs_commit_layer_n on ctxs[0]'s).  With ctx == NULL the commit fails with MI_ERR_STATE before anything is walked.  At
+ * MI_GZIP_OFF or level 0 the option has no effect.  A commit in windows takes it like any other.  The layer, TarDigest, roots,
+ * index, packs and recipes are unchanged by the option: only gzip_sha256 and gzip_bytes differ.                                */
+#define MI_MEMFS_GZIP_DEVICE 0x40u   /* (0x8 and 0x20 stay refused) */
 MI_CORE int  mi_memfs_set_options(mi_memfs* fs, uint32_t options);
 /* From now on every content-aware commit of this handle adds its batch to `index` (NULL: stop).  The index must belong
  * to the ctx the commits run on and outlive them; the handle does not own it.                                          */

@@ -113,6 +113,7 @@ MEMFS_TRUST_CTIME = 0x1
 MEMFS_CHUNK_PACK = 0x2                   # a commit also packs the chunks its index did not know (MemFS.take_pack) and keeps the recipes
 MEMFS_CHUNK_ZPACK = 0x4                  # ... codes them straight from the arena into a compressed pack instead (MemFS.take_zpack)
 MEMFS_ZPACK_LEVEL2 = 0x10                # ... at level 2 (beside MEMFS_CHUNK_ZPACK)
+MEMFS_GZIP_DEVICE = 0x40                 # a commit with an Engine codes its layer's gzip leg on the device (Layer.set_gzip_engine)
 PACK_VERIFY = 0x1                        # mi_batch_pack_chunks: hash the blob again on the device
 
 
@@ -369,6 +370,11 @@ ZPACK_ENTRY_DTYPE = _np_dtype(ZPackEntry)
 _lib = None
 
 
+class DeflateInfo(C.Structure):
+    _fields_ = [("n_pieces", C.c_uint64), ("n_dynamic", C.c_uint64), ("n_stored", C.c_uint64), ("in_bytes", C.c_uint64),
+                ("out_bytes", C.c_uint64), ("ms_device", C.c_double)]
+
+
 def load_library(rebuild=False):
     """Loads (building first if stale) makisu_amd/libmakisu_mi.so.  Raises if it is missing."""
     global _lib
@@ -491,6 +497,9 @@ def load_library(rebuild=False):
         "mi_layer_finish": ([vp, C.POINTER(LayerResult)], C.c_int),
         "mi_layer_error": ([vp], C.c_char_p),
         "mi_layer_free": ([vp], None),
+        "mi_layer_set_gzip_ctx": ([vp, vp], C.c_int),
+        "mi_deflate_bound": ([u64], u64),
+        "mi_deflate_buffer": ([vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(DeflateInfo)], C.c_int),
         "mi_layer_header_bytes": ([C.POINTER(TreeEntry), C.c_uint32, vp, u64, u64p], C.c_int),
         "mi_cache_parse_entry_str": ([C.c_char_p, C.c_char_p, u64, C.c_char_p, u64], C.c_int),
         "mi_cache_key": ([C.c_char_p, C.c_char_p, u64], C.c_int),
@@ -1013,15 +1022,17 @@ class MemFS:
         engine._children.add(self)
         self._check(self._lib.mi_memfs_reserve_device(self._h, engine._h, files, nbytes), "mi_memfs_reserve_device")
 
-    def set_options(self, trust_ctime=False, chunk_pack=False, chunk_zpack=False, zpack_level=1):
+    def set_options(self, trust_ctime=False, chunk_pack=False, chunk_zpack=False, zpack_level=1, gzip_device=False):
         """MI_MEMFS_TRUST_CTIME: scan commits do not read files again whose inode is what it was when they were hashed.
         MI_MEMFS_CHUNK_PACK: a commit (one Engine, an index set) also packs the chunks the index did not know -- take_pack() --
         and its layer's regular files carry "chunks": [(digest, length), ...], their recipes.
         MI_MEMFS_CHUNK_ZPACK: the same with the chunks coded straight from the arena into a compressed pack -- take_zpack();
-        both at once are refused (MI_ERR_INVALID); zpack_level=2 (MI_MEMFS_ZPACK_LEVEL2): that zpack is coded at level 2"""
+        both at once are refused (MI_ERR_INVALID); zpack_level=2 (MI_MEMFS_ZPACK_LEVEL2): that zpack is coded at level 2.
+        MI_MEMFS_GZIP_DEVICE: a commit with an Engine codes the layer's gzip leg on its device (only the gzip digest and size differ)"""
         _zpack_level_flag(zpack_level)
         self._check(self._lib.mi_memfs_set_options(self._h, (MEMFS_TRUST_CTIME if trust_ctime else 0) | (MEMFS_CHUNK_PACK if chunk_pack else 0) |
-                                                   (MEMFS_CHUNK_ZPACK if chunk_zpack else 0) | (MEMFS_ZPACK_LEVEL2 if zpack_level == 2 else 0)),
+                                                   (MEMFS_CHUNK_ZPACK if chunk_zpack else 0) | (MEMFS_ZPACK_LEVEL2 if zpack_level == 2 else 0) |
+                                                   (MEMFS_GZIP_DEVICE if gzip_device else 0)),
                     "mi_memfs_set_options")
         self._chunk_pack, self._chunk_zpack = bool(chunk_pack), bool(chunk_zpack)
 
@@ -1097,6 +1108,12 @@ class Layer:
     def _check(self, rc):
         if rc:
             raise MiError(rc, self._lib.mi_layer_error(self._h).decode(errors="replace"))
+
+    def set_gzip_engine(self, engine):
+        """mi_layer_set_gzip_ctx: the gzip leg of this layer is coded on the Engine's device (before the first add; there is one
+        device level, whatever gzip_level says).  The Engine must outlive the layer"""
+        self._gzip_engine = engine
+        self._check(self._lib.mi_layer_set_gzip_ctx(self._h, engine._h if engine is not None else None))
 
     def add(self, entry, src_path=None):
         keep = []
@@ -1866,6 +1883,17 @@ class Engine:
                                              offs.ctypes.data_as(u64p), lens.ctypes.data_as(u64p),
                                              len(blobs), out.ctypes.data))
         return [out[i].tobytes() for i in range(len(blobs))]
+
+    def deflate_buffer(self, data):
+        """mi_deflate_buffer: the device deflate leg's coder alone -> (blob, crc32, info dict).  The blob is the pieces' stored
+        forms end to end: zlib.decompressobj(-15).decompress(blob + b"\\x03\\x00") gives data back"""
+        src = np.frombuffer(bytes(data), dtype=np.uint8)
+        cap = self._lib.mi_deflate_bound(src.size)
+        out = np.zeros(max(cap, 1), dtype=np.uint8)
+        n, crc, info = C.c_uint64(), C.c_uint32(), DeflateInfo()
+        self._check(self._lib.mi_deflate_buffer(self._h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, cap, C.byref(n),
+                                                C.byref(crc), C.byref(info)))
+        return out[:n.value].tobytes(), crc.value, dict((f, getattr(info, f)) for f, _ in DeflateInfo._fields_)
 
     def index(self, capacity_hint=0):
         """A chunk-digest set that outlives batches (dedup across layers)."""

@@ -90,7 +90,7 @@ static double secs_since(const std::chrono::steady_clock::time_point& t0) {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
 }
 static int memfs_commit_write(mi_memfs* m, mi_copy_layer* cl, uint64_t ne, const mi_layer_config* cfg, mi_layer_result* res,
-                              mi_batch* batch, bool pipelined) {
+                              mi_batch* batch, bool pipelined, mi_ctx* gzip_ctx) {
     std::vector<mi_tree_entry> ents(ne ? ne : 1);
     std::vector<const char*> srcs(ne ? ne : 1);
     int rc = mi_copy_layer_entries(cl, ents.data(), srcs.data(), ne);
@@ -98,6 +98,9 @@ static int memfs_commit_write(mi_memfs* m, mi_copy_layer* cl, uint64_t ne, const
     if (rc) m->err = "failed to generate diff layer: layer entries";
     if (!rc && (rc = mi_layer_begin(cfg, &lw))) m->err = "failed to generate diff layer: the layer writer refused its configuration";
     if (lw && pipelined) mi_layer_set_pipelined(lw, 1);        // a file's bytes are waited for where they have not landed yet
+    // MI_MEMFS_GZIP_DEVICE: the gzip leg is coded on the first ctx's device (no effect where there is nothing to code)
+    if (lw && gzip_ctx && cfg->gzip_level != MI_GZIP_OFF && cfg->gzip_level != 0 && (rc = mi_layer_set_gzip_ctx(lw, gzip_ctx)))
+        m->err = std::string("failed to generate diff layer: the device gzip leg: ") + mi_layer_error(lw);
     for (uint64_t i = 0; i < ne && !rc; ++i) {
         const mi_copy::Node& nd = cl->nodes[i];
         if (ents[i].kind == 1 && ents[i].file_index >= 0) { ++m->last.n_layer_files; m->last.layer_file_bytes += ents[i].size; }
@@ -421,7 +424,7 @@ struct Commit {
         m->last.n_content_changed = fs.n_content_changed;
         m->last.n_roots_learned = fs.n_roots_learned;
         const auto t2 = std::chrono::steady_clock::now();
-        const int rc = memfs_commit_write(m, cl, ne, cfg, res, windowed ? nullptr : b, piped);
+        const int rc = memfs_commit_write(m, cl, ne, cfg, res, windowed ? nullptr : b, piped, m->gzip_device && n_ctx ? ctxs[0] : nullptr);
         m->last.s_write = secs_since(t2);
         return rc;
     }
@@ -586,6 +589,10 @@ static int memfs_commit(mi_memfs* m, mi_ctx* const* ctxs, uint32_t n_ctx, int mu
             return MI_ERR_INVALID;
         }
     }
+    if (!n_ctx && m->gzip_device && cfg && cfg->gzip_level != MI_GZIP_OFF && cfg->gzip_level != 0) {   // MI_MEMFS_GZIP_DEVICE: before anything is walked
+        m->err = "failed to generate diff layer: MI_MEMFS_GZIP_DEVICE codes the gzip leg on a ctx's device: the commit has none (ctx == NULL)";
+        return MI_ERR_STATE;
+    }
     if (n_ctx && m->chunk_pack) {                                                 // MI_MEMFS_CHUNK_PACK: before anything is walked
         if (!m->index) { m->err = "failed to generate diff layer: chunk pack: MI_MEMFS_CHUNK_PACK packs the chunks the index did not know: set one first (mi_memfs_set_index)"; return MI_ERR_STATE; }
         if (n_ctx > 1) { m->err = "failed to generate diff layer: chunk pack: a pack over several GPUs' arenas is not built (MI_MEMFS_CHUNK_PACK with n_ctx > 1)"; return MI_ERR_INVALID; }
@@ -636,7 +643,7 @@ extern "C" int mi_memfs_commit_stats(const mi_memfs* m, mi_commit_stats* out) {
     return MI_OK;
 }
 extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
-    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK | MI_MEMFS_CHUNK_ZPACK | MI_MEMFS_ZPACK_LEVEL2))) return MI_ERR_INVALID;
+    if (!m || (options & ~(MI_MEMFS_TRUST_CTIME | MI_MEMFS_CHUNK_PACK | MI_MEMFS_CHUNK_ZPACK | MI_MEMFS_ZPACK_LEVEL2 | MI_MEMFS_GZIP_DEVICE))) return MI_ERR_INVALID;
     if ((options & MI_MEMFS_CHUNK_PACK) && (options & MI_MEMFS_CHUNK_ZPACK)) {    // mi_pack_compress, or a decode, makes the other form
         m->err = "mi_memfs_set_options: MI_MEMFS_CHUNK_PACK and MI_MEMFS_CHUNK_ZPACK exclude each other: the commit does not do the work twice";
         return MI_ERR_INVALID;
@@ -645,6 +652,7 @@ extern "C" int mi_memfs_set_options(mi_memfs* m, uint32_t options) {
     m->chunk_pack = (options & MI_MEMFS_CHUNK_PACK) != 0;
     m->chunk_zpack = (options & MI_MEMFS_CHUNK_ZPACK) != 0;
     m->zpack_level2 = (options & MI_MEMFS_ZPACK_LEVEL2) != 0;            // (alone it changes nothing: there is no zpack to code)
+    m->gzip_device = (options & MI_MEMFS_GZIP_DEVICE) != 0;
     return MI_OK;
 }
 extern "C" int mi_memfs_take_zpack(mi_memfs* m, mi_zpack** out) {

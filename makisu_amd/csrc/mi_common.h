@@ -230,6 +230,9 @@ void crc32_build_tables(u32* out /* kCrcConstWords */);
 void launch_crc32_files(const u8* d_data, const u64* d_file_off, const u64* d_file_size,
                         const u32* d_tile_file, const u64* d_first_tile, u64 n_tiles, u64 n_files,
                         const u32* d_consts, u32* d_tile_raw, u32* d_crc, hipStream_t s);
+// mi_deflate.hip, for tests/kernel_probe: the device deflate leg's length-limiting rule alone (mi_deflate_wave.h df_code_lengths) --
+// d_counts[0, nsym) -> d_lens[0, nsym) under `limit` bits, by one wave; nsym <= 286, limit <= 15 (else nothing is launched)
+void launch_deflate_code_lengths(const u32* d_counts, u32 nsym, u32 limit, u8* d_lens, hipStream_t s);
 u32 crc32_host_bytes(u32 crc, const void* data, size_t len);
 u32 crc32_host_combine(u32 crc1, u32 crc2, u64 len2);
 // d_table: 2 x cap_pow2 words (rep | complemented minima), cleared here with one memset

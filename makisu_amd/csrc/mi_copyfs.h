@@ -661,6 +661,7 @@ struct mi_memfs {
     // MI_MEMFS_CHUNK_ZPACK: the same for the compressed pack (mi_memfs_take_zpack); the two options exclude each other
     bool chunk_zpack = false;
     bool zpack_level2 = false;                   // MI_MEMFS_ZPACK_LEVEL2: the commit codes it with MI_ZPACK_LEVEL2
+    bool gzip_device = false;                    // MI_MEMFS_GZIP_DEVICE: the layer writer's gzip leg is coded on the commit's first ctx
     mi_zpack* zpack = nullptr;
     int zpack_rc = MI_ERR_STATE;
     std::string zpack_err = "no commit since the last mi_memfs_take_zpack";

@@ -1,5 +1,5 @@
 // mi_layer.hip -- the layer writer: tar framing + the two serial layer digests, behind the C ABI.
-// Host code only (no kernels).
+// Host code only (no kernels): the opt-in device deflate leg is mi_deflate.hip's, driven through mi_local.h's mi_deflater_*.
 //
 // What it restates (reference = uber/makisu):
 //   step.tarAndGzipDiffs        lib/builder/step/common.go:35-63   tar.Writer -> tee -> {tarDigester,
@@ -176,27 +176,76 @@ public:
     int out_fd = -1;
     bool init(int level) {
         level_ = level;
-        unsigned n = 0;
-        if (const char* e = getenv("MI_GZIP_THREADS")) n = (unsigned)atoi(e);
-        if (n == 0) {
-            cpu_set_t set;
-            n = sched_getaffinity(0, sizeof set, &set) == 0 ? (unsigned)CPU_COUNT(&set) : 1u;
-            if (n > 16) n = 16;
-        }
-        if (n < 1) n = 1;
-        if (n > 64) n = 64;
-        window_ = 2 * n;
-        for (unsigned i = 0; i < n; ++i) pool_.emplace_back([this] { work(); });
-        // gzip header as compress/gzip writes it: no name, no mtime, XFL by level, OS "unknown"
-        const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0,
-                                 (uint8_t)(level == 9 ? 2 : level == 1 ? 4 : 0), 255};
-        emit(hdr, sizeof hdr);
         return true;
     }
-    ~GzipSink() override { stop_pool(); }
+    int level() const { return level_; }
+    // the device leg (mi_layer_set_gzip_ctx, before the first block): the pool below is then never started
+    void set_device(mi_ctx* ctx) { dev_ctx_ = ctx; }
+    ~GzipSink() override { stop_pool(); if (dev_) mi_deflater_free(dev_); }
 protected:
+    // on the sink thread, at the first block (or at finish, for the header alone): the pool and the header -- or the device coder
+    bool begin_leg() {
+        if (begun_) return !failed();
+        begun_ = true;
+        if (dev_ctx_) {
+            if (mi_deflater_create(dev_ctx_, mi_deflate_device_window(), &dev_) != MI_OK) { set_error("device gzip leg: no coder on the ctx's device"); return false; }
+        } else {
+            unsigned n = 0;
+            if (const char* e = getenv("MI_GZIP_THREADS")) n = (unsigned)atoi(e);
+            if (n == 0) {
+                cpu_set_t set;
+                n = sched_getaffinity(0, sizeof set, &set) == 0 ? (unsigned)CPU_COUNT(&set) : 1u;
+                if (n > 16) n = 16;
+            }
+            if (n < 1) n = 1;
+            if (n > 64) n = 64;
+            window_ = 2 * n;
+            for (unsigned i = 0; i < n; ++i) pool_.emplace_back([this] { work(); });
+        }
+        // gzip header as compress/gzip writes it: no name, no mtime, XFL by level, OS "unknown".  The device leg has ONE level,
+        // whatever was asked for: XFL = 4
+        const uint8_t hdr[10] = {0x1f, 0x8b, 8, 0, 0, 0, 0, 0,
+                                 (uint8_t)(dev_ctx_ ? 4 : level_ == 9 ? 2 : level_ == 1 ? 4 : 0), 255};
+        emit(hdr, sizeof hdr);
+        return !failed();
+    }
+    static int device_emit(void* arg, const uint8_t* bytes, uint64_t n_out, uint32_t crc, uint64_t n_in) {
+        GzipSink* g = (GzipSink*)arg;
+        g->emit(bytes, (size_t)n_out);
+        g->crc_ = g->total_in_ ? (uint32_t)crc32_combine(g->crc_, crc, (z_off_t)n_in) : crc;
+        g->total_in_ += n_in;
+        return g->failed() ? MI_ERR_IO : MI_OK;
+    }
+    void device_error(int rc) {                                     // never a fall-back to zlib inside a layer that has begun
+        if (failed()) return;
+        const char* m = mi_deflater_error(dev_);
+        char buf[500];
+        snprintf(buf, sizeof buf, "device gzip leg: %s (%d)", m && *m ? m : "no memory for a window", rc);
+        set_error(buf);
+    }
+    bool device_push() {
+        const int rc = mi_deflater_push(dev_, dev_fill_, device_emit, this);
+        dev_fill_ = 0;
+        if (rc) device_error(rc);
+        return rc == MI_OK;
+    }
+    void device_consume(const Block& b) {                           // whole windows of the stream, whatever the blocks' sizes
+        const uint8_t* p = b->data();
+        size_t n = b->size();
+        const uint64_t window = mi_deflater_window(dev_);
+        while (n) {
+            uint8_t* room = mi_deflater_room(dev_);
+            if (!room) { device_error(MI_ERR_NOMEM); return; }
+            const size_t take = (size_t)std::min<uint64_t>(n, window - dev_fill_);
+            memcpy(room + dev_fill_, p, take);
+            dev_fill_ += take; p += take; n -= take;
+            if (dev_fill_ == window && !device_push()) return;
+        }
+    }
     void consume(const Block& b) override {
         if (b->empty()) return;
+        if (!begin_leg()) return;
+        if (dev_) { device_consume(b); return; }
         auto j = std::make_shared<Job>();
         j->in = b;
         {
@@ -208,6 +257,12 @@ protected:
         while (inflight_.size() >= window_) drain_one();
     }
     void finish() override {
+        if (!begin_leg()) return;
+        if (dev_) {
+            if (dev_fill_ && !device_push()) return;
+            const int rc = mi_deflater_flush(dev_, device_emit, this);
+            if (rc) device_error(rc);
+        }
         while (!inflight_.empty()) drain_one();
         stop_pool();
         if (failed()) return;
@@ -344,6 +399,10 @@ private:
         pool_.clear();
     }
     int level_ = Z_DEFAULT_COMPRESSION;
+    bool begun_ = false;
+    mi_ctx* dev_ctx_ = nullptr;
+    mi_deflater* dev_ = nullptr;
+    uint64_t dev_fill_ = 0;                                        // bytes in the device window being filled
     size_t window_ = 2;
     std::vector<std::thread> pool_;
     std::mutex pm_;
@@ -563,7 +622,9 @@ struct mi_layer {
     double read_s = 0;                                 // ... and the seconds the framer spent getting file bytes (either source)
     std::chrono::steady_clock::time_point t_begin = std::chrono::steady_clock::now();
     bool finished = false, failed = false;
+    bool gzip_ctx_set = false;
 
+    int fail_soft(int code, const char* msg) { err = msg; return code; }    // a refused call: the layer goes on
     int fail(int code, const char* fmt, ...) {
         char buf[600];
         va_list ap;
@@ -820,6 +881,16 @@ int mi_layer_add_batch_file(mi_layer* l, const mi_tree_entry* e, mi_batch* batch
                            (unsigned long long)e->size, (unsigned long long)staged);
     }
     return layer_add_entry(l, e, nullptr, batch, file_index);
+}
+
+int mi_layer_set_gzip_ctx(mi_layer* l, mi_ctx* ctx) {
+    if (!l || !ctx) return MI_ERR_INVALID;
+    if (!l->gz || l->gz->level() == 0) return l->fail_soft(MI_ERR_INVALID, "mi_layer_set_gzip_ctx: this layer has no gzip leg to code (MI_GZIP_OFF or level 0)");
+    if (l->finished || l->failed || l->n_entries || l->cur || l->gzip_ctx_set)
+        return l->fail_soft(MI_ERR_STATE, "mi_layer_set_gzip_ctx: after mi_layer_begin and before the first add, once");
+    l->gzip_ctx_set = true;
+    l->gz->set_device(ctx);
+    return MI_OK;
 }
 
 void mi_layer_set_pipelined(mi_layer* l, int on) { if (l) l->pipelined = on != 0; }

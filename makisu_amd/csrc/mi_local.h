@@ -53,6 +53,21 @@ MI_LOCAL void mi_batch_drop_windows(mi_batch* b);
 MI_LOCAL int  mi_batch_prepare_read(mi_batch* b);      // the read-back windows now, not at the tar writer's first read
 MI_LOCAL int  mi_batch_explain_chunk(mi_batch* b, uint64_t file_index, uint64_t chunk, char* msg, uint64_t cap);
 MI_LOCAL void mi_batch_expect_host_bytes(mi_batch* b);
+// mi_deflate.hip -- the device deflate coder behind the layer writer's gzip leg and mi_deflate_buffer: windows of the stream, two
+// in flight.  room: the pinned window to fill (NULL: no memory; the message is _error's); push: its first n bytes are coded --
+// and the window pushed BEFORE it comes out through emit (the compressed bytes, their count, the window's CRC-32 and length);
+// flush: what is still in flight comes out, in order.  One thread drives a deflater.  window: a multiple of 65 536
+struct mi_deflater;
+typedef int (*mi_deflate_emit_fn)(void* arg, const uint8_t* bytes, uint64_t n_out, uint32_t crc, uint64_t n_in);
+MI_LOCAL int         mi_deflater_create(mi_ctx* ctx, uint64_t window_bytes, mi_deflater** out);
+MI_LOCAL uint64_t    mi_deflater_window(const mi_deflater* d);
+MI_LOCAL uint8_t*    mi_deflater_room(mi_deflater* d);
+MI_LOCAL int         mi_deflater_push(mi_deflater* d, uint64_t n, mi_deflate_emit_fn emit, void* arg);
+MI_LOCAL int         mi_deflater_flush(mi_deflater* d, mi_deflate_emit_fn emit, void* arg);
+MI_LOCAL const char* mi_deflater_error(const mi_deflater* d);
+MI_LOCAL void        mi_deflater_info(const mi_deflater* d, mi_deflate_info* out);
+MI_LOCAL void        mi_deflater_free(mi_deflater* d);
+MI_LOCAL uint64_t    mi_deflate_device_window(void);          // MI_GZIP_DEVICE_WINDOW_MB (1..1024), default 32
 // mi_batch_reserve for a walk whose enumeration runs ahead of what it hands over (and for mi_memfs_reserve_device): the arena
 // is the piecewise kind (mi_arena.hip) -- what is coming is known roughly and keeps growing
 MI_LOCAL int  mi_batch_reserve_ahead(mi_batch* b, uint64_t more_files, uint64_t more_bytes);
