@@ -822,6 +822,48 @@ MI_BLOCK uint64_t mi_deflate_bound(uint64_t n);   /* what dst must hold for any 
 MI_BLOCK int  mi_deflate_buffer(mi_ctx* ctx, const void* src, uint64_t n, void* dst, uint64_t cap, uint64_t* out_bytes, uint32_t* crc32,
                                 mi_deflate_info* info);
 MI_BLOCK int  mi_layer_set_gzip_ctx(mi_layer* layer, mi_ctx* ctx);
+/* THE DEVICE INFLATE (opt-in; csrc/mi_inflate_wave.h, csrc/host_inflate.h): the way back.  mi_tar_inflate and
+ * mi_tar_open_ex are what they were.  One whole gzip member is inflated on ctx's device WITHOUT AN INDEX: both of this library's
+ * writers end a run of deflate blocks with an empty stored block (00 00 FF FF on a byte boundary: the host leg every 1 MiB block, the
+ * device leg every dynamic 65 536-byte piece) and start the next run without history, so the positions behind those four bytes are
+ * found bytewise and a wave decodes from each.
+ *
+ * FORMAT RULE.  A CANDIDATE is a byte offset p with gz[p - 4, p) == 00 00 FF FF and p <= n - 8, or the first byte behind the gzip
+ * header (parsed on the host with FEXTRA / FNAME / FCOMMENT / FHCRC; a wrong magic, a method other than 8, a reserved flag bit, a
+ * wrong header CRC or a header that does not end: MI_ERR_INVALID).  The SEGMENT from a candidate is decoded -- stored, fixed and
+ * dynamic blocks -- until an empty stored block with BFINAL 0 has been read (it ends at the byte behind it, a candidate), a block with
+ * BFINAL 1 has been read (END) or a rule of csrc/host_inflate.h's InflateRule is broken (they are zlib's, and a distance that
+ * reaches before the SEGMENT's first byte).  The LIVE CHAIN runs from the header's end along the segments' ends to END, which must
+ * lie at n - 8; candidates that are not on it are dead and ignored.  The live segments are decoded a second time to their final
+ * offsets, in rounds whose output fits a window (MI_INFLATE_WINDOW_MB, 1..1024, default 64: the output of a round AND the most one
+ * segment may inflate to), two rounds in flight on streams of the call's own; the CRC-32 of every round is taken on the device,
+ * combined on the host and held against the trailer with ISIZE (mod 2^32).
+ *
+ * VERDICTS.  MI_INFLATE_DONE: the output is the member's inflation, CRC and ISIZE checked.  MI_INFLATE_NOT_PARALLEL (returned as
+ * MI_OK): nothing is delivered and the caller inflates serially -- a live segment reaches before its own start (pgzip's and pigz's
+ * blocks carry the previous block's dictionary; this cannot be told from corruption, zlib decides), a live segment inflates to
+ * more than a window, or END lies before n - 8 (more members, trailing bytes); info names the segment (at_in, at_out: its input
+ * and output offsets) and the rule.  Any other broken rule on a LIVE segment, or a CRC / ISIZE mismatch, is MI_ERR_INVALID;
+ * mi_last_error names the segment's input offset, its output offset and the rule; the ctx stays usable.
+ *
+ * mi_inflate_buffer: gz[0, n) in host memory in, its inflation in dst.  The total is known after the size pass: cap too small is
+ * MI_ERR_CAPACITY with *out_bytes = the size needed (cap == 0 with dst == NULL asks for it); on NOT_PARALLEL *out_bytes is 0.  A
+ * NULL ctx, gz or out_bytes, or a NULL dst with cap > 0: MI_ERR_INVALID.  The member lies whole on the device for the call; a failed
+ * allocation is MI_ERR_NOMEM.  info (may be NULL): the bytes, candidates, live segments, rounds, the verdict, the device time of
+ * the size pass (with the marking) and of the write passes.  Any failure leaves dst unspecified.
+ *
+ * mi_tar_inflate_ctx: mi_tar_inflate's contract and results through the device.  The blob is hashed (blob_sha256) while it goes
+ * up; the rounds come down in order into the SHA-256 stream (tar_sha256) and the output file (tar_path_out NULL: digests only).  A
+ * plain tar is copied through as mi_tar_inflate does.  On NOT_PARALLEL the call runs mi_tar_inflate itself and sets
+ * info->fell_back = 1; the output file is not created before the verdict is known.  A corrupt blob is MI_ERR_INVALID with
+ * "<blob_path>: corrupt gzip stream ..." in err, and no output file is left behind.                                            */
+#define MI_INFLATE_DONE 0
+#define MI_INFLATE_NOT_PARALLEL 1
+typedef struct { uint64_t in_bytes, out_bytes, n_candidates, n_segments, n_rounds, at_in, at_out;
+                 uint32_t verdict, rule, fell_back, reserved; double ms_size, ms_write; } mi_inflate_info;
+MI_BLOCK int  mi_inflate_buffer(mi_ctx* ctx, const void* gz, uint64_t n, void* dst, uint64_t cap, uint64_t* out_bytes, mi_inflate_info* info);
+MI_BLOCK int  mi_tar_inflate_ctx(mi_ctx* ctx, const char* blob_path, const char* tar_path_out, uint64_t* tar_bytes, uint8_t* tar_sha256,
+                                 uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap);
 /* step.commitLayer (lib/builder/step/common.go:67-111) in one call on a MemFS handle: the step's layer by scan
  * (must_scan: the root is walked here, with the handle's blacklist) or by its copy operations, written through the layer
  * writer configured by cfg (tarAndGzipDiffs: tar framing, TarDigest, the gzip leg with its digest and size), folded into

@@ -375,6 +375,19 @@ class DeflateInfo(C.Structure):
                 ("out_bytes", C.c_uint64), ("ms_device", C.c_double)]
 
 
+class InflateInfo(C.Structure):
+    _fields_ = [("in_bytes", C.c_uint64), ("out_bytes", C.c_uint64), ("n_candidates", C.c_uint64), ("n_segments", C.c_uint64),
+                ("n_rounds", C.c_uint64), ("at_in", C.c_uint64), ("at_out", C.c_uint64), ("verdict", C.c_uint32), ("rule", C.c_uint32),
+                ("fell_back", C.c_uint32), ("reserved", C.c_uint32), ("ms_size", C.c_double), ("ms_write", C.c_double)]
+
+
+INFLATE_DONE, INFLATE_NOT_PARALLEL = 0, 1
+
+
+def _inflate_info_dict(info):
+    return dict((f, getattr(info, f)) for f, _ in InflateInfo._fields_ if f != "reserved")
+
+
 def load_library(rebuild=False):
     """Loads (building first if stale) makisu_amd/libmakisu_mi.so.  Raises if it is missing."""
     global _lib
@@ -500,6 +513,8 @@ def load_library(rebuild=False):
         "mi_layer_set_gzip_ctx": ([vp, vp], C.c_int),
         "mi_deflate_bound": ([u64], u64),
         "mi_deflate_buffer": ([vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(DeflateInfo)], C.c_int),
+        "mi_inflate_buffer": ([vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateInfo)], C.c_int),
+        "mi_tar_inflate_ctx": ([vp, C.c_char_p, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.c_char_p, u64], C.c_int),
         "mi_layer_header_bytes": ([C.POINTER(TreeEntry), C.c_uint32, vp, u64, u64p], C.c_int),
         "mi_cache_parse_entry_str": ([C.c_char_p, C.c_char_p, u64, C.c_char_p, u64], C.c_int),
         "mi_cache_key": ([C.c_char_p, C.c_char_p, u64], C.c_int),
@@ -1894,6 +1909,36 @@ class Engine:
         self._check(self._lib.mi_deflate_buffer(self._h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, cap, C.byref(n),
                                                 C.byref(crc), C.byref(info)))
         return out[:n.value].tobytes(), crc.value, dict((f, getattr(info, f)) for f, _ in DeflateInfo._fields_)
+
+    def inflate_buffer(self, blob):
+        """mi_inflate_buffer: one whole gzip member -> (its inflation, info dict).  info["verdict"] is INFLATE_DONE, or
+        INFLATE_NOT_PARALLEL with b"" (the caller inflates serially: info names the segment and the rule); a corrupt member raises
+        MiError(-1)"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        n, info = C.c_uint64(), InflateInfo()
+        cap = int.from_bytes(src[-4:].tobytes(), "little") if src.size >= 18 else 0       # ISIZE: the size, if the member is sound
+        if cap > 1100 * src.size:                       # (deflate expands 1 032 times at the most: this ISIZE is not the size)
+            cap = 0
+        for _ in range(2):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self._lib.mi_inflate_buffer(self._h, src.ctypes.data if src.size else None, src.size, out.ctypes.data, cap, C.byref(n), C.byref(info))
+            if rc != -7:                                # MI_ERR_CAPACITY: *out_bytes is the size needed
+                break
+            cap = n.value
+        self._check(rc)
+        return out[:n.value].tobytes(), _inflate_info_dict(info)
+
+    def tar_inflate(self, blob_path, tar_path_out=None):
+        """mi_tar_inflate_ctx: tar_inflate() through this engine's device -> its dict + info (info["fell_back"] = 1: the blob
+        cannot be inflated in parallel and went through the host path)"""
+        nb, info = C.c_uint64(), InflateInfo()
+        t, g = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.mi_tar_inflate_ctx(self._h, os.fsencode(blob_path), os.fsencode(tar_path_out) if tar_path_out is not None else None,
+                                          C.byref(nb), t, g, C.byref(info), err, len(err))
+        if rc:
+            raise MiError(rc, "mi_tar_inflate_ctx: %s" % err.value.decode(errors="replace"))
+        return {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g), "info": _inflate_info_dict(info)}
 
     def index(self, capacity_hint=0):
         """A chunk-digest set that outlives batches (dedup across layers)."""

@@ -233,6 +233,12 @@ void launch_crc32_files(const u8* d_data, const u64* d_file_off, const u64* d_fi
 // mi_deflate.hip, for tests/kernel_probe: the device deflate leg's length-limiting rule alone (mi_deflate_wave.h df_code_lengths) --
 // d_counts[0, nsym) -> d_lens[0, nsym) under `limit` bits, by one wave; nsym <= 286, limit <= 15 (else nothing is launched)
 void launch_deflate_code_lengths(const u32* d_counts, u32 nsym, u32 limit, u8* d_lens, hipStream_t s);
+// mi_inflate.hip, for tests/kernel_probe: the device inflate's table builder alone (mi_inflate_wave.h inf_build) -- d_lens[0, nsym) ->
+// d_verdict[0..4] = over-subscribed, the code space left, symbols coded, the longest length, symbols decoded; d_out: what the bit
+// string d_bits[0, n_bits) decodes to under a primary table of tab_bits bits (at most max_out; 0xFFFF: no symbol, and the end).
+// nsym <= 288, 1 <= tab_bits <= 10 (else nothing is launched); d_bits is 4-byte aligned
+void launch_inflate_table(const u8* d_lens, u32 nsym, u32 tab_bits, const u8* d_bits, u32 n_bits, u32* d_verdict, u32* d_out, u32 max_out,
+                          hipStream_t s);
 u32 crc32_host_bytes(u32 crc, const void* data, size_t len);
 u32 crc32_host_combine(u32 crc1, u32 crc2, u64 len2);
 // d_table: 2 x cap_pow2 words (rep | complemented minima), cleared here with one memset

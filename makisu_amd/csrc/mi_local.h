@@ -68,6 +68,21 @@ MI_LOCAL const char* mi_deflater_error(const mi_deflater* d);
 MI_LOCAL void        mi_deflater_info(const mi_deflater* d, mi_deflate_info* out);
 MI_LOCAL void        mi_deflater_free(mi_deflater* d);
 MI_LOCAL uint64_t    mi_deflate_device_window(void);          // MI_GZIP_DEVICE_WINDOW_MB (1..1024), default 32
+// mi_inflate.hip -- the device inflate behind mi_inflate_buffer and mi_tar_inflate_ctx.  plan: the member gz[0, n) goes
+// up whole (`seen`, may be NULL, is told every piece of it in order while it is under way: the blob's digest), the candidates are
+// marked, the size pass leaves its rows and the host walks the chain -- MI_OK with _info's verdict (DONE: out_bytes, n_rounds; NOT_PARALLEL:
+// the segment and the rule), MI_ERR_INVALID for a corrupt member (the message is _error's).  run, after a plan that said DONE: the
+// rounds come out through emit in order, two in flight, and the CRC-32 and ISIZE are held against the trailer at the end
+// (MI_ERR_INVALID).  One thread drives an inflater; the ctx stays usable after any failure.  Window: MI_INFLATE_WINDOW_MB (1..1024), 64
+struct mi_inflater;
+typedef void (*mi_inflate_seen_fn)(void* arg, const uint8_t* bytes, uint64_t n);
+typedef int (*mi_inflate_emit_fn)(void* arg, const uint8_t* bytes, uint64_t n);
+MI_LOCAL int         mi_inflater_create(mi_ctx* ctx, mi_inflater** out);
+MI_LOCAL int         mi_inflater_plan(mi_inflater* d, const uint8_t* gz, uint64_t n, mi_inflate_seen_fn seen, void* arg);
+MI_LOCAL int         mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg);
+MI_LOCAL const char* mi_inflater_error(const mi_inflater* d);
+MI_LOCAL void        mi_inflater_info(const mi_inflater* d, mi_inflate_info* out);
+MI_LOCAL void        mi_inflater_free(mi_inflater* d);
 // mi_batch_reserve for a walk whose enumeration runs ahead of what it hands over (and for mi_memfs_reserve_device): the arena
 // is the piecewise kind (mi_arena.hip) -- what is coming is known roughly and keeps growing
 MI_LOCAL int  mi_batch_reserve_ahead(mi_batch* b, uint64_t more_files, uint64_t more_bytes);
