@@ -864,6 +864,46 @@ typedef struct { uint64_t in_bytes, out_bytes, n_candidates, n_segments, n_round
 MI_BLOCK int  mi_inflate_buffer(mi_ctx* ctx, const void* gz, uint64_t n, void* dst, uint64_t cap, uint64_t* out_bytes, mi_inflate_info* info);
 MI_BLOCK int  mi_tar_inflate_ctx(mi_ctx* ctx, const char* blob_path, const char* tar_path_out, uint64_t* tar_bytes, uint8_t* tar_sha256,
                                  uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap);
+/* A PULLED LAYER BECOMES A BATCH (csrc/mi_layerblob.hip, csrc/mi_tarscan.hip, csrc/host_tarcache.h).  The
+ * reference fills its tree from a base or cached layer by reading the tar (MemFS.UpdateFromTarPath, lib/snapshot/mem_fs.go:139-161:
+ * open, tario.NewGzipReader when the blob is gzip, UpdateFromTarReader).  Everything behind this library's scan takes a batch
+ * (mi_index_add_batch, mi_batch_pack_chunks, mi_batch_zpack_chunks, mi_zset_missing, the roots, the dedup marks); this call fills
+ * one from a layer blob in one way up: the blob -- this library's device-leg gzip, its host-leg gzip, a foreign gzip or a plain tar
+ * -- is uploaded once, inflated on the device STRAIGHT INTO THE BATCH'S ARENA, and its regular members become the batch's files
+ * where they lie: the tar does not come down, no tar file is written, nothing is staged twice, no member is copied on the device.
+ * The host needs only the tar's headers: the device marks every 512-byte block for which the parser's checksum rule holds (a meta
+ * header -- x, g, L, K -- takes the next two blocks with it), the marked blocks come down, and mi_tar_open_ex's own parser follows
+ * the live chain through them; what the cache does not hold (the end marker, a meta body beyond 1 024 bytes, a block on the chain
+ * the device did not mark -- which the parser then refuses) is fetched on demand, and counted.
+ *
+ * source: 0 a plain tar (uploaded as it is), 1 gzip inflated on the device (the plan said MI_INFLATE_DONE; the member's CRC-32 and
+ * ISIZE are checked on the device), 2 a gzip that is not parallel (MI_INFLATE_NOT_PARALLEL: zlib inflates it into host memory of
+ * the tar's size, which then goes up as a plain tar).  Every regular member (kind 1, empty ones included) becomes, in listing
+ * order, the file {arena_at + data_offset, size, tag_base + file_index}; its batch index is first_file + file_index.  arena_at is a
+ * multiple of 256 and data offsets are multiples of 512, so every member starts on the boundary every other add gives a file.
+ * *listing (may be NULL) receives the archive's mi_tar (mi_tar_entries; data offsets are offsets in the tar; mi_tar_free).
+ * blob_sha256 (may be NULL): the blob's own SHA-256, taken while it goes up.  NO TarDigest comes out of this call, on purpose: it
+ * is the serial SHA-256 stream this path exists to avoid -- a cache hit knows the pair from its entry (mi_cache_parse_entry), and
+ * a caller who wants the diffID computed keeps mi_tar_inflate_ctx.  Files from a layer carry no end-to-end byte sums (they never
+ * crossed PCIe as files); to everything behind the add they are ordinary files.  The call returns when the device work is done.
+ *
+ * info (may be NULL): the tar's size, where it lies, the files and entries, the blocks the device marked (n_marked), the headers
+ * the listing consumed from them (n_live), the on-demand fetches and their bytes, the source, the host's time for the way up
+ * (ms_upload; a gzip blob: the plan's time less its device time) and for the header pass with the listing (ms_headers), and the
+ * inflater's own info.
+ *
+ * On ANY failure the batch's files, bytes, arena offset and usability are what they were (the arena may have grown).  NULL b or
+ * blob: MI_ERR_INVALID; a batch that ran: MI_ERR_STATE; a batch group: MI_ERR_INVALID; a corrupt gzip: MI_ERR_INVALID with the
+ * inflater's message; a tar error: MI_ERR_INVALID with mi_tar_open_ex's text for the same archive -- all in mi_last_error.
+ * _path maps the file and calls _blob.  One GPU; the blob (gzip) and the tar both lie in device memory for the call. */
+typedef struct { uint64_t tar_bytes, arena_at, first_file, n_files, n_entries,
+                 n_marked, n_live, n_fetched, fetched_bytes;
+                 uint32_t source, reserved;      /* 0 plain tar, 1 gzip inflated on the device, 2 gzip through zlib */
+                 double ms_upload, ms_headers; mi_inflate_info inflate; } mi_layer_blob_info;
+MI_BLOCK int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t tag_base,
+                                     mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
+MI_BLOCK int mi_batch_add_layer_path(mi_batch* b, const char* blob_path, uint64_t tag_base,
+                                     mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
 /* step.commitLayer (lib/builder/step/common.go:67-111) in one call on a MemFS handle: the step's layer by scan
  * (must_scan: the root is walked here, with the handle's blacklist) or by its copy operations, written through the layer
  * writer configured by cfg (tarAndGzipDiffs: tar framing, TarDigest, the gzip leg with its digest and size), folded into

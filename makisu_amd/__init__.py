@@ -384,6 +384,16 @@ class InflateInfo(C.Structure):
 INFLATE_DONE, INFLATE_NOT_PARALLEL = 0, 1
 
 
+class LayerBlobInfo(C.Structure):
+    _fields_ = [("tar_bytes", C.c_uint64), ("arena_at", C.c_uint64), ("first_file", C.c_uint64), ("n_files", C.c_uint64),
+                ("n_entries", C.c_uint64), ("n_marked", C.c_uint64), ("n_live", C.c_uint64), ("n_fetched", C.c_uint64),
+                ("fetched_bytes", C.c_uint64), ("source", C.c_uint32), ("reserved", C.c_uint32), ("ms_upload", C.c_double),
+                ("ms_headers", C.c_double), ("inflate", InflateInfo)]
+
+
+LAYER_SOURCE_TAR, LAYER_SOURCE_DEVICE_GZIP, LAYER_SOURCE_ZLIB = 0, 1, 2
+
+
 def _inflate_info_dict(info):
     return dict((f, getattr(info, f)) for f, _ in InflateInfo._fields_ if f != "reserved")
 
@@ -515,6 +525,8 @@ def load_library(rebuild=False):
         "mi_deflate_buffer": ([vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(C.c_uint32), C.POINTER(DeflateInfo)], C.c_int),
         "mi_inflate_buffer": ([vp, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateInfo)], C.c_int),
         "mi_tar_inflate_ctx": ([vp, C.c_char_p, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.c_char_p, u64], C.c_int),
+        "mi_batch_add_layer_blob": ([vp, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
+        "mi_batch_add_layer_path": ([vp, C.c_char_p, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
         "mi_layer_header_bytes": ([C.POINTER(TreeEntry), C.c_uint32, vp, u64, u64p], C.c_int),
         "mi_cache_parse_entry_str": ([C.c_char_p, C.c_char_p, u64, C.c_char_p, u64], C.c_int),
         "mi_cache_key": ([C.c_char_p, C.c_char_p, u64], C.c_int),
@@ -653,6 +665,24 @@ def commit_order(relpaths):
     return [int(out[i]) for i in range(n)]
 
 
+def _tar_handle_entries(L, h, n):
+    """the n entries of an mi_tar as tar_entries' dicts; the handle is freed"""
+    try:
+        arr = (TreeEntry * max(n, 1))()
+        offs = (C.c_uint64 * max(n, 1))()
+        rc = L.mi_tar_entries(h, arr, offs, n)
+        if rc:
+            raise MiError(rc, "mi_tar_entries")
+        out = []
+        for i in range(n):
+            d = _entry_dict(arr[i])
+            d["data_offset"] = int(offs[i])
+            out.append(d)
+        return out
+    finally:
+        L.mi_tar_free(h)
+
+
 def tar_entries(path):
     """mi_tar_open + mi_tar_entries: the entries of an uncompressed layer tar as dicts (the keys of
     tree_walk(full=True) plus "data_offset": where a regular file's bytes start in the archive)."""
@@ -662,20 +692,7 @@ def tar_entries(path):
     rc = L.mi_tar_open_ex(os.fsencode(path), C.byref(h), C.byref(n), None, err, len(err))
     if rc:
         raise MiError(rc, "mi_tar_open: %s" % err.value.decode(errors="replace"))
-    try:
-        arr = (TreeEntry * max(n.value, 1))()
-        offs = (C.c_uint64 * max(n.value, 1))()
-        rc = L.mi_tar_entries(h, arr, offs, n.value)
-        if rc:
-            raise MiError(rc, "mi_tar_entries")
-        out = []
-        for i in range(n.value):
-            d = _entry_dict(arr[i])
-            d["data_offset"] = int(offs[i])
-            out.append(d)
-        return out
-    finally:
-        L.mi_tar_free(h)
+    return _tar_handle_entries(L, h, n.value)
 
 
 def tar_inflate(blob_path, tar_path_out=None):
@@ -2209,6 +2226,28 @@ class Batch:
             ptr, n = sel.ctypes.data, len(select)
         self._check(self._lib.mi_batch_zpack_chunks(self._h, ptr, n, (ZPACK_VERIFY if verify else 0) | _zpack_level_flag(level), C.byref(h)))
         return ZPack(self.engine, h)
+
+    def add_layer_blob(self, blob, tag_base=0):
+        """mi_batch_add_layer_blob: a layer blob (gzip or plain tar) in host memory goes up once, is inflated on the device into this
+        batch's arena where that is possible, and its regular members become the batch's files where they lie (batch index
+        info["first_file"] + the entry's "file_index", tag tag_base + "file_index").  -> (entries as tar_entries gives them, their
+        data offsets in the tar, info dict, the blob's SHA-256 as 32 bytes).  A failure raises MiError and leaves the batch as it was"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        keep = src if src.size else np.zeros(1, dtype=np.uint8)      # (never NULL: an empty blob is an empty archive)
+        return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_blob(self._h, keep.ctypes.data, src.size, tag_base, C.byref(h), sha,
+                                                                                       C.byref(info)))
+
+    def add_layer_path(self, path, tag_base=0):
+        """mi_batch_add_layer_path: add_layer_blob for a blob file, mapped by the library"""
+        return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_path(self._h, os.fsencode(path), tag_base, C.byref(h), sha, C.byref(info)))
+
+    def _add_layer(self, call):
+        h, sha, info = C.c_void_p(), (C.c_uint8 * 32)(), LayerBlobInfo()
+        self._check(call(h, sha, info))
+        entries = _tar_handle_entries(self._lib, h, info.n_entries)
+        d = dict((f, getattr(info, f)) for f, _ in LayerBlobInfo._fields_ if f not in ("reserved", "inflate"))
+        d["inflate"] = _inflate_info_dict(info.inflate)
+        return entries, [e["data_offset"] for e in entries], d, bytes(sha)
 
     def add_recipes(self, packset, recipes, tags=None, verify=False):
         """mi_batch_add_recipes: one file per recipe, assembled on the device from the pack set.  recipes: a list of (digests:

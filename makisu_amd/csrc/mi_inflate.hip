@@ -12,7 +12,9 @@
 //   inflate_write_kernel         one wave a live segment: the decode again, to its final offset in the round's output
 //   crc32.hip's tiles and fold over the round's output as ONE file: the rounds' CRCs are combined on the host
 // and comes down through a pinned window.  TWO ROUNDS are in flight, on streams of the object's own (never the ctx's scan stream):
-// round k comes down on the copy stream while round k + 1 is decoded on the code stream.
+// round k comes down on the copy stream while round k + 1 is decoded on the code stream.  With a DEVICE DESTINATION
+// (mi_inflater_run_device, DESIGN 4.21: a layer inflated into a batch's arena) a round is decoded where it belongs in the caller's
+// memory, its CRC taken there, and only the CRC and the bad word come down.
 #include "mi_internal.h"
 #include "mi_inflate_wave.h"
 #include "mi_plan.h"
@@ -229,7 +231,8 @@ int upload(mi_inflater* d, const u8* gz, u64 n, mi_inflate_seen_fn seen, void* a
     return MI_OK;
 }
 
-int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg) {
+// windows: the round's output lies in the slot's own d_out and comes down through h_out (false: the caller's device destination)
+int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg, bool windows) {
     const u64 nt = (out_bytes + kGearTile - 1) / kGearTile;
     if (!s->h_small.p) {
         IFCHK(d, s->h_small.ensure(64));
@@ -241,9 +244,11 @@ int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg) {
         IFCHK(d, s->t0.create());
         IFCHK(d, s->t1.create());
     }
-    if (out_bytes > s->h_out.bytes || !s->d_out.p) {
-        IFCHK(d, s->h_out.ensure(out_bytes ? out_bytes : 1));
-        IFCHK(d, s->d_out.alloc_exact(out_bytes));
+    if (windows ? out_bytes > s->h_out.bytes || !s->d_out.p : nt * 4 + 256 > s->d_tile_file.bytes) {
+        if (windows) {
+            IFCHK(d, s->h_out.ensure(out_bytes ? out_bytes : 1));
+            IFCHK(d, s->d_out.alloc_exact(out_bytes));
+        }
         IFCHK(d, s->d_tile_file.alloc_exact(nt * 4));
         IFCHK(d, s->d_tile_raw.alloc_exact(nt * 4));
         if (nt) IFCHK(d, hipMemsetAsync(s->d_tile_file.p, 0, nt * 4, d->code));     // every tile is file 0's
@@ -255,8 +260,10 @@ int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg) {
     return MI_OK;
 }
 
-// round r of the plan: its segments' table goes up, the decode, the CRC, the bytes on their way down; s->down is its end
-int slot_submit(mi_inflater* d, Slot* s, u64 r) {
+// round r of the plan: its segments' table goes up, the decode, the CRC, the bytes on their way down; s->down is its end.
+// d_dst (may be NULL: the slot's window): the member's inflation lies at d_dst[0, total) -- the round is written where it
+// belongs there and no byte comes down
+int slot_submit(mi_inflater* d, Slot* s, u64 r, u8* d_dst) {
     const u64 a = d->round_first[r], b = d->round_first[r + 1];
     const mi_host::InflateSeg* segs = d->chain.segs.data();
     const u64 base = segs[a].out_at;
@@ -272,16 +279,17 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r) {
     s->n_seg = b - a;
     u64* row = s->h_small.as<u64>();
     row[0] = 0; row[1] = bytes; row[2] = 0; row[4] = 0; row[5] = ~0ull;
+    u8* out = d_dst ? d_dst + base : s->d_out.as<u8>();
     IFCHK(d, hipMemcpyAsync(s->d_seg.p, t, 24 * s->n_seg, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipMemcpyAsync(s->d_row.p, row, 24, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipMemcpyAsync(s->d_bad.p, row + 5, 8, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipEventRecord(s->t0, d->code));
     hipLaunchKernelGGL(inflate_write_kernel, dim3((u32)s->n_seg), dim3(64), 0, d->code, d->d_gz.as<u8>(), d->n, s->d_seg.as<u64>(), s->n_seg, bytes,
-                       s->d_out.as<u8>(), s->d_bad.as<u64>());
+                       out, s->d_bad.as<u64>());
     IFCHK(d, hipEventRecord(s->t1, d->code));
     if (bytes) {
         const u64* rw = s->d_row.as<u64>();
-        launch_crc32_files(s->d_out.as<u8>(), rw, rw + 1, s->d_tile_file.as<u32>(), rw + 2, (bytes + kGearTile - 1) / kGearTile, 1,
+        launch_crc32_files(out, rw, rw + 1, s->d_tile_file.as<u32>(), rw + 2, (bytes + kGearTile - 1) / kGearTile, 1,
                            d->ctx->crc_consts.as<u32>(), s->d_tile_raw.as<u32>(), s->d_crc.as<u32>(), d->code);
         IFCHK(d, hipMemcpyAsync(row + 4, s->d_crc.p, 4, hipMemcpyDeviceToHost, d->code));
     }
@@ -289,7 +297,7 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r) {
     IFCHK(d, hipMemcpyAsync(row + 5, s->d_bad.p, 8, hipMemcpyDeviceToHost, d->code));
     IFCHK(d, hipEventRecord(s->done, d->code));
     IFCHK(d, hipStreamWaitEvent(d->copy, s->done, 0));
-    if (bytes) IFCHK(d, hipMemcpyAsync(s->h_out.p, s->d_out.p, bytes, hipMemcpyDeviceToHost, d->copy));
+    if (bytes && !d_dst) IFCHK(d, hipMemcpyAsync(s->h_out.p, s->d_out.p, bytes, hipMemcpyDeviceToHost, d->copy));
     IFCHK(d, hipEventRecord(s->down, d->copy));
     s->pending = true;
     return MI_OK;
@@ -297,7 +305,7 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r) {
 
 struct RunState { u32 crc = 0; u64 bytes = 0; };
 
-// waits for the round, folds its CRC into the member's and hands its bytes on
+// waits for the round, folds its CRC into the member's and hands its bytes on (emit NULL: they stay where they are)
 int slot_finish(mi_inflater* d, Slot* s, RunState* st, mi_inflate_emit_fn emit, void* arg) {
     if (!s->pending) return MI_OK;
     s->pending = false;
@@ -312,7 +320,7 @@ int slot_finish(mi_inflater* d, Slot* s, RunState* st, mi_inflate_emit_fn emit, 
         st->crc = st->bytes ? crc32_host_combine(st->crc, (u32)row[4], s->bytes) : (u32)row[4];
         st->bytes += s->bytes;
     }
-    return s->bytes ? emit(arg, s->h_out.as<u8>(), s->bytes) : MI_OK;
+    return s->bytes && emit ? emit(arg, s->h_out.as<u8>(), s->bytes) : MI_OK;
 }
 
 }  // namespace
@@ -409,8 +417,8 @@ int mi_inflater_plan(mi_inflater* d, const uint8_t* gz, uint64_t n, mi_inflate_s
     }
 }
 
-int mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg) {
-    if (!d || !emit) return MI_ERR_INVALID;
+// the rounds of a plan that said DONE, two in flight: through emit (d_dst NULL) or to d_dst (emit NULL)
+static int inflater_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u8* d_dst) {
     if (d->info.verdict != MI_INFLATE_DONE || d->round_first.empty()) return d->fail(MI_ERR_STATE, "device inflate: run without a plan");
     IFCHK(d, hipSetDevice(d->ctx->device));
     const u64 n_rounds = d->round_first.size() - 1;
@@ -426,8 +434,8 @@ int mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg) {
     for (u64 r = 0; r < n_rounds && rc == MI_OK; ++r) {
         Slot* s = &d->slot[r & 1];
         rc = slot_finish(d, s, &st, emit, arg);             // round r - 2, while r - 1 is under way
-        if (rc == MI_OK) rc = slot_prepare(d, s, most_bytes, most_seg);
-        if (rc == MI_OK) rc = slot_submit(d, s, r);
+        if (rc == MI_OK) rc = slot_prepare(d, s, most_bytes, most_seg, d_dst == nullptr);
+        if (rc == MI_OK) rc = slot_submit(d, s, r, d_dst);
     }
     for (u64 r = n_rounds; r < n_rounds + 2 && rc == MI_OK; ++r) rc = slot_finish(d, &d->slot[r & 1], &st, emit, arg);
     if (rc != MI_OK) {
@@ -443,6 +451,18 @@ int mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg) {
                        "lies at input offset %llu (output offset %llu)", (unsigned long long)st.bytes, st.crc, d->want_isize, d->want_crc,
                        (unsigned long long)d->chain.at_in, (unsigned long long)d->chain.at_out);
     return MI_OK;
+}
+
+int mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg) {
+    if (!d || !emit) return MI_ERR_INVALID;
+    return inflater_rounds(d, emit, arg, nullptr);
+}
+
+// what lies at d_dst was put there on wait_for (may be NULL: nothing to wait for) -- the rounds begin behind it
+int mi_inflater_run_device(mi_inflater* d, uint8_t* d_dst, hipStream_t wait_for) {
+    if (!d || !d_dst) return MI_ERR_INVALID;
+    if (wait_for) IFCHK(d, hipStreamSynchronize(wait_for));
+    return inflater_rounds(d, nullptr, nullptr, d_dst);
 }
 
 void mi_inflater_free(mi_inflater* d) {

@@ -83,6 +83,20 @@ MI_LOCAL int         mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, vo
 MI_LOCAL const char* mi_inflater_error(const mi_inflater* d);
 MI_LOCAL void        mi_inflater_info(const mi_inflater* d, mi_inflate_info* out);
 MI_LOCAL void        mi_inflater_free(mi_inflater* d);
+// run with a DEVICE destination: the member's inflation goes to d_dst[0, out_bytes) -- each round is decoded where it
+// belongs there, its CRC-32 taken over that range, and only the CRC and the bad word come down; CRC and ISIZE are held against the
+// trailer as in _run, with the same messages.  wait_for (may be NULL): the stream on which d_dst was made ready.  The bytes lie
+// there when the call returns
+typedef struct ihipStream_t* hipStream_t;
+MI_LOCAL int         mi_inflater_run_device(mi_inflater* d, uint8_t* d_dst, hipStream_t wait_for);
+// mi_tar.hip -- an mi_tar from a tar of tar_bytes that lies on the device: blocks / kinds / dense are what
+// mi_tarscan.hip brought down (n_marked of them; host_tarcache.h), fetch copies tar[off, off + n) to dst for what the cache does
+// not hold (MI_OK, or the listing fails with MI_ERR_IO).  The parser, its errors and its texts are mi_tar_open_ex's (err: the
+// text without a path).  counts (may be NULL; four words): headers served from the cache as header candidates, fetches, fetched bytes, entries.
+// mi_tar_entries and mi_tar_free work on *out as on any other
+typedef int (*mi_tar_fetch_fn)(void* arg, uint64_t off, void* dst, uint64_t n);
+MI_LOCAL int         mi_tar_open_device(uint64_t tar_bytes, const uint64_t* blocks, const uint8_t* kinds, const uint8_t* dense, uint64_t n_marked,
+                                        mi_tar_fetch_fn fetch, void* fetch_arg, mi_tar** out, uint64_t* counts, char* err, uint64_t err_cap);
 // mi_batch_reserve for a walk whose enumeration runs ahead of what it hands over (and for mi_memfs_reserve_device): the arena
 // is the piecewise kind (mi_arena.hip) -- what is coming is known roughly and keeps growing
 MI_LOCAL int  mi_batch_reserve_ahead(mi_batch* b, uint64_t more_files, uint64_t more_bytes);

@@ -54,6 +54,8 @@
 #include <zlib.h>
 
 #include "host_sha256.h"
+#include "host_tarcache.h"
+#include "mi_local.h"
 
 #include <map>
 #include <string>
@@ -189,8 +191,10 @@ static bool parse_pax(const std::string& body, std::map<std::string, std::string
     return true;
 }
 
-// Where the tar bytes come from: a plain file (random access) or a gzip stream (forward only --
-// the parser only ever moves forward).
+// Where the tar bytes come from: a plain file (random access), a gzip stream (forward only --
+// the parser only ever moves forward) or a tar of known size that lies ON THE DEVICE:
+// a plain source whose reads are served from the header cache the device filled (host_tarcache.h)
+// and, where the cache does not hold what is asked, by an on-demand fetch.
 struct Source {
     int fd = -1;
     bool gz = false;
@@ -201,8 +205,36 @@ struct Source {
     std::vector<unsigned char> in, sink;   // compressed input window; where skipped bytes are inflated to
     uint64_t in_off = 0, pos = 0;      // compressed bytes consumed from fd, uncompressed position
     std::string error;
+    // device state: the cache, who fetches what it does not hold, the last fetch (an end marker's second block lies in it),
+    // and the counts -- headers served from the cache as header candidates, fetches, their bytes
+    mi_host::TarCache* cache = nullptr;
+    mi_tar_fetch_fn fetch = nullptr;
+    void* fetch_arg = nullptr;
+    std::vector<unsigned char> fetched;
+    uint64_t fetched_off = 0, n_live = 0, n_fetched = 0, fetched_bytes = 0;
 
     ~Source() { if (z_ready) inflateEnd(&z); }
+
+    // [off, off + n) of the device's tar, n > 0 and inside it; header: the parser reads a header here
+    bool device_read(uint64_t off, void* dst, size_t n, bool header) {
+        uint8_t kind = 0;
+        if (const uint8_t* p = cache->lookup(off, n, &kind)) {
+            memcpy(dst, p, n);
+            if (header && (kind & mi_host::kTarHeader)) ++n_live;
+            return true;
+        }
+        if (off < fetched_off || off + n > fetched_off + fetched.size()) {
+            uint64_t first = 0, bytes = 0;
+            mi_host::tar_fetch_range(off, n, size, &first, &bytes);
+            fetched.resize((size_t)bytes);
+            fetched_off = first;
+            if (fetch(fetch_arg, first, fetched.data(), bytes) != MI_OK) { fetched.clear(); error = "the archive could not be read from the device"; return false; }
+            ++n_fetched;
+            fetched_bytes += bytes;
+        }
+        memcpy(dst, fetched.data() + (off - fetched_off), n);
+        return true;
+    }
 
     bool open_fd(int f) {
         fd = f;
@@ -256,6 +288,7 @@ struct Source {
     bool read_at(uint64_t off, void* dst, size_t n) {
         if (!gz) {
             if (off + n > size) return false;
+            if (cache) return n == 0 || device_read(off, dst, n, false);
             size_t got = 0;
             while (got < n) {
                 const ssize_t r = pread(fd, (char*)dst + got, n - got, (off_t)(off + got));
@@ -277,6 +310,7 @@ struct Source {
         if (!gz) {
             if (off >= size) return 0;
             const size_t m = (size_t)(size - off < n ? size - off : n);
+            if (cache) return device_read(off, dst, m, true) ? m : 0;
             return read_at(off, dst, m) ? m : 0;
         }
         if (off < pos) { error = "gzip source cannot seek backwards"; return 0; }
@@ -518,6 +552,30 @@ int mi_tar_open_ex(const char* path, mi_tar** out, uint64_t* n_entries, int* is_
     for (const mi_tarfile::Item& it : h->t.items) h->rel.push_back(mi_tarfile::rel_name(it.name));
     *out = h;
     if (n_entries) *n_entries = h->t.items.size();
+    return MI_OK;
+}
+
+// (hidden: mi_local.h) the listing of a tar of tar_bytes that lies on the device, through the header cache
+int mi_tar_open_device(uint64_t tar_bytes, const uint64_t* blocks, const uint8_t* kinds, const uint8_t* dense, uint64_t n_marked,
+                       mi_tar_fetch_fn fetch, void* fetch_arg, mi_tar** out, uint64_t* counts, char* err, uint64_t err_cap) {
+    if (!out || !fetch) return MI_ERR_INVALID;
+    *out = nullptr;
+    mi_host::TarCache cache(blocks, kinds, dense, n_marked);
+    mi_tarfile::Source src;
+    src.size = tar_bytes;
+    src.cache = &cache;
+    src.fetch = fetch;
+    src.fetch_arg = fetch_arg;
+    mi_tar* h = new mi_tar();
+    const int rc = mi_tarfile::parse(src, &h->t);
+    if (counts) { counts[0] = src.n_live; counts[1] = src.n_fetched; counts[2] = src.fetched_bytes; counts[3] = h->t.items.size(); }
+    if (rc) {
+        put_err(err, err_cap, h->t.error);
+        delete h;
+        return rc;
+    }
+    for (const mi_tarfile::Item& it : h->t.items) h->rel.push_back(mi_tarfile::rel_name(it.name));
+    *out = h;
     return MI_OK;
 }
 
