@@ -239,6 +239,13 @@ void launch_deflate_code_lengths(const u32* d_counts, u32 nsym, u32 limit, u8* d
 // nsym <= 288, 1 <= tab_bits <= 10 (else nothing is launched); d_bits is 4-byte aligned
 void launch_inflate_table(const u8* d_lens, u32 nsym, u32 tab_bits, const u8* d_bits, u32 n_bits, u32* d_verdict, u32* d_out, u32 max_out,
                           hipStream_t s);
+// ... and the two passes alone, with no kernel of their own.  ROWS: inflate_size_kernel over the starts the caller gives -- d_rows
+// takes n_starts rows of 32 bytes (host_inflate.h InflateRow: end, out_bytes, status, rule, bit); a start at or behind n leaves its row
+// as it was.  WRITE: inflate_write_kernel over the caller's segment table (three words a segment: where it starts in the member,
+// where its bytes go in d_out, how many they are -- what a row said) into d_out[0, round_bytes); *d_bad, ~0 before, takes the smallest
+// segment whose decode did not end as the table says.  d_gz is 4-byte aligned; nothing is launched for an empty list
+void launch_inflate_rows(const u8* d_gz, u64 n, const u64* d_starts, u64 n_starts, u64 window, void* d_rows, hipStream_t s);
+void launch_inflate_write(const u8* d_gz, u64 n, const u64* d_seg, u64 n_seg, u64 round_bytes, u8* d_out, u64* d_bad, hipStream_t s);
 u32 crc32_host_bytes(u32 crc, const void* data, size_t len);
 u32 crc32_host_combine(u32 crc1, u32 crc2, u64 len2);
 // d_table: 2 x cap_pow2 words (rep | complemented minima), cleared here with one memset

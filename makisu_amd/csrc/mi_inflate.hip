@@ -134,6 +134,17 @@ void launch_inflate_table(const u8* d_lens, u32 nsym, u32 tab_bits, const u8* d_
     hipLaunchKernelGGL(inflate_table_kernel, dim3(1), dim3(64), 0, s, d_lens, nsym, tab_bits, d_bits, n_bits, d_verdict, d_out, max_out);
 }
 
+// (hidden: the kernel probe's) the size pass over given starts, and the write pass over a given segment table
+void launch_inflate_rows(const u8* d_gz, u64 n, const u64* d_starts, u64 n_starts, u64 window, void* d_rows, hipStream_t s) {
+    if (n_starts == 0 || n_starts > 0x7FFFFFFFull) return;
+    hipLaunchKernelGGL(inflate_size_kernel, dim3((u32)n_starts), dim3(64), 0, s, d_gz, n, d_starts, n_starts, window, (mi_host::InflateRow*)d_rows);
+}
+
+void launch_inflate_write(const u8* d_gz, u64 n, const u64* d_seg, u64 n_seg, u64 round_bytes, u8* d_out, u64* d_bad, hipStream_t s) {
+    if (n_seg == 0 || n_seg > 0x7FFFFFFFull) return;
+    hipLaunchKernelGGL(inflate_write_kernel, dim3((u32)n_seg), dim3(64), 0, s, d_gz, n, d_seg, n_seg, round_bytes, d_out, d_bad);
+}
+
 }  // namespace mi
 
 using namespace mi;

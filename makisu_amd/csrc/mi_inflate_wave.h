@@ -51,7 +51,8 @@ namespace mi {
 typedef uint16_t u16;
 
 constexpr u32 kInfLitBits = 10, kInfDistBits = 8;   // the primary tables' index bits
-constexpr u32 kInfRing = 512;                       // the write pass's staging: literals and matches, flushed 254 bytes or more at a time
+constexpr u32 kInfRing = 512;                       // the write pass's staging: literals and matches, flushed 255 bytes or more at a time (in front of a token
+                                                    // once fill > kInfRing - 258), whatever it holds at a stored block and at the segment's end
 constexpr u32 kInfMaxLit = 288, kInfMaxDist = 32;   // symbols a code may have lengths for (the fixed code: all of them)
 constexpr u32 kInfLenCodeAt = 320;                  // lens[320, 339): the code-length code's own lengths
 constexpr u32 kInfNoSymbol = 0xFFFFu;

@@ -129,6 +129,8 @@ def test_every_block_type_and_the_match_edges(engine):
                      (ic.one_stream(x[:140000], 0), x[:140000]),                          # stored blocks of 65 535
                      (ic.one_stream(x[:30000], 6, zlib.Z_HUFFMAN_ONLY), x[:30000]),
                      (ic.one_stream(bytes(100000), 6, zlib.Z_RLE), bytes(100000)),         # distance 1, length 258
+                     # 32 KB of literals and a few short matches: zlib's longest distance is 32 768 - 262, so the repeat 32 768 behind is
+                     # written as literals -- distance 32 768 itself is test_gpu_inflate_planted.py's (far_first, far_second)
                      (ic.one_stream(ic.repeat_at(32768), 9), ic.repeat_at(32768)),
                      ic.source_at_start()):
         _check(engine, gz, data)
