@@ -864,6 +864,49 @@ typedef struct { uint64_t in_bytes, out_bytes, n_candidates, n_segments, n_round
 MI_BLOCK int  mi_inflate_buffer(mi_ctx* ctx, const void* gz, uint64_t n, void* dst, uint64_t cap, uint64_t* out_bytes, mi_inflate_info* info);
 MI_BLOCK int  mi_tar_inflate_ctx(mi_ctx* ctx, const char* blob_path, const char* tar_path_out, uint64_t* tar_bytes, uint8_t* tar_sha256,
                                  uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap);
+/* ANY GZIP MEMBER FROM AN INDEX OF CHECKPOINTS (opt-in; csrc/host_inflate_index.h, csrc/mi_inflate_index.hip).  The
+ * calls above pay off on blobs this library's device leg wrote.  For every other gzip -- a base image from a registry, a cache layer
+ * the reference wrote through pgzip, the host leg's blob -- the missing piece is the classic one (zran, rapidgzip): an index of
+ * CHECKPOINTS, each a deflate block boundary with its bit offset in the member, its output offset and the (up to) 32 KiB of output in
+ * front of it.  It is built once, by zlib, when the blob is pulled for the first time (zlib inflates serially then anyway; with
+ * tar_sha256 the same pass gives the TarDigest) and is kept beside the blob.  With it every SPAN between two checkpoints is
+ * independent: one wave a span decodes straight to the span's final offset, no size pass, no marker, any encoder's output.
+ *
+ * THE INDEX, little-endian, a pure function of (member, spacing): 64 bytes "MIGZIX01" | u64 member bytes | u64 out_bytes | u32 CRC-32 |
+ * u32 ISIZE | u64 gzip header length | u64 n_points | u64 spacing | u64 windows_bytes; n_points rows u64 in_bit | u64 out_at | u64 win_at
+ * | u32 win_bytes = min(32 768, out_at) | u32 0; the windows, each padded with zeros to 16.  Point 0 is the stream's start; after every
+ * non-final block that ends with at least `spacing` bytes of output since the last point there is a new one (spacing 0: 262 144; a
+ * point at which the output is already complete is dropped).  Only a single member that ends at n - 8 is indexed.
+ *
+ * mi_inflate_index_build (host only): gz[0, n) -> *index (malloc'ed: mi_inflate_index_free), *index_bytes.  CRC-32 and ISIZE are
+ * checked; tar_sha256 (may be NULL): the SHA-256 of the inflation.  MI_ERR_INVALID with the reason in err: no gzip header, a corrupt
+ * stream, a second member, trailing bytes, a wrong CRC-32 or ISIZE.  mi_inflate_index_check (host only): 0, or the number of the first
+ * reason an UNTRUSTED index is refused (mi_inflate_index_refusal: its text) -- 1 magic, 2 sizes, 3 point 0, 4 in_bit not ascending,
+ * 5 out_at not ascending, 6 in_bit behind the stream, 7 out_at behind the output, 8 win_bytes, 9 a window out of bounds, unaligned or
+ * overlapping, 10 (gz given) another member's: n, header length, CRC-32 or ISIZE differ.
+ *
+ * VERDICTS of the indexed calls, all returned as MI_OK: MI_INFLATE_DONE; MI_INFLATE_NOT_PARALLEL (a span larger than the window
+ * MI_INFLATE_WINDOW_MB, or the last span's stream ends before n - 8); MI_INFLATE_INDEX_REFUSED: the checker refused the index
+ * (info.reserved: its number), a span broke a rule (rule 12: it does not end where the index says; info: the span's at_in = in_bit / 8,
+ * at_out and the rule), or CRC-32 / ISIZE do not hold (rule 0).  A stale index cannot be told from a corrupt blob, so the index is
+ * only ever a hint: it never produces MI_ERR_INVALID and never delivers bytes that fail the trailer.
+ *
+ * mi_inflate_buffer_indexed: mi_inflate_buffer with the index.  The total is the index's: MI_ERR_CAPACITY (with *out_bytes = the size
+ * needed) comes before any device work; *out_bytes is 0 unless the verdict is DONE (dst is then unspecified).
+ * mi_tar_inflate_ctx_indexed: mi_tar_inflate_ctx with the index; on INDEX_REFUSED or NOT_PARALLEL any partial output is removed and
+ * mi_tar_inflate runs -- zlib decides whether the blob is corrupt --, info->fell_back = 2 when the index was refused, 1 otherwise.   */
+#define MI_INFLATE_INDEX_REFUSED 2
+typedef struct { uint64_t n_points, n_blocks, out_bytes, windows_bytes, spacing; double ms_build; } mi_inflate_index_info;
+MI_BLOCK int  mi_inflate_index_build(const void* gz, uint64_t n, uint64_t spacing, void** index, uint64_t* index_bytes,
+                                     mi_inflate_index_info* info, uint8_t* tar_sha256, char* err, uint64_t err_cap);
+MI_BLOCK void mi_inflate_index_free(void* index);
+MI_BLOCK int  mi_inflate_index_check(const void* index, uint64_t index_bytes, const void* gz, uint64_t n);
+MI_BLOCK const char* mi_inflate_index_refusal(int refusal);
+MI_BLOCK int  mi_inflate_buffer_indexed(mi_ctx* ctx, const void* gz, uint64_t n, const void* index, uint64_t index_bytes, void* dst, uint64_t cap,
+                                        uint64_t* out_bytes, mi_inflate_info* info);
+MI_BLOCK int  mi_tar_inflate_ctx_indexed(mi_ctx* ctx, const char* blob_path, const void* index, uint64_t index_bytes, const char* tar_path_out,
+                                         uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err,
+                                         uint64_t err_cap);
 /* A PULLED LAYER BECOMES A BATCH (csrc/mi_layerblob.hip, csrc/mi_tarscan.hip, csrc/host_tarcache.h).  The
  * reference fills its tree from a base or cached layer by reading the tar (MemFS.UpdateFromTarPath, lib/snapshot/mem_fs.go:139-161:
  * open, tario.NewGzipReader when the blob is gzip, UpdateFromTarReader).  Everything behind this library's scan takes a batch
@@ -904,6 +947,14 @@ MI_BLOCK int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, 
                                      mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
 MI_BLOCK int mi_batch_add_layer_path(mi_batch* b, const char* blob_path, uint64_t tag_base,
                                      mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
+/* ... with the blob's index of checkpoints (mi_inflate_index_build): a gzip blob whose index carries through is decoded
+ * span by span straight into the arena -- source 3.  The index is a hint: when it is refused (or a span is larger than the window) the
+ * batch is as it was and the call proceeds exactly as the unindexed one does, with info->inflate.fell_back = 2 (refused) and the
+ * source the unindexed call gives.  A plain tar ignores the index. */
+MI_BLOCK int mi_batch_add_layer_blob_indexed(mi_batch* b, const void* blob, uint64_t n, const void* index, uint64_t index_bytes,
+                                             uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
+MI_BLOCK int mi_batch_add_layer_path_indexed(mi_batch* b, const char* blob_path, const void* index, uint64_t index_bytes,
+                                             uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
 /* step.commitLayer (lib/builder/step/common.go:67-111) in one call on a MemFS handle: the step's layer by scan
  * (must_scan: the root is walked here, with the handle's blacklist) or by its copy operations, written through the layer
  * writer configured by cfg (tarAndGzipDiffs: tar framing, TarDigest, the gzip leg with its digest and size), folded into

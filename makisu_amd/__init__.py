@@ -382,6 +382,13 @@ class InflateInfo(C.Structure):
 
 
 INFLATE_DONE, INFLATE_NOT_PARALLEL = 0, 1
+INFLATE_INDEX_REFUSED = 2
+INFLATE_INDEX_SPACING = 262144
+
+
+class InflateIndexInfo(C.Structure):
+    _fields_ = [("n_points", C.c_uint64), ("n_blocks", C.c_uint64), ("out_bytes", C.c_uint64), ("windows_bytes", C.c_uint64),
+                ("spacing", C.c_uint64), ("ms_build", C.c_double)]
 
 
 class LayerBlobInfo(C.Structure):
@@ -392,10 +399,17 @@ class LayerBlobInfo(C.Structure):
 
 
 LAYER_SOURCE_TAR, LAYER_SOURCE_DEVICE_GZIP, LAYER_SOURCE_ZLIB = 0, 1, 2
+LAYER_SOURCE_INDEXED_GZIP = 3
 
 
 def _inflate_info_dict(info):
     return dict((f, getattr(info, f)) for f, _ in InflateInfo._fields_ if f != "reserved")
+
+
+def _indexed_info_dict(info):
+    d = _inflate_info_dict(info)
+    d["index_refusal"] = info.reserved                  # the checker's number when it refused the index, else 0
+    return d
 
 
 def load_library(rebuild=False):
@@ -527,6 +541,14 @@ def load_library(rebuild=False):
         "mi_tar_inflate_ctx": ([vp, C.c_char_p, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.c_char_p, u64], C.c_int),
         "mi_batch_add_layer_blob": ([vp, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
         "mi_batch_add_layer_path": ([vp, C.c_char_p, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
+        "mi_inflate_index_build": ([vp, u64, u64, C.POINTER(vp), C.POINTER(u64), C.POINTER(InflateIndexInfo), vp, C.c_char_p, u64], C.c_int),
+        "mi_inflate_index_free": ([vp], None),
+        "mi_inflate_index_check": ([vp, u64, vp, u64], C.c_int),
+        "mi_inflate_index_refusal": ([C.c_int], C.c_char_p),
+        "mi_inflate_buffer_indexed": ([vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateInfo)], C.c_int),
+        "mi_tar_inflate_ctx_indexed": ([vp, C.c_char_p, vp, u64, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.c_char_p, u64], C.c_int),
+        "mi_batch_add_layer_blob_indexed": ([vp, vp, u64, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
+        "mi_batch_add_layer_path_indexed": ([vp, C.c_char_p, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
         "mi_layer_header_bytes": ([C.POINTER(TreeEntry), C.c_uint32, vp, u64, u64p], C.c_int),
         "mi_cache_parse_entry_str": ([C.c_char_p, C.c_char_p, u64, C.c_char_p, u64], C.c_int),
         "mi_cache_key": ([C.c_char_p, C.c_char_p, u64], C.c_int),
@@ -707,6 +729,39 @@ def tar_inflate(blob_path, tar_path_out=None):
     if rc:
         raise MiError(rc, "mi_tar_inflate: %s" % err.value.decode(errors="replace"))
     return {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g)}
+
+
+def inflate_index_build(blob, spacing=0, want_digest=False):
+    """mi_inflate_index_build (host only): one whole gzip member -> (its index of checkpoints as bytes, info dict).  spacing 0: the
+    default, INFLATE_INDEX_SPACING.  want_digest: info["tar_digest"] is the SHA-256 of the inflation, taken in the same pass.  A member
+    that cannot be indexed (corrupt, two members, trailing bytes, a wrong CRC-32) raises MiError(-1) with the reason"""
+    L = load_library()
+    src = np.frombuffer(bytes(blob), dtype=np.uint8)
+    p, n, info = C.c_void_p(), C.c_uint64(), InflateIndexInfo()
+    sha = (C.c_uint8 * 32)() if want_digest else None
+    err = C.create_string_buffer(512)
+    rc = L.mi_inflate_index_build(src.ctypes.data if src.size else None, src.size, spacing, C.byref(p), C.byref(n), C.byref(info), sha, err, len(err))
+    if rc:
+        raise MiError(rc, err.value.decode(errors="replace") or "mi_inflate_index_build failed")
+    try:
+        index = C.string_at(p, n.value)
+    finally:
+        L.mi_inflate_index_free(p)
+    d = dict((f, getattr(info, f)) for f, _ in InflateIndexInfo._fields_)
+    if want_digest:
+        d["tar_digest"] = Digest.from_raw(sha)
+    return index, d
+
+
+def inflate_index_check(index, blob=None):
+    """mi_inflate_index_check (host only): an untrusted index -> (0, "ok"), or (the number of the first reason it is refused, its text);
+    blob: the member it is said to belong to"""
+    L = load_library()
+    ix = np.frombuffer(bytes(index), dtype=np.uint8)
+    gz = np.frombuffer(bytes(blob), dtype=np.uint8) if blob is not None else None
+    r = L.mi_inflate_index_check(ix.ctypes.data if ix.size else None, ix.size, gz.ctypes.data if gz is not None and gz.size else None,
+                                 gz.size if gz is not None else 0)
+    return r, L.mi_inflate_index_refusal(r).decode()
 
 
 def _entry_array(dicts, keep):
@@ -1957,6 +2012,40 @@ class Engine:
             raise MiError(rc, "mi_tar_inflate_ctx: %s" % err.value.decode(errors="replace"))
         return {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g), "info": _inflate_info_dict(info)}
 
+    def inflate_buffer_indexed(self, blob, index):
+        """mi_inflate_buffer_indexed: one whole gzip member and its index of checkpoints (inflate_index_build) -> (its inflation, info
+        dict).  info["verdict"] is INFLATE_DONE, or INFLATE_NOT_PARALLEL / INFLATE_INDEX_REFUSED with b"": the index is a hint, the
+        caller inflates without it (info names the span and the rule, info["index_refusal"] the checker's number)"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        ix = np.frombuffer(bytes(index), dtype=np.uint8)
+        keep = ix if ix.size else np.zeros(1, dtype=np.uint8)
+        n, info = C.c_uint64(), InflateInfo()
+        cap = 0
+        for _ in range(2):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            rc = self._lib.mi_inflate_buffer_indexed(self._h, src.ctypes.data if src.size else None, src.size, keep.ctypes.data, ix.size,
+                                                     out.ctypes.data, cap, C.byref(n), C.byref(info))
+            if rc != -7:                                # MI_ERR_CAPACITY: *out_bytes is the size needed
+                break
+            cap = n.value
+        self._check(rc)
+        return out[:n.value].tobytes(), _indexed_info_dict(info)
+
+    def tar_inflate_indexed(self, blob_path, index, tar_path_out=None):
+        """mi_tar_inflate_ctx_indexed: Engine.tar_inflate with the blob's index of checkpoints (info["fell_back"] = 2: the index was
+        refused and the blob went through the host path, 1: it is not parallel)"""
+        ix = np.frombuffer(bytes(index), dtype=np.uint8)
+        keep = ix if ix.size else np.zeros(1, dtype=np.uint8)
+        nb, info = C.c_uint64(), InflateInfo()
+        t, g = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+        err = C.create_string_buffer(512)
+        rc = self._lib.mi_tar_inflate_ctx_indexed(self._h, os.fsencode(blob_path), keep.ctypes.data, ix.size,
+                                                  os.fsencode(tar_path_out) if tar_path_out is not None else None, C.byref(nb), t, g, C.byref(info),
+                                                  err, len(err))
+        if rc:
+            raise MiError(rc, "mi_tar_inflate_ctx_indexed: %s" % err.value.decode(errors="replace"))
+        return {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g), "info": _indexed_info_dict(info)}
+
     def index(self, capacity_hint=0):
         """A chunk-digest set that outlives batches (dedup across layers)."""
         return ChunkIndex(self, capacity_hint)
@@ -2240,6 +2329,24 @@ class Batch:
     def add_layer_path(self, path, tag_base=0):
         """mi_batch_add_layer_path: add_layer_blob for a blob file, mapped by the library"""
         return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_path(self._h, os.fsencode(path), tag_base, C.byref(h), sha, C.byref(info)))
+
+    def add_layer_blob_indexed(self, blob, index, tag_base=0):
+        """mi_batch_add_layer_blob_indexed: add_layer_blob with the blob's index of checkpoints -- info["source"] is
+        LAYER_SOURCE_INDEXED_GZIP when the spans were decoded straight into the arena; a refused index leaves the batch as it was and the
+        call goes on as add_layer_blob does, with info["inflate"]["fell_back"] = 2"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        keep = src if src.size else np.zeros(1, dtype=np.uint8)
+        ix = np.frombuffer(bytes(index), dtype=np.uint8)
+        keep_ix = ix if ix.size else np.zeros(1, dtype=np.uint8)
+        return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_blob_indexed(self._h, keep.ctypes.data, src.size, keep_ix.ctypes.data,
+                                                                                               ix.size, tag_base, C.byref(h), sha, C.byref(info)))
+
+    def add_layer_path_indexed(self, path, index, tag_base=0):
+        """mi_batch_add_layer_path_indexed: add_layer_blob_indexed for a blob file, mapped by the library"""
+        ix = np.frombuffer(bytes(index), dtype=np.uint8)
+        keep_ix = ix if ix.size else np.zeros(1, dtype=np.uint8)
+        return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_path_indexed(self._h, os.fsencode(path), keep_ix.ctypes.data, ix.size,
+                                                                                               tag_base, C.byref(h), sha, C.byref(info)))
 
     def _add_layer(self, call):
         h, sha, info = C.c_void_p(), (C.c_uint8 * 32)(), LayerBlobInfo()

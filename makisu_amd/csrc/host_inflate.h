@@ -29,6 +29,7 @@ enum InflateRule : uint32_t {
     kInfInputEnds = 9,        // the input ends inside a block
     kInfDistance = 10,        // a distance that reaches before the segment's first byte
     kInfWindow = 11,          // output beyond the window
+    kInfIndex = 12,           // (a span of an index, host_inflate_index.h) the span does not end where the index says
 };
 
 static inline const char* inflate_rule_name(uint32_t rule) {
@@ -37,7 +38,8 @@ static inline const char* inflate_rule_name(uint32_t rule) {
                                         "a repeat with no previous length or a run that passes HLIT + HDIST", "no end-of-block code",
                                         "a literal/length or distance code that is over-subscribed or incomplete",
                                         "a symbol that does not exist", "input that ends inside a block",
-                                        "a distance that reaches before the segment's first byte", "output beyond the window"};
+                                        "a distance that reaches before the segment's first byte", "output beyond the window",
+                                        "the span does not end where the index says"};
     return rule < sizeof names / sizeof names[0] ? names[rule] : "?";
 }
 

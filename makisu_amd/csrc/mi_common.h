@@ -246,6 +246,13 @@ void launch_inflate_table(const u8* d_lens, u32 nsym, u32 tab_bits, const u8* d_
 // segment whose decode did not end as the table says.  d_gz is 4-byte aligned; nothing is launched for an empty list
 void launch_inflate_rows(const u8* d_gz, u64 n, const u64* d_starts, u64 n_starts, u64 window, void* d_rows, hipStream_t s);
 void launch_inflate_write(const u8* d_gz, u64 n, const u64* d_seg, u64 n_seg, u64 round_bytes, u8* d_out, u64* d_bad, hipStream_t s);
+// mi_inflate_index.hip, for tests/kernel_probe too: inflate_span_kernel over the caller's span table (six words a span: in_bit, end_bit
+// -- 0: the last span, which ends at its BFINAL block --, where its bytes go in d_out, how many they are, its window's offset in
+// d_hist, the window's bytes) into d_out[0, round_bytes).  d_hist[0, hist_total) is the window area.  *d_bad, ~0 before, takes the
+// smallest refused span; d_verdict holds 16 bytes a span (u32 span, u32 rule, u64 bit), written for a refused span only.  d_gz is
+// 4-byte aligned; nothing is launched for an empty list
+void launch_inflate_spans(const u8* d_gz, u64 n, const u64* d_span, u64 n_span, u64 round_bytes, u8* d_out, const u8* d_hist, u64 hist_total,
+                          u64* d_bad, void* d_verdict, hipStream_t s);
 u32 crc32_host_bytes(u32 crc, const void* data, size_t len);
 u32 crc32_host_combine(u32 crc1, u32 crc2, u64 len2);
 // d_table: 2 x cap_pow2 words (rep | complemented minima), cleared here with one memset

@@ -16,13 +16,13 @@
 // (mi_inflater_run_device, DESIGN 4.21: a layer inflated into a batch's arena) a round is decoded where it belongs in the caller's
 // memory, its CRC taken there, and only the CRC and the bad word come down.
 #include "mi_internal.h"
+#include "mi_inflate_local.h"
 #include "mi_inflate_wave.h"
 #include "mi_plan.h"
 #include "host_sha256.h"
 
 #include <errno.h>
 #include <fcntl.h>
-#include <stdarg.h>
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -154,57 +154,7 @@ namespace {
 
 constexpr u64 kMiB = 1ull << 20;
 constexpr u64 kStage = 4 * kMiB;                        // the member goes up in pieces of this, through two pinned buffers
-
-struct Slot {
-    PinBuf h_out, h_seg, h_small;                       // h_small: [0..2] the CRC pass's file row, [4] the CRC, [5] the bad segment
-    DevBuf d_out, d_seg, d_row, d_tile_file, d_tile_raw, d_crc, d_bad;
-    Event done, down, t0, t1;
-    u64 bytes = 0, n_seg = 0;
-    bool pending = false;
-};
-
-}  // namespace
-
-struct mi_inflater {
-    mi_ctx* ctx = nullptr;
-    u64 window = 0;
-    Stream code, copy;
-    PinBuf h_stage[2];
-    Event staged[2], t0, t1;
-    DevBuf d_gz, d_cand, d_rows, d_blk, d_tot;
-    Slot slot[2];
-    std::string err;
-    mi_inflate_info info = {};
-    // the plan
-    u64 n = 0, header = 0;
-    u32 want_crc = 0, want_isize = 0;
-    std::vector<u64> cand, round_first;
-    std::vector<InflateRow> rows;
-    mi_host::InflateChain chain;
-    ~mi_inflater() {                                    // nothing is under way when the buffers and events go
-        if (code) (void)hipStreamSynchronize(code);
-        if (copy) (void)hipStreamSynchronize(copy);
-    }
-    int fail(int code_, const char* fmt, ...) {
-        char buf[400];
-        va_list ap;
-        va_start(ap, fmt);
-        vsnprintf(buf, sizeof buf, fmt, ap);
-        va_end(ap);
-        err = buf;
-        return code_;
-    }
-};
-
-#define IFCHK(d, call)                                                                                                   \
-    do {                                                                                                                 \
-        const hipError_t e_ = (call);                                                                                    \
-        if (e_ != hipSuccess)                                                                                            \
-            return (d)->fail(e_ == hipErrorOutOfMemory ? MI_ERR_NOMEM : MI_ERR_HIP, "device inflate: %s failed: %s", #call, \
-                             hipGetErrorString(e_));                                                                     \
-    } while (0)
-
-namespace {
+typedef InfSlot Slot;
 
 u64 inflate_window() {
     u64 mb = 64;
@@ -212,8 +162,10 @@ u64 inflate_window() {
     return mb * kMiB;
 }
 
+}  // namespace
+
 // the member goes up through the two pinned buffers; `seen` (may be NULL) is told every piece, in order, while it is under way
-int upload(mi_inflater* d, const u8* gz, u64 n, mi_inflate_seen_fn seen, void* arg) {
+int mi::inflate_upload(mi_inflater* d, const u8* gz, u64 n, mi_inflate_seen_fn seen, void* arg) {
     if (guard_alloc()) {                                // exactly n bytes: the member's last byte is the allocation's last
         d->d_gz.release();
         void* p = nullptr;
@@ -242,6 +194,8 @@ int upload(mi_inflater* d, const u8* gz, u64 n, mi_inflate_seen_fn seen, void* a
     return MI_OK;
 }
 
+namespace {
+
 // windows: the round's output lies in the slot's own d_out and comes down through h_out (false: the caller's device destination)
 int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg, bool windows) {
     const u64 nt = (out_bytes + kGearTile - 1) / kGearTile;
@@ -264,10 +218,12 @@ int slot_prepare(mi_inflater* d, Slot* s, u64 out_bytes, u64 n_seg, bool windows
         IFCHK(d, s->d_tile_raw.alloc_exact(nt * 4));
         if (nt) IFCHK(d, hipMemsetAsync(s->d_tile_file.p, 0, nt * 4, d->code));     // every tile is file 0's
     }
-    if (24 * n_seg > s->h_seg.bytes) {
-        IFCHK(d, s->h_seg.ensure(24 * n_seg));
-        IFCHK(d, s->d_seg.alloc_exact(24 * n_seg));
+    const u64 row = d->indexed ? 48 : 24;               // a span's six words, a segment's three
+    if (row * n_seg > s->h_seg.bytes) {
+        IFCHK(d, s->h_seg.ensure(row * n_seg));
+        IFCHK(d, s->d_seg.alloc_exact(row * n_seg));
     }
+    if (d->indexed && 16 * n_seg > s->d_verdict.bytes) IFCHK(d, s->d_verdict.alloc_exact(16 * n_seg));
     return MI_OK;
 }
 
@@ -281,9 +237,11 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r, u8* d_dst) {
     u64* t = s->h_seg.as<u64>();
     u64 bytes = 0;
     for (u64 k = a; k < b; ++k) {
-        t[3 * (k - a)] = segs[k].in_at;
-        t[3 * (k - a) + 1] = segs[k].out_at - base;
-        t[3 * (k - a) + 2] = segs[k].out_bytes;
+        if (!d->indexed) {
+            t[3 * (k - a)] = segs[k].in_at;
+            t[3 * (k - a) + 1] = segs[k].out_at - base;
+            t[3 * (k - a) + 2] = segs[k].out_bytes;
+        }
         bytes += segs[k].out_bytes;
     }
     s->bytes = bytes;
@@ -291,12 +249,17 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r, u8* d_dst) {
     u64* row = s->h_small.as<u64>();
     row[0] = 0; row[1] = bytes; row[2] = 0; row[4] = 0; row[5] = ~0ull;
     u8* out = d_dst ? d_dst + base : s->d_out.as<u8>();
-    IFCHK(d, hipMemcpyAsync(s->d_seg.p, t, 24 * s->n_seg, hipMemcpyHostToDevice, d->code));
+    if (!d->indexed) IFCHK(d, hipMemcpyAsync(s->d_seg.p, t, 24 * s->n_seg, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipMemcpyAsync(s->d_row.p, row, 24, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipMemcpyAsync(s->d_bad.p, row + 5, 8, hipMemcpyHostToDevice, d->code));
     IFCHK(d, hipEventRecord(s->t0, d->code));
-    hipLaunchKernelGGL(inflate_write_kernel, dim3((u32)s->n_seg), dim3(64), 0, d->code, d->d_gz.as<u8>(), d->n, s->d_seg.as<u64>(), s->n_seg, bytes,
-                       out, s->d_bad.as<u64>());
+    if (d->indexed) {
+        const int rc = inflate_span_submit(d, s, a, b, base, bytes, out);
+        if (rc) return rc;
+    } else {
+        hipLaunchKernelGGL(inflate_write_kernel, dim3((u32)s->n_seg), dim3(64), 0, d->code, d->d_gz.as<u8>(), d->n, s->d_seg.as<u64>(), s->n_seg, bytes,
+                           out, s->d_bad.as<u64>());
+    }
     IFCHK(d, hipEventRecord(s->t1, d->code));
     if (bytes) {
         const u64* rw = s->d_row.as<u64>();
@@ -317,11 +280,12 @@ int slot_submit(mi_inflater* d, Slot* s, u64 r, u8* d_dst) {
 struct RunState { u32 crc = 0; u64 bytes = 0; };
 
 // waits for the round, folds its CRC into the member's and hands its bytes on (emit NULL: they stay where they are)
-int slot_finish(mi_inflater* d, Slot* s, RunState* st, mi_inflate_emit_fn emit, void* arg) {
+int slot_finish(mi_inflater* d, Slot* s, u64 r, RunState* st, mi_inflate_emit_fn emit, void* arg) {
     if (!s->pending) return MI_OK;
     s->pending = false;
     IFCHK(d, hipEventSynchronize(s->down));
     const u64* row = s->h_small.as<u64>();
+    if (row[5] != ~0ull && d->indexed) return inflate_span_refused(d, s, d->round_first[r], row[5]);
     if (row[5] != ~0ull)
         return d->fail(MI_ERR_HIP, "device inflate: segment %llu of a round did not decode a second time as it did the first", (unsigned long long)row[5]);
     float ms = 0;
@@ -370,7 +334,7 @@ int mi_inflater_plan(mi_inflater* d, const uint8_t* gz, uint64_t n, mi_inflate_s
                        (unsigned long long)n, (unsigned long long)d->header);
     d->want_crc = mi_host::inflate_le32(gz + n - 8);
     d->want_isize = mi_host::inflate_le32(gz + n - 4);
-    int rc = upload(d, gz, n, seen, arg);
+    int rc = inflate_upload(d, gz, n, seen, arg);
     if (rc) return rc;
     const u64 n_pos = n - 7, nb = (n_pos + kPlanTile - 1) / kPlanTile;
     IFCHK(d, d->d_blk.alloc_exact(nb * 8));
@@ -428,8 +392,10 @@ int mi_inflater_plan(mi_inflater* d, const uint8_t* gz, uint64_t n, mi_inflate_s
     }
 }
 
+}  // extern "C"
+
 // the rounds of a plan that said DONE, two in flight: through emit (d_dst NULL) or to d_dst (emit NULL)
-static int inflater_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u8* d_dst) {
+int mi::inflate_run_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u8* d_dst) {
     if (d->info.verdict != MI_INFLATE_DONE || d->round_first.empty()) return d->fail(MI_ERR_STATE, "device inflate: run without a plan");
     IFCHK(d, hipSetDevice(d->ctx->device));
     const u64 n_rounds = d->round_first.size() - 1;
@@ -444,11 +410,11 @@ static int inflater_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u
     int rc = MI_OK;
     for (u64 r = 0; r < n_rounds && rc == MI_OK; ++r) {
         Slot* s = &d->slot[r & 1];
-        rc = slot_finish(d, s, &st, emit, arg);             // round r - 2, while r - 1 is under way
+        rc = slot_finish(d, s, r - 2, &st, emit, arg);      // round r - 2, while r - 1 is under way (nothing is pending before round 2)
         if (rc == MI_OK) rc = slot_prepare(d, s, most_bytes, most_seg, d_dst == nullptr);
         if (rc == MI_OK) rc = slot_submit(d, s, r, d_dst);
     }
-    for (u64 r = n_rounds; r < n_rounds + 2 && rc == MI_OK; ++r) rc = slot_finish(d, &d->slot[r & 1], &st, emit, arg);
+    for (u64 r = n_rounds; r < n_rounds + 2 && rc == MI_OK; ++r) rc = slot_finish(d, &d->slot[r & 1], r - 2, &st, emit, arg);
     if (rc != MI_OK) {
         (void)hipStreamSynchronize(d->code);
         (void)hipStreamSynchronize(d->copy);
@@ -457,6 +423,13 @@ static int inflater_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u
     }
     if (st.bytes != d->chain.total) return d->fail(MI_ERR_HIP, "device inflate: the rounds gave %llu bytes, the plan %llu", (unsigned long long)st.bytes,
                                                    (unsigned long long)d->chain.total);
+    if (d->indexed && (st.crc != d->want_crc || (u32)st.bytes != d->want_isize)) {     // a stale index cannot be told from a corrupt blob: zlib decides
+        d->info.verdict = MI_INFLATE_INDEX_REFUSED;
+        d->info.rule = 0;
+        d->fail(kInflateRefused, "the spans gave %llu bytes with CRC-32 %08x, the trailer states %u (mod 2^32) and %08x", (unsigned long long)st.bytes, st.crc,
+                d->want_isize, d->want_crc);
+        return kInflateRefused;
+    }
     if (st.crc != d->want_crc || (u32)st.bytes != d->want_isize)
         return d->fail(MI_ERR_INVALID, "corrupt gzip stream: %llu bytes with CRC-32 %08x, the trailer states %u (mod 2^32) and %08x; the last segment "
                        "lies at input offset %llu (output offset %llu)", (unsigned long long)st.bytes, st.crc, d->want_isize, d->want_crc,
@@ -464,16 +437,18 @@ static int inflater_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* arg, u
     return MI_OK;
 }
 
+extern "C" {
+
 int mi_inflater_run(mi_inflater* d, mi_inflate_emit_fn emit, void* arg) {
     if (!d || !emit) return MI_ERR_INVALID;
-    return inflater_rounds(d, emit, arg, nullptr);
+    return inflate_run_rounds(d, emit, arg, nullptr);
 }
 
 // what lies at d_dst was put there on wait_for (may be NULL: nothing to wait for) -- the rounds begin behind it
 int mi_inflater_run_device(mi_inflater* d, uint8_t* d_dst, hipStream_t wait_for) {
     if (!d || !d_dst) return MI_ERR_INVALID;
     if (wait_for) IFCHK(d, hipStreamSynchronize(wait_for));
-    return inflater_rounds(d, nullptr, nullptr, d_dst);
+    return inflate_run_rounds(d, nullptr, nullptr, d_dst);
 }
 
 void mi_inflater_free(mi_inflater* d) {
@@ -541,6 +516,13 @@ int inflate_tar_emit(void* arg, const uint8_t* bytes, uint64_t n) {
 
 int mi_tar_inflate_ctx(mi_ctx* c, const char* blob_path, const char* tar_path_out, uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256,
                        mi_inflate_info* info, char* err, uint64_t err_cap) {
+    return mi_tar_inflate_ctx_with(c, blob_path, nullptr, 0, tar_path_out, tar_bytes, tar_sha256, blob_sha256, info, err, err_cap);
+}
+
+// index (may be NULL): the blob's index of checkpoints -- a hint: whatever it does not carry through goes the unindexed
+// host way, fell_back 2 when it was refused
+int mi_tar_inflate_ctx_with(mi_ctx* c, const char* blob_path, const uint8_t* index, uint64_t index_bytes, const char* tar_path_out, uint64_t* tar_bytes,
+                            uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap) {
     if (!c || !blob_path) return MI_ERR_INVALID;
     if (info) memset(info, 0, sizeof *info);
     const int fd = open(blob_path, O_RDONLY | O_CLOEXEC);
@@ -558,12 +540,14 @@ int mi_tar_inflate_ctx(mi_ctx* c, const char* blob_path, const char* tar_path_ou
     int rc = mi_inflater_create(c, &d);
     if (rc) { munmap(map, (size_t)n); inflate_put_err(err, err_cap, "mi_tar_inflate_ctx: no stream"); return rc; }
     mi_host::Sha256 sha_blob;
-    rc = mi_inflater_plan(d, (const u8*)map, n, inflate_sha_seen, &sha_blob);
+    rc = index ? mi_inflater_plan_indexed(d, (const u8*)map, n, index, index_bytes, inflate_sha_seen, &sha_blob)
+               : mi_inflater_plan(d, (const u8*)map, n, inflate_sha_seen, &sha_blob);
     if (info) *info = d->info;
-    if (rc == MI_OK && d->info.verdict == MI_INFLATE_NOT_PARALLEL) {     // zlib decides; nothing has been written yet
+    if (rc == MI_OK && d->info.verdict != MI_INFLATE_DONE) {             // zlib decides; nothing has been written yet
+        const u32 fb = d->info.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 1;
         mi_inflater_free(d);
         munmap(map, (size_t)n);
-        if (info) info->fell_back = 1;
+        if (info) info->fell_back = fb;
         return mi_tar_inflate(blob_path, tar_path_out, tar_bytes, tar_sha256, blob_sha256, err, err_cap);
     }
     TarSink sink{-1, mi_host::Sha256(), 0, 0};
@@ -577,6 +561,13 @@ int mi_tar_inflate_ctx(mi_ctx* c, const char* blob_path, const char* tar_path_ou
         }
     } else if (rc == MI_OK) {
         rc = mi_inflater_run(d, inflate_tar_emit, &sink);
+    }
+    if (rc == kInflateRefused) {                                         // (an index only) the spans did not carry through: the partial output
+        const u32 fb = d->info.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 1;   // is gone, and zlib decides whether the blob is corrupt
+        if (info) { *info = d->info; info->fell_back = fb; }
+        mi_inflater_free(d);
+        munmap(map, (size_t)n);
+        return mi_tar_inflate(blob_path, tar_path_out, tar_bytes, tar_sha256, blob_sha256, err, err_cap);
     }
     if (rc == MI_ERR_IO && sink.io_errno) inflate_put_err(err, err_cap, std::string("write ") + tar_path_out + ": " + strerror(sink.io_errno));
     else if (rc && rc != MI_ERR_IO) {

@@ -34,7 +34,10 @@
 // op - dist + (i mod dist) with 0 < dist <= op: inside the segment's own output.  LDS: a primary-table index is masked to the
 // table's bits; a sorted-list index is offset + (code - first) < the number of coded symbols <= the list's size; lens[] is indexed
 // below HLIT + HDIST <= 316 (+ the 19 code-length lengths behind 320); the ring below kInfRing (a token is placed only with
-// 258 bytes of room).  No kernel faults on any input: corrupt input is the normal case for this code.
+// 258 bytes of room).  A SPAN's match (kSpan) may reach before the span: its source is then hist[hist_bytes - back + i], 0 < back =
+// dist - op <= hist_bytes checked before the copy and i < back -- window reads lie in [hist, hist + hist_bytes) only, and the kernel has
+// held [hist, hist + hist_bytes) against the uploaded window area before the decode begins.  No kernel faults on any input: corrupt
+// input -- and a corrupt or stale index -- is the normal case for this code.
 //
 // VISIBILITY.  The workgroup IS the wave.  What one lane wrote (a literal in the ring, a code length) and another lane reads is
 // separated by __syncthreads(): `ring_seen` is the ring's fill at the last barrier, and a match whose source lies at or above it
@@ -224,6 +227,8 @@ struct InfOut {
     u8* out;              // the segment's first output byte
     u32 fill, ring_seen;  // the ring holds out[op - fill, op); below ring_seen it is visible to every lane.  FLUSHED = op - fill:
                           // out[0, flushed) is written and visible to every lane
+    const u8* hist;       // (a span only) the hist_bytes of output in front of the span's first byte, in global memory
+    u32 hist_bytes;
 };
 
 template <bool kWrite>
@@ -238,7 +243,7 @@ static __device__ __forceinline__ void inf_flush(InfOut<kWrite>* o, InfLds* lds,
 }
 
 // the symbols of one fixed or dynamic block whose tables stand; 0 or the rule
-template <bool kWrite>
+template <bool kWrite, bool kSpan = false>
 static __device__ __forceinline__ u32 inf_block(InfBits* b, InfLds* lds, InfOut<kWrite>* o, u64* op_io, u64 limit, u64 nbits, int lane) {
     u64 op = *op_io;
     u32 rule = 0;
@@ -279,9 +284,30 @@ static __device__ __forceinline__ u32 inf_block(InfBits* b, InfLds* lds, InfOut<
             dist = 1 + ((2 + (d & 1)) << e) + inf_take(b, e);
         }
         if (inf_bit(b) > nbits) { rule = mi_host::kInfInputEnds; break; }
-        if ((u64)dist > op) { rule = mi_host::kInfDistance; break; }
+        if (kSpan ? (u64)dist > op + o->hist_bytes : (u64)dist > op) { rule = mi_host::kInfDistance; break; }
         if (op + len > limit) { rule = mi_host::kInfWindow; break; }
-        if (kWrite) {
+        if (kSpan && kWrite && (u64)dist > op) {
+            // (a span only) the source begins in the window: its first `back` bytes are hist[hist_bytes - back, hist_bytes), the
+            // rest -- i mod dist is what it was -- the span's own bytes from 0 on, flushed or in the ring
+            const u32 back = dist - (u32)op, fresh = len < dist ? len : dist;     // (op < dist <= 32 768)
+            const u64 flushed = op - o->fill;
+            if (fresh > back && (u64)(fresh - back) > flushed + o->ring_seen) {
+                __syncthreads();
+                o->ring_seen = o->fill;
+            }
+#pragma nounroll
+            for (u32 i = lane; i < len; i += 64) {
+                const u32 at = i < dist ? i : i % dist;
+                u8 v;
+                if (at < back) v = o->hist[o->hist_bytes - back + at];           // back <= hist_bytes: checked above
+                else {
+                    const u64 p = at - back;
+                    v = p >= flushed ? lds->ring[(u32)(p - flushed)] : o->out[p];
+                }
+                lds->ring[o->fill + i] = v;
+            }
+            o->fill += len;
+        } else if (kWrite) {
             // the match repeats the `dist` bytes in front of op; they lie in out[0, flushed) or in the ring behind it
             const u64 src = op - dist, flushed = op - o->fill;
             const u32 fresh = len < dist ? len : dist;
@@ -374,19 +400,42 @@ static __device__ __forceinline__ void inf_fixed_lengths(InfLds* lds, int lane) 
 }
 
 // the segment from byte `start` of gz[0, n): how it ends.  kWrite: its bytes go to out[0, limit), limit = what the size pass found
-template <bool kWrite>
-static __device__ __forceinline__ InfEnd inf_segment(const u8* __restrict__ gz, u64 n, u64 start, u8* out, u64 limit, InfLds* lds, int lane) {
+//
+// kSpan: the SPAN between two checkpoints of an index (host_inflate_index.h), five differences.  `start` is a BIT of the
+// member; an empty stored block is a block like any other; the span ends where the next block's header would begin at bit
+// sp->end_bit, with exactly `limit` bytes made -- a header that begins behind end_bit, a BFINAL block in front of it and output
+// beyond `limit` are all kInfIndex, "the span does not end where the index says" --; the last span (end_bit 0) ends at its BFINAL
+// block; and a match may reach up to sp->hist_bytes before the span's first byte, into sp->hist (inf_block).
+struct InfSpan { u64 end_bit; const u8* hist; u32 hist_bytes; };
+
+template <bool kWrite, bool kSpan = false>
+static __device__ __forceinline__ InfEnd inf_segment(const u8* __restrict__ gz, u64 n, u64 start, u8* out, u64 limit, InfLds* lds, int lane,
+                                                     const InfSpan* sp = nullptr) {
     InfBits b;
     b.gz = gz;
     b.n = n;
-    inf_seek(&b, start, lane);
-    InfOut<kWrite> o = {out, 0, 0};
+    inf_seek(&b, kSpan ? start / 8 : start, lane);
+    InfOut<kWrite> o = {out, 0, 0, nullptr, 0};
+    if (kSpan) {
+        inf_drop(&b, (u32)start & 7u);                        // (the seek left at least 8 bits)
+        o.hist = sp->hist;
+        o.hist_bytes = sp->hist_bytes;
+    }
     const u64 nbits = n * 8;
     u64 op = 0;
     for (;;) {
+        if (kSpan && sp->end_bit) {
+            if (inf_bit(&b) == sp->end_bit) {
+                inf_flush(&o, lds, op, lane);
+                if (op != limit) return inf_broken(mi_host::kInfIndex, op, inf_bit(&b));
+                return InfEnd{inf_bit(&b) / 8, op, inf_bit(&b), mi_host::kInfSegEnds, 0};
+            }
+            if (inf_bit(&b) > sp->end_bit) return inf_broken(mi_host::kInfIndex, op, inf_bit(&b));
+        }
         inf_need(&b, lane);
         const u32 bfinal = inf_take(&b, 1), btype = inf_take(&b, 2);
         if (inf_bit(&b) > nbits) return inf_broken(mi_host::kInfInputEnds, op, inf_bit(&b));
+        if (kSpan && bfinal && sp->end_bit) return inf_broken(mi_host::kInfIndex, op, inf_bit(&b));
         if (btype == 3) return inf_broken(mi_host::kInfBlockType, op, inf_bit(&b));
         if (btype == 0) {
             inf_drop(&b, (u32)(0 - inf_bit(&b)) & 7u);         // to the byte boundary
@@ -395,12 +444,12 @@ static __device__ __forceinline__ InfEnd inf_segment(const u8* __restrict__ gz, 
             if (inf_bit(&b) > nbits) return inf_broken(mi_host::kInfInputEnds, op, inf_bit(&b));
             if ((len ^ 0xFFFFu) != nlen) return inf_broken(mi_host::kInfStoredLen, op, inf_bit(&b));
             const u64 byte = inf_bit(&b) / 8;
-            if (len == 0 && !bfinal) {
+            if (!kSpan && len == 0 && !bfinal) {
                 inf_flush(&o, lds, op, lane);
                 return InfEnd{byte, op, inf_bit(&b), mi_host::kInfSegEnds, 0};
             }
             if (byte + len > n) return inf_broken(mi_host::kInfInputEnds, op, nbits);
-            if (op + len > limit) return inf_broken(mi_host::kInfWindow, op, inf_bit(&b));
+            if (op + len > limit) return inf_broken(kSpan ? mi_host::kInfIndex : mi_host::kInfWindow, op, inf_bit(&b));
             if (kWrite) {
                 inf_flush(&o, lds, op, lane);
 #pragma nounroll
@@ -415,8 +464,8 @@ static __device__ __forceinline__ InfEnd inf_segment(const u8* __restrict__ gz, 
             else rule = inf_dynamic_header(&b, lds, nbits, lane, &hlit, &hdist);
             if (!rule) rule = inf_tables(lds, hlit, hdist, lane);
             if (rule) return inf_broken(rule, op, inf_bit(&b));
-            rule = inf_block<kWrite>(&b, lds, &o, &op, limit, nbits, lane);
-            if (rule) return inf_broken(rule, op, inf_bit(&b));
+            rule = inf_block<kWrite, kSpan>(&b, lds, &o, &op, limit, nbits, lane);
+            if (rule) return inf_broken(kSpan && rule == mi_host::kInfWindow ? (u32)mi_host::kInfIndex : rule, op, inf_bit(&b));
         }
         if (bfinal) {
             inf_flush(&o, lds, op, lane);

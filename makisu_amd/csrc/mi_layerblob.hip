@@ -100,12 +100,9 @@ int fetch_from_device(void* arg, uint64_t off, void* dst, uint64_t n) {
 
 struct InflaterOwner { mi_inflater* d = nullptr; ~InflaterOwner() { mi_inflater_free(d); } };
 
-}  // namespace
-
-extern "C" {
-
-int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
-                            mi_layer_blob_info* info_out) {
+// mi_batch_add_layer_blob's body; index (may be NULL): the blob's index of checkpoints, a hint
+int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing,
+                   uint8_t* blob_sha256, mi_layer_blob_info* info_out) {
     if (listing) *listing = nullptr;
     if (info_out) memset(info_out, 0, sizeof *info_out);
     if (!b || !blob) return MI_ERR_INVALID;
@@ -116,20 +113,31 @@ int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t 
     int rc = b->window.flush(b);                        // the inline window may hold bytes of earlier small adds
     if (rc) return rc;
     const u8* src = (const u8*)blob;
+    const bool gzip = n >= 2 && src[0] == 0x1f && src[1] == 0x8b;
+    u32 fell_back = 0;
+    // with an index the way up may be gone twice: the spans straight into the arena, and -- the index refused, at the plan or by a span or
+    // the trailer -- everything again as the unindexed call does it (nothing of the batch has changed by then)
+    for (int with_index = gzip && index ? 1 : 0; ; with_index = 0) {
     mi_layer_blob_info info = {};
     mi_host::Sha256 sha;
     InflaterOwner inf;
     std::vector<u8> host_tar;                           // source 2: the tar as zlib gave it
+    src = (const u8*)blob;
     u64 T = n;
     auto t0 = std::chrono::steady_clock::now();
-    if (n >= 2 && src[0] == 0x1f && src[1] == 0x8b) {
+    if (gzip) {
         rc = mi_inflater_create(c, &inf.d);
         if (rc) return rc;
-        rc = mi_inflater_plan(inf.d, src, n, blob_sha256 ? blob_sha_seen : nullptr, &sha);
+        rc = with_index ? mi_inflater_plan_indexed(inf.d, src, n, index, index_bytes, blob_sha256 ? blob_sha_seen : nullptr, &sha)
+                        : mi_inflater_plan(inf.d, src, n, blob_sha256 ? blob_sha_seen : nullptr, &sha);
         mi_inflater_info(inf.d, &info.inflate);
         if (rc) return fail(c, rc, "mi_batch_add_layer_blob: %s", mi_inflater_error(inf.d));
+        if (with_index && info.inflate.verdict != MI_INFLATE_DONE) {
+            fell_back = info.inflate.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 0;
+            continue;
+        }
         if (info.inflate.verdict == MI_INFLATE_DONE) {
-            info.source = 1;
+            info.source = with_index ? 3 : 1;
             T = info.inflate.out_bytes;
             info.ms_upload = std::max(0.0, ms_since(t0) - info.inflate.ms_size);
         } else {
@@ -151,9 +159,13 @@ int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t 
     rc = arena_wait_mapped(c, &b->arena, std::min<u64>(b->arena.bytes, end_aligned + 4096));   // a walk-fed arena is mapped piece by piece
     if (rc) return rc;
     u8* d_tar = b->arena.as<u8>() + at;
-    if (info.source == 1) {
+    if (info.source == 1 || info.source == 3) {
         rc = mi_inflater_run_device(inf.d, d_tar, nullptr);
         mi_inflater_info(inf.d, &info.inflate);
+        if (rc == 1 && with_index) {                    // a verdict: what the spans wrote lies behind arena_used, where nothing counts
+            fell_back = info.inflate.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 0;
+            continue;
+        }
         if (rc) return fail(c, rc, "mi_batch_add_layer_blob: %s", mi_inflater_error(inf.d));
     } else {
         rc = upload_plain(c, d_tar, src, T, info.source == 0 && blob_sha256 ? &sha : nullptr);
@@ -202,14 +214,49 @@ int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t 
         if (ents[i].kind == 1) b->files.push_back({at + offs[i], ents[i].size, tag_base + (u64)ents[i].file_index});
     b->arena_used = at + T;
     b->total_bytes += bytes;
+    if (fell_back) info.inflate.fell_back = fell_back;
     if (blob_sha256) sha.final(blob_sha256);
     if (info_out) *info_out = info;
     if (listing) *listing = tar; else mi_tar_free(tar);
     return MI_OK;
+    }
+}
+
+int add_layer_path(mi_batch* b, const char* blob_path, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
+                   mi_layer_blob_info* info);
+
+}  // namespace
+
+extern "C" {
+
+int mi_batch_add_layer_blob(mi_batch* b, const void* blob, uint64_t n, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
+                            mi_layer_blob_info* info_out) {
+    return add_layer_blob(b, blob, n, nullptr, 0, tag_base, listing, blob_sha256, info_out);
+}
+
+int mi_batch_add_layer_blob_indexed(mi_batch* b, const void* blob, uint64_t n, const void* index, uint64_t index_bytes, uint64_t tag_base,
+                                    mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info_out) {
+    if (!index) { if (listing) *listing = nullptr; if (info_out) memset(info_out, 0, sizeof *info_out); return MI_ERR_INVALID; }
+    return add_layer_blob(b, blob, n, (const u8*)index, index_bytes, tag_base, listing, blob_sha256, info_out);
+}
+
+int mi_batch_add_layer_path_indexed(mi_batch* b, const char* blob_path, const void* index, uint64_t index_bytes, uint64_t tag_base, mi_tar** listing,
+                                    uint8_t* blob_sha256, mi_layer_blob_info* info) {
+    if (!index) { if (listing) *listing = nullptr; if (info) memset(info, 0, sizeof *info); return MI_ERR_INVALID; }
+    return add_layer_path(b, blob_path, (const u8*)index, index_bytes, tag_base, listing, blob_sha256, info);
 }
 
 int mi_batch_add_layer_path(mi_batch* b, const char* blob_path, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
                             mi_layer_blob_info* info) {
+    return add_layer_path(b, blob_path, nullptr, 0, tag_base, listing, blob_sha256, info);
+}
+
+}  // extern "C"
+
+namespace {
+
+int add_layer_path(mi_batch* b, const char* blob_path, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
+                   mi_layer_blob_info* info) {
     if (listing) *listing = nullptr;
     if (info) memset(info, 0, sizeof *info);
     if (!b || !blob_path) return MI_ERR_INVALID;
@@ -223,9 +270,9 @@ int mi_batch_add_layer_path(mi_batch* b, const char* blob_path, uint64_t tag_bas
     const int map_errno = errno;
     close(fd);
     if (map == MAP_FAILED) return fail(c, MI_ERR_IO, "mi_batch_add_layer_path: mmap %s: %s", blob_path, strerror(map_errno));
-    const int rc = mi_batch_add_layer_blob(b, map, n, tag_base, listing, blob_sha256, info);
+    const int rc = add_layer_blob(b, map, n, index, index_bytes, tag_base, listing, blob_sha256, info);
     if (n) munmap(map, (size_t)n);
     return rc;
 }
 
-}  // extern "C"
+}  // namespace

@@ -89,6 +89,17 @@ MI_LOCAL void        mi_inflater_free(mi_inflater* d);
 // there when the call returns
 typedef struct ihipStream_t* hipStream_t;
 MI_LOCAL int         mi_inflater_run_device(mi_inflater* d, uint8_t* d_dst, hipStream_t wait_for);
+// mi_inflate_index.hip -- the plan from an index of checkpoints instead of a size pass: the index is checked on the host,
+// the member and the window area go up, the spans are cut into rounds.  MI_OK with _info's verdict: DONE; NOT_PARALLEL (a span larger
+// than the window); MI_INFLATE_INDEX_REFUSED (the checker's number in info.reserved).  After DONE, _run and _run_device decode the spans;
+// they return 1 -- not an error: _info's verdict is then INDEX_REFUSED (a span broke a rule -- info names it --, or the trailer does not
+// hold) or NOT_PARALLEL (the last span ends before n - 8) and the caller inflates without the index
+MI_LOCAL int         mi_inflater_plan_indexed(mi_inflater* d, const uint8_t* gz, uint64_t n, const uint8_t* index, uint64_t index_bytes,
+                                              mi_inflate_seen_fn seen, void* arg);
+// mi_inflate.hip -- mi_tar_inflate_ctx's body; index (may be NULL): mi_tar_inflate_ctx_indexed's
+MI_LOCAL int         mi_tar_inflate_ctx_with(mi_ctx* ctx, const char* blob_path, const uint8_t* index, uint64_t index_bytes, const char* tar_path_out,
+                                             uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err,
+                                             uint64_t err_cap);
 // mi_tar.hip -- an mi_tar from a tar of tar_bytes that lies on the device: blocks / kinds / dense are what
 // mi_tarscan.hip brought down (n_marked of them; host_tarcache.h), fetch copies tar[off, off + n) to dst for what the cache does
 // not hold (MI_OK, or the listing fails with MI_ERR_IO).  The parser, its errors and its texts are mi_tar_open_ex's (err: the
