@@ -907,6 +907,38 @@ MI_BLOCK int  mi_inflate_buffer_indexed(mi_ctx* ctx, const void* gz, uint64_t n,
 MI_BLOCK int  mi_tar_inflate_ctx_indexed(mi_ctx* ctx, const char* blob_path, const void* index, uint64_t index_bytes, const char* tar_path_out,
                                          uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err,
                                          uint64_t err_cap);
+/* A GZIP MEMBER NOBODY INDEXED: SPECULATIVE SPANS (opt-in; csrc/mi_inflate_spec.hip, csrc/host_inflate_spec.h).  The
+ * first pull of a foreign gzip has no index yet.  These calls make the indexed inflate's span table and window area on the device from
+ * the member alone (pugz's and rapidgzip's technique): the deflate stream behind the header is cut into PIECES of piece_bytes member
+ * bytes (0: 65 536; otherwise 1 024 .. 16 777 216, else MI_ERR_INVALID; doubled until there are at most 16 384 pieces -- the value used
+ * is reported); a finder takes for every piece the smallest bit at which a non-final dynamic block header parses (piece 0: the
+ * stream's start); a speculative pass decodes from every such CANDIDATE without the 32 KiB in front of it, into a ring of markers,
+ * until the next block header that begins at a candidate; the host walks the chain of these spans from the stream's start; a window
+ * pass resolves the markers in chain order.  From there the spans are decoded as an index's are, held to their ends, and the member's
+ * CRC-32 and ISIZE decide.  One route serves every gzip; the marker route of the unindexed calls is not tried first.
+ *
+ * VERDICTS (returned as MI_OK): MI_INFLATE_DONE; MI_INFLATE_NOT_PARALLEL -- a span larger than the window MI_INFLATE_WINDOW_MB (rule
+ * 11), a span of more than 32 x piece_bytes literals and matches that reaches no candidate (rule 13: a stream of fixed blocks; stored
+ * bytes do not count), or a stream that ends before n - 8 (more members); MI_INFLATE_INDEX_REFUSED -- the write pass refused a span
+ * (rule 10: a match reaches before the member's first byte) or the trailer does not hold (rule 0): nothing is delivered and zlib
+ * decides.  A rule broken on a span of the chain in the speculative pass is MI_ERR_INVALID; mi_last_error names the span, the rule
+ * and the bit.
+ *
+ * mi_inflate_buffer_spec: mi_inflate_buffer this way.  The total is known after the plan: MI_ERR_CAPACITY (with *out_bytes = the size
+ * needed) comes before the write pass.  index / index_bytes (both NULL, or both given): with the verdict DONE they receive a MIGZIX01
+ * index of the spans -- the points as planned, the windows as the device made them, the spacing field = the piece_bytes used -- that
+ * passes mi_inflate_index_check and drives every indexed call; free it with mi_inflate_index_free.  It is NOT what
+ * mi_inflate_index_build gives for any spacing: its points are the candidates the chain passed.
+ * mi_tar_inflate_ctx_spec: mi_tar_inflate_ctx this way; on NOT_PARALLEL or INDEX_REFUSED any partial output is removed and
+ * mi_tar_inflate runs (info->fell_back 1 or 2).  A plain tar is copied through.
+ * mi_inflate_spec_info: the piece used, the pieces, the pieces with a candidate, the spans on the chain (before spans without output
+ * are merged into the one in front), the rings' bytes, and the device times of the finder, the speculative pass and the window pass. */
+typedef struct { uint64_t piece_bytes, n_pieces, n_found, n_live, ring_bytes; double ms_find, ms_speculate, ms_windows; } mi_inflate_spec_info;
+MI_BLOCK int  mi_inflate_buffer_spec(mi_ctx* ctx, const void* gz, uint64_t n, uint64_t piece_bytes, void* dst, uint64_t cap, uint64_t* out_bytes,
+                                     mi_inflate_info* info, mi_inflate_spec_info* spec_info, void** index, uint64_t* index_bytes);
+MI_BLOCK int  mi_tar_inflate_ctx_spec(mi_ctx* ctx, const char* blob_path, uint64_t piece_bytes, const char* tar_path_out, uint64_t* tar_bytes,
+                                      uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, mi_inflate_spec_info* spec_info,
+                                      void** index, uint64_t* index_bytes, char* err, uint64_t err_cap);
 /* A PULLED LAYER BECOMES A BATCH (csrc/mi_layerblob.hip, csrc/mi_tarscan.hip, csrc/host_tarcache.h).  The
  * reference fills its tree from a base or cached layer by reading the tar (MemFS.UpdateFromTarPath, lib/snapshot/mem_fs.go:139-161:
  * open, tario.NewGzipReader when the blob is gzip, UpdateFromTarReader).  Everything behind this library's scan takes a batch
@@ -955,6 +987,12 @@ MI_BLOCK int mi_batch_add_layer_blob_indexed(mi_batch* b, const void* blob, uint
                                              uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
 MI_BLOCK int mi_batch_add_layer_path_indexed(mi_batch* b, const char* blob_path, const void* index, uint64_t index_bytes,
                                              uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256, mi_layer_blob_info* info);
+/* ... and with no index at all: the speculative plan takes the index's place and route -- source 4.  On NOT_PARALLEL or
+ * INDEX_REFUSED the batch is as it was and the call proceeds exactly as the unindexed one does (info->inflate.fell_back = 2: refused). */
+MI_BLOCK int mi_batch_add_layer_blob_spec(mi_batch* b, const void* blob, uint64_t n, uint64_t piece_bytes, uint64_t tag_base, mi_tar** listing,
+                                          uint8_t* blob_sha256, mi_layer_blob_info* info, mi_inflate_spec_info* spec_info);
+MI_BLOCK int mi_batch_add_layer_path_spec(mi_batch* b, const char* blob_path, uint64_t piece_bytes, uint64_t tag_base, mi_tar** listing,
+                                          uint8_t* blob_sha256, mi_layer_blob_info* info, mi_inflate_spec_info* spec_info);
 /* step.commitLayer (lib/builder/step/common.go:67-111) in one call on a MemFS handle: the step's layer by scan
  * (must_scan: the root is walked here, with the handle's blacklist) or by its copy operations, written through the layer
  * writer configured by cfg (tarAndGzipDiffs: tar framing, TarDigest, the gzip leg with its digest and size), folded into

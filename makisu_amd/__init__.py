@@ -391,6 +391,14 @@ class InflateIndexInfo(C.Structure):
                 ("spacing", C.c_uint64), ("ms_build", C.c_double)]
 
 
+class InflateSpecInfo(C.Structure):
+    _fields_ = [("piece_bytes", C.c_uint64), ("n_pieces", C.c_uint64), ("n_found", C.c_uint64), ("n_live", C.c_uint64),
+                ("ring_bytes", C.c_uint64), ("ms_find", C.c_double), ("ms_speculate", C.c_double), ("ms_windows", C.c_double)]
+
+
+INFLATE_SPEC_PIECE = 65536
+
+
 class LayerBlobInfo(C.Structure):
     _fields_ = [("tar_bytes", C.c_uint64), ("arena_at", C.c_uint64), ("first_file", C.c_uint64), ("n_files", C.c_uint64),
                 ("n_entries", C.c_uint64), ("n_marked", C.c_uint64), ("n_live", C.c_uint64), ("n_fetched", C.c_uint64),
@@ -400,10 +408,15 @@ class LayerBlobInfo(C.Structure):
 
 LAYER_SOURCE_TAR, LAYER_SOURCE_DEVICE_GZIP, LAYER_SOURCE_ZLIB = 0, 1, 2
 LAYER_SOURCE_INDEXED_GZIP = 3
+LAYER_SOURCE_SPEC_GZIP = 4
 
 
 def _inflate_info_dict(info):
     return dict((f, getattr(info, f)) for f, _ in InflateInfo._fields_ if f != "reserved")
+
+
+def _spec_info_dict(spec):
+    return dict((f, getattr(spec, f)) for f, _ in InflateSpecInfo._fields_)
 
 
 def _indexed_info_dict(info):
@@ -547,6 +560,12 @@ def load_library(rebuild=False):
         "mi_inflate_index_refusal": ([C.c_int], C.c_char_p),
         "mi_inflate_buffer_indexed": ([vp, vp, u64, vp, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateInfo)], C.c_int),
         "mi_tar_inflate_ctx_indexed": ([vp, C.c_char_p, vp, u64, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.c_char_p, u64], C.c_int),
+        "mi_inflate_buffer_spec": ([vp, vp, u64, u64, vp, u64, C.POINTER(u64), C.POINTER(InflateInfo), C.POINTER(InflateSpecInfo), C.POINTER(vp),
+                                    C.POINTER(u64)], C.c_int),
+        "mi_tar_inflate_ctx_spec": ([vp, C.c_char_p, u64, C.c_char_p, u64p, vp, vp, C.POINTER(InflateInfo), C.POINTER(InflateSpecInfo), C.POINTER(vp),
+                                     C.POINTER(u64), C.c_char_p, u64], C.c_int),
+        "mi_batch_add_layer_blob_spec": ([vp, vp, u64, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo), C.POINTER(InflateSpecInfo)], C.c_int),
+        "mi_batch_add_layer_path_spec": ([vp, C.c_char_p, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo), C.POINTER(InflateSpecInfo)], C.c_int),
         "mi_batch_add_layer_blob_indexed": ([vp, vp, u64, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
         "mi_batch_add_layer_path_indexed": ([vp, C.c_char_p, vp, u64, u64, C.POINTER(vp), vp, C.POINTER(LayerBlobInfo)], C.c_int),
         "mi_layer_header_bytes": ([C.POINTER(TreeEntry), C.c_uint32, vp, u64, u64p], C.c_int),
@@ -2046,6 +2065,58 @@ class Engine:
             raise MiError(rc, "mi_tar_inflate_ctx_indexed: %s" % err.value.decode(errors="replace"))
         return {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g), "info": _indexed_info_dict(info)}
 
+    def _spec_index(self, p, n):
+        """the index a spec call returned (or None), copied and freed"""
+        if not p.value:
+            return None
+        try:
+            return C.string_at(p.value, n.value)
+        finally:
+            self._lib.mi_inflate_index_free(p)
+
+    def inflate_buffer_spec(self, blob, piece_bytes=0, want_index=False):
+        """mi_inflate_buffer_spec: one whole gzip member nobody indexed -> (its inflation, info dict, spec dict[, the index]).  The span
+        table and the windows are made on the device from the member alone (piece_bytes: 0 = INFLATE_SPEC_PIECE).  info["verdict"] is
+        INFLATE_DONE, or INFLATE_NOT_PARALLEL / INFLATE_INDEX_REFUSED with b"" (the caller inflates serially); a member whose live span
+        breaks a rule raises MiError(-1).  want_index: a fourth value, the MIGZIX01 index of the spans (None unless DONE) -- it drives
+        every indexed call"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        n, info, spec = C.c_uint64(), InflateInfo(), InflateSpecInfo()
+        cap = 0
+        for _ in range(2):
+            out = np.zeros(max(cap, 1), dtype=np.uint8)
+            p, nb = C.c_void_p(), C.c_uint64()
+            rc = self._lib.mi_inflate_buffer_spec(self._h, src.ctypes.data if src.size else None, src.size, piece_bytes, out.ctypes.data, cap,
+                                                  C.byref(n), C.byref(info), C.byref(spec), C.byref(p) if want_index else None,
+                                                  C.byref(nb) if want_index else None)
+            if rc != -7:                                # MI_ERR_CAPACITY: *out_bytes is the size needed
+                break
+            cap = n.value
+        ix = self._spec_index(p, nb)
+        self._check(rc)
+        res = (out[:n.value].tobytes(), _indexed_info_dict(info), _spec_info_dict(spec))
+        return res + (ix,) if want_index else res
+
+    def tar_inflate_spec(self, blob_path, tar_path_out=None, piece_bytes=0, want_index=False):
+        """mi_tar_inflate_ctx_spec: Engine.tar_inflate through speculative spans -- the first pull of a blob that has no index yet
+        (info["fell_back"]: 1 not parallel, 2 refused in the write pass: the blob went through the host path).  -> tar_inflate's dict +
+        "spec" and, with want_index, "index" (None when the call fell back)"""
+        nb, info, spec = C.c_uint64(), InflateInfo(), InflateSpecInfo()
+        t, g = (C.c_uint8 * 32)(), (C.c_uint8 * 32)()
+        err = C.create_string_buffer(512)
+        p, n = C.c_void_p(), C.c_uint64()
+        rc = self._lib.mi_tar_inflate_ctx_spec(self._h, os.fsencode(blob_path), piece_bytes, os.fsencode(tar_path_out) if tar_path_out is not None else None,
+                                               C.byref(nb), t, g, C.byref(info), C.byref(spec), C.byref(p) if want_index else None,
+                                               C.byref(n) if want_index else None, err, len(err))
+        ix = self._spec_index(p, n)
+        if rc:
+            raise MiError(rc, "mi_tar_inflate_ctx_spec: %s" % err.value.decode(errors="replace"))
+        res = {"tar_bytes": nb.value, "tar_digest": Digest.from_raw(t), "blob_digest": Digest.from_raw(g), "info": _indexed_info_dict(info),
+               "spec": _spec_info_dict(spec)}
+        if want_index:
+            res["index"] = ix
+        return res
+
     def index(self, capacity_hint=0):
         """A chunk-digest set that outlives batches (dedup across layers)."""
         return ChunkIndex(self, capacity_hint)
@@ -2347,6 +2418,26 @@ class Batch:
         keep_ix = ix if ix.size else np.zeros(1, dtype=np.uint8)
         return self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_path_indexed(self._h, os.fsencode(path), keep_ix.ctypes.data, ix.size,
                                                                                                tag_base, C.byref(h), sha, C.byref(info)))
+
+    def add_layer_blob_spec(self, blob, tag_base=0, piece_bytes=0):
+        """mi_batch_add_layer_blob_spec: add_layer_blob for a gzip nobody indexed -- the speculative plan takes the index's place:
+        info["source"] is LAYER_SOURCE_SPEC_GZIP when its spans were decoded straight into the arena (info["spec"]: the plan's figures);
+        not parallel or refused, the batch is as it was and the call goes on as add_layer_blob does"""
+        src = np.frombuffer(bytes(blob), dtype=np.uint8)
+        keep = src if src.size else np.zeros(1, dtype=np.uint8)
+        spec = InflateSpecInfo()
+        res = self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_blob_spec(self._h, keep.ctypes.data, src.size, piece_bytes, tag_base,
+                                                                                          C.byref(h), sha, C.byref(info), C.byref(spec)))
+        res[2]["spec"] = _spec_info_dict(spec)
+        return res
+
+    def add_layer_path_spec(self, path, tag_base=0, piece_bytes=0):
+        """mi_batch_add_layer_path_spec: add_layer_blob_spec for a blob file, mapped by the library"""
+        spec = InflateSpecInfo()
+        res = self._add_layer(lambda h, sha, info: self._lib.mi_batch_add_layer_path_spec(self._h, os.fsencode(path), piece_bytes, tag_base, C.byref(h),
+                                                                                          sha, C.byref(info), C.byref(spec)))
+        res[2]["spec"] = _spec_info_dict(spec)
+        return res
 
     def _add_layer(self, call):
         h, sha, info = C.c_void_p(), (C.c_uint8 * 32)(), LayerBlobInfo()

@@ -12,7 +12,7 @@ SOURCES = ["mi_api.hip", "mi_readback.hip", "mi_group.hip", "gear_cdc.hip", "sha
            "mi_index.hip", "mi_alloc.hip", "mi_arena.hip", "mi_tar.hip", "mi_stage.hip", "mi_layer.hip", "mi_copyops.hip", "mi_memfs.hip", "mi_commit.hip", "mi_pack.hip",
            "mi_slot_table.hip", "mi_restore.hip", "mi_fetch.hip", "mi_zpack.hip", "mi_zset.hip", "mi_zbatch.hip", "mi_zprune.hip", "mi_zpack2.hip",
            "mi_zrecode.hip", "mi_zentropy.hip", "mi_zserve.hip", "mi_zage.hip", "mi_deflate.hip", "mi_inflate.hip", "mi_tarscan.hip",
-           "mi_layerblob.hip", "mi_inflate_index.hip"]
+           "mi_layerblob.hip", "mi_inflate_index.hip", "mi_inflate_spec.hip"]
 # every header there is, listed from the directories: a new one cannot be forgotten
 INCLUDE = os.path.join(HERE, "..", "include")
 HEADERS = sorted(os.path.join(d, h) for d in (CSRC, INCLUDE) for h in os.listdir(d) if h.endswith(".h"))

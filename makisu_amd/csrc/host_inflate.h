@@ -30,6 +30,7 @@ enum InflateRule : uint32_t {
     kInfDistance = 10,        // a distance that reaches before the segment's first byte
     kInfWindow = 11,          // output beyond the window
     kInfIndex = 12,           // (a span of an index, host_inflate_index.h) the span does not end where the index says
+    kInfSymbolCap = 13,       // (a speculative span, host_inflate_spec.h) more symbols than the cap without reaching a candidate
 };
 
 static inline const char* inflate_rule_name(uint32_t rule) {
@@ -39,7 +40,8 @@ static inline const char* inflate_rule_name(uint32_t rule) {
                                         "a literal/length or distance code that is over-subscribed or incomplete",
                                         "a symbol that does not exist", "input that ends inside a block",
                                         "a distance that reaches before the segment's first byte", "output beyond the window",
-                                        "the span does not end where the index says"};
+                                        "the span does not end where the index says",
+                                        "more symbols than the speculative pass allows without reaching a block start it found"};
     return rule < sizeof names / sizeof names[0] ? names[rule] : "?";
 }
 

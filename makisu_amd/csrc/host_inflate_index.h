@@ -13,6 +13,10 @@
 //                      u32 win_bytes = min(32 768, out_at) | u32 zero
 //   the window area    each window: the win_bytes of output in front of its point, raw, zero-padded to 16; in the points' order
 //
+// (An index may also come out of a speculative plan -- mi_inflate_buffer_spec, DESIGN 4.23: the same format, passes the same checker and
+// drives the same calls, but its points are the candidates that plan's chain passed and its spacing field is the piece used.  It is NOT
+// the builder's index for any spacing.)
+//
 // THE POINT RULE.  Point 0 is (8 * header length, 0) with no window.  After every non-final block, ending at bit b with output o: if
 // o - the last point's out_at >= spacing, (b, o) is a new point.  An empty stored block is a block like any other.  Spacing 0 means
 // kIndexSpacing; spacing 1 makes every boundary at which output has advanced a point.  A point at which the output is already

@@ -253,6 +253,18 @@ void launch_inflate_write(const u8* d_gz, u64 n, const u64* d_seg, u64 n_seg, u6
 // 4-byte aligned; nothing is launched for an empty list
 void launch_inflate_spans(const u8* d_gz, u64 n, const u64* d_span, u64 n_span, u64 round_bytes, u8* d_out, const u8* d_hist, u64 hist_total,
                           u64* d_bad, void* d_verdict, hipStream_t s);
+// mi_inflate_spec.hip, for tests/kernel_probe too: the three kernels of the speculative inflate, each alone.  FIND: d_cand
+// takes one candidate bit (or ~0) for each of the n_pieces pieces of `piece` bytes behind the header of hdr bytes.  SPECULATE: one wave a
+// candidate that is a bit of the stream; d_rings holds 32 768 u16 entries a piece, d_rows 32 bytes a piece (host_inflate.h InflateRow,
+// `end` a bit; a row nobody wrote stays what it was); window and cap: the most output and the most symbols of a span.  WINDOWS: d_live
+// holds five words a live span (out_at, out_bytes, its window's offset in d_hist, the window's bytes, the piece whose ring holds its
+// output); *d_bad, ~0 before, takes the first span whose words do not fit.  Nothing is launched for a shape that is none (no piece,
+// a header that leaves no stream)
+void launch_inflate_find(const u8* d_gz, u64 n, u64 hdr, u64 piece, u64 n_pieces, u64* d_cand, hipStream_t s);
+void launch_inflate_speculate(const u8* d_gz, u64 n, u64 hdr, u64 piece, u64 n_pieces, const u64* d_cand, u64 window, u64 cap, uint16_t* d_rings,
+                              void* d_rows, hipStream_t s);
+void launch_inflate_spec_windows(const uint16_t* d_rings, u64 n_rings, const u64* d_live, u64 n_live, u8* d_hist, u64 hist_total, u64* d_bad,
+                                 hipStream_t s);
 u32 crc32_host_bytes(u32 crc, const void* data, size_t len);
 u32 crc32_host_combine(u32 crc1, u32 crc2, u64 len2);
 // d_table: 2 x cap_pow2 words (rep | complemented minima), cleared here with one memset

@@ -519,10 +519,18 @@ int mi_tar_inflate_ctx(mi_ctx* c, const char* blob_path, const char* tar_path_ou
     return mi_tar_inflate_ctx_with(c, blob_path, nullptr, 0, tar_path_out, tar_bytes, tar_sha256, blob_sha256, info, err, err_cap);
 }
 
-// index (may be NULL): the blob's index of checkpoints (DESIGN 4.22) -- a hint: whatever it does not carry through goes the unindexed
-// host way, fell_back 2 when it was refused
 int mi_tar_inflate_ctx_with(mi_ctx* c, const char* blob_path, const uint8_t* index, uint64_t index_bytes, const char* tar_path_out, uint64_t* tar_bytes,
                             uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap) {
+    return tar_inflate_ctx_route(c, blob_path, index, index_bytes, nullptr, tar_path_out, tar_bytes, tar_sha256, blob_sha256, info, err, err_cap);
+}
+
+}  // extern "C"
+
+// index (may be NULL): the blob's index of checkpoints (DESIGN 4.22) -- a hint: whatever it does not carry through goes the unindexed
+// host way, fell_back 2 when it was refused.  spec (may be NULL; no index then): the plan from speculative spans, a hint
+// in the same way
+int mi::tar_inflate_ctx_route(mi_ctx* c, const char* blob_path, const u8* index, u64 index_bytes, const InfSpecAsk* spec, const char* tar_path_out,
+                              uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap) {
     if (!c || !blob_path) return MI_ERR_INVALID;
     if (info) memset(info, 0, sizeof *info);
     const int fd = open(blob_path, O_RDONLY | O_CLOEXEC);
@@ -540,9 +548,11 @@ int mi_tar_inflate_ctx_with(mi_ctx* c, const char* blob_path, const uint8_t* ind
     int rc = mi_inflater_create(c, &d);
     if (rc) { munmap(map, (size_t)n); inflate_put_err(err, err_cap, "mi_tar_inflate_ctx: no stream"); return rc; }
     mi_host::Sha256 sha_blob;
-    rc = index ? mi_inflater_plan_indexed(d, (const u8*)map, n, index, index_bytes, inflate_sha_seen, &sha_blob)
+    rc = spec  ? mi_inflater_plan_spec(d, (const u8*)map, n, spec->piece_bytes, inflate_sha_seen, &sha_blob)
+       : index ? mi_inflater_plan_indexed(d, (const u8*)map, n, index, index_bytes, inflate_sha_seen, &sha_blob)
                : mi_inflater_plan(d, (const u8*)map, n, inflate_sha_seen, &sha_blob);
     if (info) *info = d->info;
+    if (spec && spec->spec_info) *spec->spec_info = d->spec;
     if (rc == MI_OK && d->info.verdict != MI_INFLATE_DONE) {             // zlib decides; nothing has been written yet
         const u32 fb = d->info.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 1;
         mi_inflater_free(d);
@@ -574,6 +584,10 @@ int mi_tar_inflate_ctx_with(mi_ctx* c, const char* blob_path, const uint8_t* ind
         inflate_put_err(err, err_cap, std::string(blob_path) + ": " + d->err);
         fail(c, rc, "mi_tar_inflate_ctx: %s: %s", blob_path, d->err.c_str());
     }
+    if (rc == MI_OK && spec && spec->index) {                            // the first pull leaves its index behind
+        rc = inflate_spec_index(d, spec->index, spec->index_bytes);
+        if (rc) { inflate_put_err(err, err_cap, std::string(blob_path) + ": " + d->err); if (tar_path_out) unlink(tar_path_out); }
+    }
     if (info) { const u32 fb = info->fell_back; *info = d->info; info->fell_back = fb; }
     mi_inflater_free(d);
     munmap(map, (size_t)n);
@@ -583,5 +597,3 @@ int mi_tar_inflate_ctx_with(mi_ctx* c, const char* blob_path, const uint8_t* ind
     if (blob_sha256) sha_blob.final(blob_sha256);
     return MI_OK;
 }
-
-}  // extern "C"

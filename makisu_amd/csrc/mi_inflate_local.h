@@ -24,6 +24,9 @@ struct InfSlot {
     bool pending = false;
 };
 
+//  what a call that plans speculatively asks for: the piece, and where the plan's figures and its index go (each may be NULL)
+struct InfSpecAsk { u64 piece_bytes; mi_inflate_spec_info* spec_info; void** index; u64* index_bytes; };
+
 constexpr int kInflateRefused = 1;                      // (spans) inflate_run_rounds: a span broke a rule or the trailer does not hold; d->info says which
 
 }  // namespace mi
@@ -50,6 +53,9 @@ struct mi_inflater {
     std::vector<mi::u64> spans;
     mi::DevBuf d_hist;
     mi::u64 hist_bytes = 0;
+    // the plan from speculative spans (mi_inflate_spec.hip): an indexed plan whose table and windows were made on the device
+    bool spec_plan = false;
+    mi_inflate_spec_info spec = {};
     ~mi_inflater() {                                    // nothing is under way when the buffers and events go
         if (code) (void)hipStreamSynchronize(code);
         if (copy) (void)hipStreamSynchronize(copy);
@@ -85,5 +91,10 @@ MI_LOCAL int inflate_run_rounds(mi_inflater* d, mi_inflate_emit_fn emit, void* a
 // round's bad span `k` comes down and becomes d->info -- kInflateRefused
 MI_LOCAL int inflate_span_submit(mi_inflater* d, InfSlot* s, u64 a, u64 b, u64 base, u64 bytes, u8* out);
 MI_LOCAL int inflate_span_refused(mi_inflater* d, InfSlot* s, u64 round_first, u64 k);
+// mi_inflate_spec.hip.  spec_index: a speculative plan that was run to DONE as a MIGZIX01 index (malloc'ed), the windows brought down
+MI_LOCAL int inflate_spec_index(mi_inflater* d, void** index, u64* index_bytes);
+// mi_inflate.hip.  mi_tar_inflate_ctx's body -- index (may be NULL): mi_tar_inflate_ctx_indexed's; spec (may be NULL): mi_tar_inflate_ctx_spec's
+MI_LOCAL int tar_inflate_ctx_route(mi_ctx* c, const char* blob_path, const u8* index, u64 index_bytes, const InfSpecAsk* spec, const char* tar_path_out,
+                                   uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err, uint64_t err_cap);
 
 }  // namespace mi

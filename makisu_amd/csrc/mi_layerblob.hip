@@ -7,6 +7,7 @@
 // Order of work: checks, window.flush | the source from the first two bytes, the plan of a gzip blob with the blob's SHA-256
 // taken while it goes up | the reservation behind what the arena holds | the bytes | the header pass and the listing | the batch.
 #include "mi_internal.h"
+#include "mi_inflate_local.h"
 #include "mi_tarscan.h"
 #include "host_sha256.h"
 
@@ -100,9 +101,10 @@ int fetch_from_device(void* arg, uint64_t off, void* dst, uint64_t n) {
 
 struct InflaterOwner { mi_inflater* d = nullptr; ~InflaterOwner() { mi_inflater_free(d); } };
 
-// mi_batch_add_layer_blob's body; index (may be NULL): the blob's index of checkpoints, a hint
+// mi_batch_add_layer_blob's body; index (may be NULL): the blob's index of checkpoints, a hint; spec (may be NULL; no index
+// then): the plan from speculative spans takes the index's place and route -- source 4
 int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing,
-                   uint8_t* blob_sha256, mi_layer_blob_info* info_out) {
+                   uint8_t* blob_sha256, mi_layer_blob_info* info_out, const InfSpecAsk* spec = nullptr) {
     if (listing) *listing = nullptr;
     if (info_out) memset(info_out, 0, sizeof *info_out);
     if (!b || !blob) return MI_ERR_INVALID;
@@ -117,7 +119,7 @@ int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u
     u32 fell_back = 0;
     // with an index the way up may be gone twice: the spans straight into the arena, and -- the index refused, at the plan or by a span or
     // the trailer -- everything again as the unindexed call does it (nothing of the batch has changed by then)
-    for (int with_index = gzip && index ? 1 : 0; ; with_index = 0) {
+    for (int with_index = gzip && (index || spec) ? 1 : 0; ; with_index = 0) {
     mi_layer_blob_info info = {};
     mi_host::Sha256 sha;
     InflaterOwner inf;
@@ -128,16 +130,18 @@ int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u
     if (gzip) {
         rc = mi_inflater_create(c, &inf.d);
         if (rc) return rc;
-        rc = with_index ? mi_inflater_plan_indexed(inf.d, src, n, index, index_bytes, blob_sha256 ? blob_sha_seen : nullptr, &sha)
-                        : mi_inflater_plan(inf.d, src, n, blob_sha256 ? blob_sha_seen : nullptr, &sha);
+        rc = with_index && spec ? mi_inflater_plan_spec(inf.d, src, n, spec->piece_bytes, blob_sha256 ? blob_sha_seen : nullptr, &sha)
+           : with_index         ? mi_inflater_plan_indexed(inf.d, src, n, index, index_bytes, blob_sha256 ? blob_sha_seen : nullptr, &sha)
+                                : mi_inflater_plan(inf.d, src, n, blob_sha256 ? blob_sha_seen : nullptr, &sha);
         mi_inflater_info(inf.d, &info.inflate);
+        if (with_index && spec && spec->spec_info) mi_inflater_spec_info(inf.d, spec->spec_info);
         if (rc) return fail(c, rc, "mi_batch_add_layer_blob: %s", mi_inflater_error(inf.d));
         if (with_index && info.inflate.verdict != MI_INFLATE_DONE) {
             fell_back = info.inflate.verdict == MI_INFLATE_INDEX_REFUSED ? 2 : 0;
             continue;
         }
         if (info.inflate.verdict == MI_INFLATE_DONE) {
-            info.source = with_index ? 3 : 1;
+            info.source = with_index ? (spec ? 4 : 3) : 1;
             T = info.inflate.out_bytes;
             info.ms_upload = std::max(0.0, ms_since(t0) - info.inflate.ms_size);
         } else {
@@ -159,7 +163,7 @@ int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u
     rc = arena_wait_mapped(c, &b->arena, std::min<u64>(b->arena.bytes, end_aligned + 4096));   // a walk-fed arena is mapped piece by piece
     if (rc) return rc;
     u8* d_tar = b->arena.as<u8>() + at;
-    if (info.source == 1 || info.source == 3) {
+    if (info.source == 1 || info.source == 3 || info.source == 4) {
         rc = mi_inflater_run_device(inf.d, d_tar, nullptr);
         mi_inflater_info(inf.d, &info.inflate);
         if (rc == 1 && with_index) {                    // a verdict: what the spans wrote lies behind arena_used, where nothing counts
@@ -223,7 +227,7 @@ int add_layer_blob(mi_batch* b, const void* blob, uint64_t n, const u8* index, u
 }
 
 int add_layer_path(mi_batch* b, const char* blob_path, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
-                   mi_layer_blob_info* info);
+                   mi_layer_blob_info* info, const InfSpecAsk* spec = nullptr);
 
 }  // namespace
 
@@ -251,12 +255,26 @@ int mi_batch_add_layer_path(mi_batch* b, const char* blob_path, uint64_t tag_bas
     return add_layer_path(b, blob_path, nullptr, 0, tag_base, listing, blob_sha256, info);
 }
 
+int mi_batch_add_layer_blob_spec(mi_batch* b, const void* blob, uint64_t n, uint64_t piece_bytes, uint64_t tag_base, mi_tar** listing,
+                                 uint8_t* blob_sha256, mi_layer_blob_info* info_out, mi_inflate_spec_info* spec_info) {
+    if (spec_info) memset(spec_info, 0, sizeof *spec_info);
+    const InfSpecAsk ask = {piece_bytes, spec_info, nullptr, nullptr};
+    return add_layer_blob(b, blob, n, nullptr, 0, tag_base, listing, blob_sha256, info_out, &ask);
+}
+
+int mi_batch_add_layer_path_spec(mi_batch* b, const char* blob_path, uint64_t piece_bytes, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
+                                 mi_layer_blob_info* info, mi_inflate_spec_info* spec_info) {
+    if (spec_info) memset(spec_info, 0, sizeof *spec_info);
+    const InfSpecAsk ask = {piece_bytes, spec_info, nullptr, nullptr};
+    return add_layer_path(b, blob_path, nullptr, 0, tag_base, listing, blob_sha256, info, &ask);
+}
+
 }  // extern "C"
 
 namespace {
 
 int add_layer_path(mi_batch* b, const char* blob_path, const u8* index, u64 index_bytes, uint64_t tag_base, mi_tar** listing, uint8_t* blob_sha256,
-                   mi_layer_blob_info* info) {
+                   mi_layer_blob_info* info, const InfSpecAsk* spec) {
     if (listing) *listing = nullptr;
     if (info) memset(info, 0, sizeof *info);
     if (!b || !blob_path) return MI_ERR_INVALID;
@@ -270,7 +288,7 @@ int add_layer_path(mi_batch* b, const char* blob_path, const u8* index, u64 inde
     const int map_errno = errno;
     close(fd);
     if (map == MAP_FAILED) return fail(c, MI_ERR_IO, "mi_batch_add_layer_path: mmap %s: %s", blob_path, strerror(map_errno));
-    const int rc = add_layer_blob(b, map, n, index, index_bytes, tag_base, listing, blob_sha256, info);
+    const int rc = add_layer_blob(b, map, n, index, index_bytes, tag_base, listing, blob_sha256, info, spec);
     if (n) munmap(map, (size_t)n);
     return rc;
 }

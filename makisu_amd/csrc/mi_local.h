@@ -96,6 +96,13 @@ MI_LOCAL int         mi_inflater_run_device(mi_inflater* d, uint8_t* d_dst, hipS
 // hold) or NOT_PARALLEL (the last span ends before n - 8) and the caller inflates without the index
 MI_LOCAL int         mi_inflater_plan_indexed(mi_inflater* d, const uint8_t* gz, uint64_t n, const uint8_t* index, uint64_t index_bytes,
                                               mi_inflate_seen_fn seen, void* arg);
+// mi_inflate_spec.hip -- the plan from SPECULATIVE SPANS: no index is given, the span table and the window area are made on
+// the device from the member alone (piece_bytes: 0 or 1 024 .. 16 777 216, else MI_ERR_INVALID).  MI_OK with _info's verdict: DONE (an
+// indexed plan: _run and _run_device as above, a refusal there is INDEX_REFUSED); NOT_PARALLEL (a span beyond the window or the symbol
+// cap, more members).  A broken rule on a live span is MI_ERR_INVALID naming the span, the rule and the bit.  _spec_info: the pieces,
+// the candidates found, the live spans, the three passes' device times
+MI_LOCAL int         mi_inflater_plan_spec(mi_inflater* d, const uint8_t* gz, uint64_t n, uint64_t piece_bytes, mi_inflate_seen_fn seen, void* arg);
+MI_LOCAL void        mi_inflater_spec_info(const mi_inflater* d, mi_inflate_spec_info* out);
 // mi_inflate.hip -- mi_tar_inflate_ctx's body; index (may be NULL): mi_tar_inflate_ctx_indexed's
 MI_LOCAL int         mi_tar_inflate_ctx_with(mi_ctx* ctx, const char* blob_path, const uint8_t* index, uint64_t index_bytes, const char* tar_path_out,
                                              uint64_t* tar_bytes, uint8_t* tar_sha256, uint8_t* blob_sha256, mi_inflate_info* info, char* err,
