@@ -17,8 +17,12 @@
 // run of it.
 //   1. a lane streams its run straight from HBM in 128-byte pieces (8 x 16 B loads
 //      = exactly one cache line, touched once), the next piece in flight while the
-//      current one is hashed; it warms h over the 64 bytes before its run (6 % extra
-//      reads, L2 hits: they are the previous lane's last line);
+//      current one is hashed.  The bitmap-free kernels read NOTHING in front of a run (deferred heads,
+//      mark_tile_loaded): a lane rolls its first 64 bytes untested, and tests them last, from the hash its
+//      left neighbour hands up; only lane 0 of a tile inside a file loads the 64 bytes before it.  The bitmap
+//      kernels still warm h over the 64 bytes before every run -- 6 % extra reads, and NOT L2 hits as rounds
+//      1-3 had it here: half of the previous lane's last line, fetched from HBM a second time (FETCH_SIZE
+//      x1.127 of the file bytes per launch, profiles/r04_gear_ab.txt);
 //   2. the Gear table lives in LDS, replicated and interleaved so lanes that differ in
 //      (lane % copies) never share a bank: the byte-indexed ds_read_b64 lookups -- the
 //      dominant LDS traffic, 8 B per input byte -- are conflict-free with the 32 copies of
@@ -40,7 +44,7 @@
 // a second pass re-selects from the previous group's speculative exit until it meets the
 // speculative cut list again (Gear + min/max re-synchronises within a few chunks), and a
 // per-file pass only walks the groups whose assumption failed (see "large files" below).
-// HBM traffic: every file byte read once (+6 % warm-up, mostly L2 hits), 4 B written
+// HBM traffic: every file byte read once (the bitmap kernels, which see dense tiles only: +6 % warm-up, from HBM), 4 B written
 // per chunk (+ 256 B of candidates per tile and a 40-byte record per group for large files).  Bound: HBM bandwidth / LDS lookup rate.
 #include "mi_common.h"
 
@@ -53,8 +57,9 @@ constexpr int kCopies      = kGearTableCopies;          // Gear table replicas i
 // were measured against this one -- 16 copies with 256-thread workgroups, a VGPR budget for more waves per SIMD, 64- and 32-byte
 // pieces, the marking through an LDS exchange of coalesced loads (mark_tile_coal), raised wave priority, a v_min3 tree, the
 // warm-up line taken from the lane's own run (wrong cuts; an upper bound of what a free warm-up could save) -- live as a patch
-// under tools/experiments/gear_cdc_experiments.patch with their numbers (profiles/r03_gear_ab.txt, r04_gear_ab.txt): the
-// shipped source has no switch that changes a cut.
+// under tools/experiments/gear_cdc_experiments.patch with their numbers (profiles/r03_gear_ab.txt, r04_gear_ab.txt; that last
+// switch alone, for the kernel as it was just before the deferred heads: gear_no_warmup_line.patch,
+// profiles/gear_deferred_heads_ab.txt): the shipped source has no switch that changes a cut.
 constexpr int kFastCopies  = 32;                        // ... in the bitmap-free marking kernels (see below)
 constexpr int kFastWG      = 512;
 constexpr int kFastWaves   = kFastWG / 64;
@@ -107,17 +112,36 @@ __device__ __forceinline__ void cand_push(CandPack& pk, bool& ovf, u32 o) {
     else ovf = true;
 }
 
+// The head pack of the bitmap-free kernels (deferred heads, mark_tile_loaded): the candidates among the FIRST 64 bytes of
+// a lane's run are found last, from the left neighbour's hash, and precede all of pk's: up to four 6-bit run offsets in
+// one more VGPR, the count in bits 29..31.  A run still holds six candidates at the most, head and body together
+// (cand_compact), so what makes a tile dense has not changed.
+__device__ __forceinline__ void head_push(u32& hp, bool& ovf, u32 o) {
+    const u32 c = hp >> 29;
+    if (c < 4) hp = ((c + 1) << 29) | (((hp & 0x3FFFFu) << 6) | o);
+    else ovf = true;
+}
+
 // returns true (wave-uniform) when `list` holds the tile's candidates (tile-relative byte
-// indices, ascending, padded with kNoCand)
-__device__ __forceinline__ bool cand_compact(CandPack pk, bool ovf, u32 run0, int lane, u32* list) {
+// indices, ascending, padded with kNoCand).  kHead: hp holds the lane's head candidates, which come first.
+template <bool kHead = false>
+__device__ __forceinline__ bool cand_compact(CandPack pk, bool ovf, u32 run0, int lane, u32* list, u32 hp = 0) {
     const u32 ca = pk.a >> 30, cb = pk.b >> 30;
-    const u32 cnt = ca + cb;                             // 0..6
+    const u32 ch = kHead ? hp >> 29 : 0u;
+    const u32 cnt = ca + cb + ch;                        // 0..6 (with a head pack up to 10: an overflow past 6)
+    if (kHead) ovf = ovf || cnt > 6u;
     const u64 b0 = __ballot(cnt & 1u), b1 = __ballot(cnt & 2u), b2 = __ballot(cnt & 4u);
     const u32 total = (u32)__popcll(b0) + 2u * (u32)__popcll(b1) + 4u * (u32)__popcll(b2);
     if (__ballot(ovf) || total > 64u) return false;
     const u64 below = (1ull << lane) - 1ull;
-    const u32 first = (u32)__popcll(b0 & below) + 2u * (u32)__popcll(b1 & below) + 4u * (u32)__popcll(b2 & below);
+    u32 first = (u32)__popcll(b0 & below) + 2u * (u32)__popcll(b1 & below) + 4u * (u32)__popcll(b2 & below);
     list[lane] = kNoCand;
+    if (kHead && ch) {                                   // rare: a candidate in the run's first 64 bytes (1 run in 128)
+#pragma unroll
+        for (u32 k = 0; k < 4; ++k)
+            if (k < ch) list[first + k] = run0 + ((hp >> (6 * (ch - 1 - k))) & 63u);
+        first += ch;
+    }
 #pragma unroll
     for (u32 k = 0; k < 3; ++k)                          // field c-1-k of a register holds its k-th (ascending) one
         if (k < ca) list[first + k] = run0 + ((pk.a >> (10 * (ca - 1 - k))) & 1023u);
@@ -196,9 +220,11 @@ __device__ __forceinline__ void load_piece(const u8* p, u32x4 (&d)[kPieceUnits])
 }
 
 // 16 more bytes of a lane's run (run-relative offset `base`): roll, test, record the candidates.
+// skip (a multiple of 16): the lane's window is not complete before run offset `skip`, what the test finds there is
+// dropped -- looked at on the rare path only, the common one is as without it.
 template <int kC, bool kBitmap>
 __device__ __forceinline__ void hash16(u64& h, const u32x4 v, u32 tab, u32 thresh_m1, u32 run0, u32 base,
-                                       u32* bitmap, CandPack& pk, bool& ovf) {
+                                       u32* bitmap, CandPack& pk, bool& ovf, u32 skip = 0) {
     u32 hh[16];
     roll16<kC>(h, v, tab, hh);
     // (a v_min3_u32 chain would be 8 ops instead of the 11 hipcc emits, but it is one dependent
@@ -211,12 +237,28 @@ __device__ __forceinline__ void hash16(u64& h, const u32x4 v, u32 tab, u32 thres
         // beyond the tile's last byte, and at most one lane hashes up to 127 slack bytes)
 #pragma unroll
         for (int k = 0; k < 16; ++k) {
-            if (hh[k] <= thresh_m1) {
+            if (hh[k] <= thresh_m1 && base >= skip) {
                 const u32 pos = run0 + base + (u32)k;    // byte index in tile
                 if (kBitmap) atomicOr(&bitmap[pos >> 5], 1u << (pos & 31));
                 cand_push(pk, ovf, base + (u32)k);
             }
         }
+    }
+}
+
+// 16 bytes of a lane's kept head (run offsets base .. base + 15 < 64) from the left neighbour's hash: the tests that
+// the run's first pass could not make; the candidates go to the head pack.
+template <int kC>
+__device__ __forceinline__ void head16(u64& h, const u32x4 v, u32 tab, u32 thresh_m1, u32 base, u32& hp, bool& ovf) {
+    u32 hh[16];
+    roll16<kC>(h, v, tab, hh);
+    u32 m = 0xFFFFFFFFu;
+#pragma unroll
+    for (int k = 0; k < 16; k += 2) m = min(m, min(hh[k], hh[k + 1]));
+    if (m <= thresh_m1) {
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (hh[k] <= thresh_m1) head_push(hp, ovf, base + (u32)k);
     }
 }
 
@@ -227,13 +269,15 @@ __device__ __forceinline__ void hash16(u64& h, const u32x4 v, u32 tab, u32 thres
 // mark_tile in two steps, so that a kernel can issue a tile's first loads -- which need no table -- before it
 // fills the table: tile_first_loads requests the first piece of the lane's run and the 64 bytes before it,
 // mark_tile_loaded does the rest.
+// kBitmap = false (deferred heads, below): only lane 0 of a tile that does not begin its file requests a warm-up line.
+template <bool kBitmap>
 __device__ __forceinline__ void tile_first_loads(const u8* __restrict__ fptr, u64 ts, u32 tlen, int lane,
                                                  u32x4 (&cur)[kPieceUnits], u32x4 (&wq)[4]) {
     const u32 run0 = (u32)lane * kLaneRun;               // tile-relative start of my run
     if (run0 >= tlen) return;
     const u8* p = fptr + ts + run0;
     load_piece(p, cur);
-    if (ts + run0 != 0) {                                // the window's warm-up: 64 bytes before my run
+    if (kBitmap ? ts + run0 != 0 : (ts != 0 && run0 == 0)) {   // the window's warm-up: 64 bytes before my run
 #pragma unroll
         for (int i = 0; i < 4; ++i) wq[i] = *(const u32x4*)(p - 64 + 16 * i);
     }
@@ -243,10 +287,56 @@ template <int kC, bool kBitmap>
 __device__ __forceinline__ void mark_tile_loaded(const u8* __restrict__ fptr, u64 ts, u32 tlen,
                                                  u32* bitmap, u32 tab, u32 thresh_m1, int lane,
                                                  u32x4 (&cur)[kPieceUnits], const u32x4 (&wq)[4],
-                                                 CandPack& pk, bool& ovf) {
+                                                 CandPack& pk, bool& ovf, u32& hp) {
     pk.a = pk.b = 0;
+    hp = 0;
     ovf = false;
     const u32 run0 = (u32)lane * kLaneRun;
+    if constexpr (!kBitmap) {
+        // DEFERRED HEADS: no lane but a tile's first reads the 64 bytes before its run -- half of the left neighbour's last
+        // cache line, which came from HBM a second time (FETCH_SIZE x1.127 of the file bytes).  h_i depends only on the 64
+        // bytes ending at i, so a lane (1) keeps its first 64 bytes, (2) rolls them from h = 0 WITHOUT testing -- after
+        // byte 63 its window is complete and h exact --, (3) rolls and tests offsets 64 .. run_len - 1 as ever, (4) hands
+        // its last h one lane up: the state the right neighbour's run starts from, (5) rolls its kept head again from the
+        // h it received, now WITH the tests, into the head pack (head_push), which cand_compact writes before the
+        // body's.  The rolls of (2) are the warm-up's; (5) adds 64 rolls and tests per run.  Lane 0 has no left lane: it
+        // starts from h = 0 at a file's first byte and from the 64 bytes before the tile otherwise (one active lane), and
+        // tests from its offset 0.  Only a lane with a full run has a right neighbour with bytes, so the h handed up is
+        // always that of 1 024 whole bytes; a last lane shorter than its head tests slack like any last piece does.
+        // C2 marking 1.222-1.251 -> 1.144-1.152 ms, FETCH_SIZE x1.131 -> x1.004 (profiles/gear_deferred_heads_ab.txt);
+        // 122 VGPRs instead of 108: the sixteen of the kept head must stay under the 128 of four waves per SIMD.
+        const bool active = run0 < tlen;
+        const u8* p = fptr + ts + run0;
+        const u32 run_len = !active ? 0u : tlen - run0 < (u32)kLaneRun ? tlen - run0 : (u32)kLaneRun;
+        const int n_pieces = (int)((run_len + kPiece - 1) / kPiece);
+        u64 h = 0;
+        if (ts != 0 && run0 == 0 && active) {                // a later tile's lane 0: warm the window
+            u32 hw[16];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) roll16<kC>(h, wq[i], tab, hw);
+        }
+        const u32 skip = lane == 0 ? 0u : 64u;
+        u32x4 head[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) head[i] = cur[i];
+        u32x4 nxt[kPieceUnits];
+        for (int pc = 0; pc < n_pieces; ++pc) {
+            if (pc + 1 < n_pieces) load_piece(p + (pc + 1) * kPiece, nxt);   // in flight while hashing
+#pragma unroll
+            for (int g = 0; g < kPieceUnits; ++g)
+                hash16<kC, false>(h, cur[g], tab, thresh_m1, run0, (u32)(pc * kPiece + g * 16), bitmap, pk, ovf, skip);
+#pragma unroll
+            for (int i = 0; i < kPieceUnits; ++i) cur[i] = nxt[i];
+        }
+        // every lane of the wave is here again: lane l - 1's h, once per tile (lane 0 gets its own back and drops it)
+        const u32 lo = __shfl_up((u32)h, 1), hi = __shfl_up((u32)(h >> 32), 1);
+        if (active && lane != 0) {
+            u64 hl = ((u64)hi << 32) | lo;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) head16<kC>(hl, head[i], tab, thresh_m1, (u32)(16 * i), hp, ovf);
+        }
+        return;
+    }
     if (run0 >= tlen) return;
     const u8* p = fptr + ts + run0;
     const u32 run_len = tlen - run0 < (u32)kLaneRun ? tlen - run0 : (u32)kLaneRun;
@@ -282,8 +372,9 @@ __device__ __forceinline__ void mark_tile(const u8* __restrict__ fptr, u64 ts, u
         for (int i = 0; i < kBitmapWords / 4 / 64; ++i) bz[i * 64 + lane] = z;
     }
     u32x4 cur[kPieceUnits], wq[4];
-    tile_first_loads(fptr, ts, tlen, lane, cur, wq);
-    mark_tile_loaded<kC, kBitmap>(fptr, ts, tlen, bitmap, tab, thresh_m1, lane, cur, wq, pk, ovf);
+    u32 hp;                                              // no head pack with a bitmap: stays 0
+    tile_first_loads<kBitmap>(fptr, ts, tlen, lane, cur, wq);
+    mark_tile_loaded<kC, kBitmap>(fptr, ts, tlen, bitmap, tab, thresh_m1, lane, cur, wq, pk, ovf, hp);
 }
 
 // Wave-uniform cut selection over one marked tile.  Every cut is handed to emit(cut) (wave-uniform
@@ -409,7 +500,7 @@ void gear_cdc_small_fast_kernel(const u8* __restrict__ data, const u64* __restri
         slot = seg_slot[s];
     }
     u32x4 cur[kPieceUnits], wq[4];
-    tile_first_loads(data + off, 0, (u32)size, lane, cur, wq);
+    tile_first_loads<false>(data + off, 0, (u32)size, lane, cur, wq);
     load_table_fast(table, gear_table, tid);
     __syncthreads();
     const u32 lane_tab = lds_lane_table<kFastCopies>(table, lane);
@@ -420,8 +511,9 @@ void gear_cdc_small_fast_kernel(const u8* __restrict__ data, const u64* __restri
     if (size) {
         CandPack pk;
         bool ovf;
-        mark_tile_loaded<kFastCopies, false>(data + off, 0, (u32)size, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf);
-        if (!cand_compact(pk, ovf, (u32)lane * kLaneRun, lane, cand_list)) {      // wave-uniform
+        u32 hp;
+        mark_tile_loaded<kFastCopies, false>(data + off, 0, (u32)size, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf, hp);
+        if (!cand_compact<true>(pk, ovf, (u32)lane * kLaneRun, lane, cand_list, hp)) {      // wave-uniform
             if (lane == 0) dense_list[atomicAdd(dense_count, 1u)] = s;
             return;
         }
@@ -596,7 +688,7 @@ void gear_tile_mark_kernel(const u8* __restrict__ data, const u64* __restrict__ 
     }
     const u32 tlen = ts >= size ? 0u : (u32)((size - ts < (u64)kGearTile) ? (size - ts) : (u64)kGearTile);
     u32x4 cur[kPieceUnits], wq[4];
-    tile_first_loads(data + off, ts, tlen, lane, cur, wq);
+    tile_first_loads<false>(data + off, ts, tlen, lane, cur, wq);
     load_table_fast(table, gear_table, tid);
     __syncthreads();
     const u32 lane_tab = lds_lane_table<kFastCopies>(table, lane);
@@ -605,8 +697,9 @@ void gear_tile_mark_kernel(const u8* __restrict__ data, const u64* __restrict__ 
     if (tlen) {
         CandPack pk;
         bool ovf;
-        mark_tile_loaded<kFastCopies, false>(data + off, ts, tlen, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf);
-        fast = cand_compact(pk, ovf, (u32)lane * kLaneRun, lane, cl);
+        u32 hp;
+        mark_tile_loaded<kFastCopies, false>(data + off, ts, tlen, nullptr, lane_tab, p.thresh_m1, lane, cur, wq, pk, ovf, hp);
+        fast = cand_compact<true>(pk, ovf, (u32)lane * kLaneRun, lane, cl, hp);
         __builtin_amdgcn_wave_barrier();
         tile_lists[t * 64 + lane] = fast ? cl[lane] : kNoCand;
     }
